@@ -19,7 +19,15 @@ Other workloads: --workload actor (config C5: MA-PPO actor fused with the obs, t
 --workload greedy (config C3: device greedy-myopic controller, then env.step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--houses H] [--chunk C] [--window W]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, the
+configuration).  --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs; the inputs are seeded, so two builds can be compared array for array).  --full adds
+what the headline figure does not need: cpu_baseline (the oracle timed on this host, before the GPU
+is touched) and roofline (the dominant kernel timed alone after the timed region, at this size and
+above the Infinity Cache; the actor's other arithmetic forms).
 """
 from __future__ import annotations
 
@@ -70,6 +78,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the CPU "
+                         "baselines, the step kernel timed alone (roofline, at 1M houses and above the Infinity "
+                         "Cache), the actor's other arithmetic forms (--workload actor)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its reward row, the state it left, the greedy "
+                         "workload's actions) as DIR/<name>.npy")
     ap.add_argument("--houses", type=int, default=1 << 20,
                     help="houses in the cluster (strong scaling, the default) or per GPU (--scaling weak)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
@@ -86,7 +101,7 @@ def parse():
                     help="kernel-only timing calls (16 x 1024 ticks = 512 timed launches of the 32-tick window kernel)")
     ap.add_argument("--kernel-warm-ticks", type=int, default=2048,
                     help="untimed kernel-only ticks before that timing (the GPU at its steady-state clock)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="cpu_baseline time budget")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="cpu_baseline time budget (--full)")
     ap.add_argument("--clock-warmup", type=float, default=0.0,
                     help="seconds of non-environment device work before the timed region (GPU clock ramp; "
                          "off by default: measured to slow the host side of a short timed region ~3x, "
@@ -99,7 +114,7 @@ def parse():
                     help="warmup runs at least W steps AND at least this many rollout calls of the timed chunk "
                          "size (graph capture + 2 replays: the first replay of a graph and of the host path is "
                          "2-3x slower than the steady state, profiles/r02e_bench20_warmup.log)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline leg")
     ap.add_argument("--gq-band", type=int, default=None, choices=[0, 1],
                     help="greedy: A/B of the predicted band (MDR_OPT_GQ_BAND; default on)")
     ap.add_argument("--step-tpw", type=int, default=None,
@@ -125,7 +140,10 @@ def parse():
                     help="exchange for the sharded path (default: rccl when WORLD_SIZE > 1); "
                          "'rccl' at world 1 exercises the sharded C loop on one GPU; 'host' = the same C loops "
                          "with gloo collectives (ranks may share one GPU: a rehearsal of the multi-GPU line)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    return args
 
 
 def env_props(n_total: int):
@@ -331,6 +349,30 @@ def above_mall(houses: int, args, kern_1m: str) -> dict:
             "timing": "hipExtLaunchKernel events around each 32-tick launch, 8 calls after 4 untimed ones"}
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much in all (.npy headers included)
+
+
+def dump_outputs(dirname: str, arrays: dict, suffix: str = "") -> dict:
+    """Write each array as ``dirname/<name><suffix>.npy``: float64 and float32 as they are, masks
+    and counters as float32 (exact: they are small integers).  Every array gets an equal share of
+    DUMP_BYTES; a larger one is cut to a fixed sample, the elements at a seeded (RandomState(0))
+    sorted choice of flat indices, so two runs with the same arguments write the same elements."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 128  # (a .npy header: 128 bytes)
+    files = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = a.astype(a.dtype if a.dtype in (np.float32, np.float64) else np.float32, copy=False).reshape(-1)
+        total, keep = a.size, share // a.dtype.itemsize
+        if total > keep:
+            a = a[np.sort(np.random.RandomState(0).choice(total, keep, replace=False))]
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+        files[f"{name}{suffix}.npy"] = {"dtype": str(a.dtype), "elements": int(a.size), "of": int(total)}
+    return files
+
+
 def main():
     args = parse()
     import torch
@@ -341,7 +383,7 @@ def main():
     if args.gpus != world and world > 1:
         print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds)  # before this process touches the GPU
     if args.comm == "host":  # (rehearsal: the ranks may share the visible GPUs)
         local = local % max(1, torch.cuda.device_count())
@@ -379,7 +421,8 @@ def main():
     chunks = [chunk] * (args.steps // chunk) + ([args.steps % chunk] if args.steps % chunk else [])
     acts = None
     if args.mode == "buffer":
-        acts = (torch.rand((chunk, n_loc), device=dev) < 0.5).to(torch.uint8)
+        gen = torch.Generator(device=dev).manual_seed(1234 + rank)  # (the same actions from run to run)
+        acts = (torch.rand((chunk, n_loc), device=dev, generator=gen) < 0.5).to(torch.uint8)
     rew = torch.empty((chunk, n_loc), dtype=torch.float64, device=dev)
     dactor = None
     if args.workload == "actor":  # (sharded: the RCCL C loop with the ring-halo exchange per tick)
@@ -491,98 +534,111 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = n_total * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results, before anything else touches the environment
+        last = rew[chunks[-1] - 1]
+        st = sh.host_state()
+        arrays = {"rewards": last, "state_T": st["T"], "state_Tm": st["Tm"], "state_on": st["on"],
+                  "state_lock": st["lock"], "state_sso": st["sso"]}
+        if g_act is not None:
+            arrays["actions"] = g_act
+        dumped = dump_outputs(args.dump_outputs, arrays, "" if world == 1 else f"_rank{rank}")
+    actor_status = None
+    if dactor is not None and not args.full:  # (counts since the last call: --full reads them after its own launches)
+        actor_status = dactor.status()
 
-    # ---- roofline of the dominant kernel: timed ALONE after the timed region, >= 500 ticks in one
-    # graph-captured local rollout (rewards kept: [ticks, n] rows), HIP events on its launch stream
-    cur = torch.cuda.current_stream(dev)
-    kt = max(args.kernel_ticks, 1)
-    mode_id = L.ACT_RANDOM if args.mode == "random" else L.ACT_BUFFER
-    simple = env.init_props.cluster_prop.house_prop.deadband == 0.0 and env._norm_temp == 1.0
-    kern = step_kernel_name(n_loc, args.mode, window, simple, args.thermal)
-    actor_ms = graph_ms = None
-    if dactor is None and g_act is None:
-        kbuf = torch.empty((kt, n_loc), dtype=torch.float64, device=dev)
-        kacts = None if acts is None else (torch.rand((kt, n_loc), device=dev) < 0.5).to(torch.uint8)
-        kticks = env.driver_window(kt)
-        ls = sh.launch_stream()
-        for rep in range(2):  # the whole graph (count, reduce and step kernels): capture, then a timed replay
-            if rep:
-                torch.cuda.synchronize()
-                ev0.record(ls)
-            sh.rollout(kticks, kacts, n_loc if kacts is not None else 0, mode_id, kbuf, n_loc, True)
-        ev1.record(ls)
-        torch.cuda.synchronize()
-        graph_ms = ev0.elapsed_time(ev1)
-        # the step kernel ALONE, in steady state: --kernel-warm-ticks untimed, then the same rollout
-        # issued directly with hipExtLaunchKernel start/stop events around every step-kernel launch
-        # (mdr_time_step_kernels), averaged over its launches
-        for _ in range(max(args.kernel_warm_ticks, 0) // kt):
-            sh.rollout(env.driver_window(kt), kacts, n_loc if kacts is not None else 0, mode_id, kbuf, n_loc, True)
-        step_ms, launches = 0.0, 0
-        for _ in range(max(args.kernel_reps, 1)):
-            ms_r, l_r = sh.time_step_kernels(env.driver_window(kt), kacts, n_loc if kacts is not None else 0,
-                                             mode_id, kbuf, n_loc)
-            step_ms += ms_r
-            launches += l_r
-        del kbuf
-        kern_ms = step_ms / launches
-        k_win = kt * max(args.kernel_reps, 1) // launches if window > 0 else 1
-        bytes_launch = window_bytes(n_loc, k_win, args.mode) if window > 0 else BYTES_PER_HOUSE_STEP * n_loc
-        steps_launch = k_win
-    elif g_act is not None:
-        K = min(20, rew.shape[0])
-        gt = env.driver_window(K)  # (the drivers first: the events bracket the device work)
-        torch.cuda.synchronize()
-        ev0.record(cur)
-        sh.greedy_rollout(gt, g_act, 0, rew[:K], n_loc)
-        ev1.record(cur)
-        torch.cuda.synchronize()
-        launches, kern_ms = K, ev0.elapsed_time(ev1) / K
-        bytes_launch = (BYTES_PER_HOUSE_STEP + GREEDY_EXTRA) * n_loc
-        steps_launch = 1
-        kern = ("greedy tick: histogram select (k_gq_binsc, k_gq_finish; codes, superbin and predicted-band "
-                "bin counts from the previous k_step_pipe's epilogue) + k_step_pipe")
-    else:
-        # the actor rollout graph interleaves k_actor and k_step: time the actor alone
-        K = 50
-        act_buf = torch.empty(n_loc, dtype=torch.uint8, device=dev)
-        prob_buf = torch.empty(n_loc, dtype=torch.float32, device=dev)
-        dactor.select_actions(action=act_buf, prob=prob_buf, count_next=False)
-        torch.cuda.synchronize()
-        ev0.record(cur)
-        for _ in range(K):
+    if args.full:
+        # ---- roofline of the dominant kernel: timed ALONE after the timed region, >= 500 ticks in one
+        # graph-captured local rollout (rewards kept: [ticks, n] rows), HIP events on its launch stream
+        cur = torch.cuda.current_stream(dev)
+        kt = max(args.kernel_ticks, 1)
+        mode_id = L.ACT_RANDOM if args.mode == "random" else L.ACT_BUFFER
+        simple = env.init_props.cluster_prop.house_prop.deadband == 0.0 and env._norm_temp == 1.0
+        kern = step_kernel_name(n_loc, args.mode, window, simple, args.thermal)
+        actor_ms = graph_ms = None
+        if dactor is None and g_act is None:
+            kbuf = torch.empty((kt, n_loc), dtype=torch.float64, device=dev)
+            kacts = None if acts is None else (torch.rand((kt, n_loc), device=dev) < 0.5).to(torch.uint8)
+            kticks = env.driver_window(kt)
+            ls = sh.launch_stream()
+            for rep in range(2):  # the whole graph (count, reduce and step kernels): capture, then a timed replay
+                if rep:
+                    torch.cuda.synchronize()
+                    ev0.record(ls)
+                sh.rollout(kticks, kacts, n_loc if kacts is not None else 0, mode_id, kbuf, n_loc, True)
+            ev1.record(ls)
+            torch.cuda.synchronize()
+            graph_ms = ev0.elapsed_time(ev1)
+            # the step kernel ALONE, in steady state: --kernel-warm-ticks untimed, then the same rollout
+            # issued directly with hipExtLaunchKernel start/stop events around every step-kernel launch
+            # (mdr_time_step_kernels), averaged over its launches
+            for _ in range(max(args.kernel_warm_ticks, 0) // kt):
+                sh.rollout(env.driver_window(kt), kacts, n_loc if kacts is not None else 0, mode_id, kbuf, n_loc, True)
+            step_ms, launches = 0.0, 0
+            for _ in range(max(args.kernel_reps, 1)):
+                ms_r, l_r = sh.time_step_kernels(env.driver_window(kt), kacts, n_loc if kacts is not None else 0,
+                                                 mode_id, kbuf, n_loc)
+                step_ms += ms_r
+                launches += l_r
+            del kbuf
+            kern_ms = step_ms / launches
+            k_win = kt * max(args.kernel_reps, 1) // launches if window > 0 else 1
+            bytes_launch = window_bytes(n_loc, k_win, args.mode) if window > 0 else BYTES_PER_HOUSE_STEP * n_loc
+            steps_launch = k_win
+        elif g_act is not None:
+            K = min(20, rew.shape[0])
+            gt = env.driver_window(K)  # (the drivers first: the events bracket the device work)
+            torch.cuda.synchronize()
+            ev0.record(cur)
+            sh.greedy_rollout(gt, g_act, 0, rew[:K], n_loc)
+            ev1.record(cur)
+            torch.cuda.synchronize()
+            launches, kern_ms = K, ev0.elapsed_time(ev1) / K
+            bytes_launch = (BYTES_PER_HOUSE_STEP + GREEDY_EXTRA) * n_loc
+            steps_launch = 1
+            kern = ("greedy tick: histogram select (k_gq_binsc, k_gq_finish; codes, superbin and predicted-band "
+                    "bin counts from the previous k_step_pipe's epilogue) + k_step_pipe")
+        else:
+            # the actor rollout graph interleaves k_actor and k_step: time the actor alone
+            K = 50
+            act_buf = torch.empty(n_loc, dtype=torch.uint8, device=dev)
+            prob_buf = torch.empty(n_loc, dtype=torch.float32, device=dev)
             dactor.select_actions(action=act_buf, prob=prob_buf, count_next=False)
-        ev1.record(cur)
-        torch.cuda.synchronize()
-        actor_ms = ev0.elapsed_time(ev1) / K
-        actor_status = dactor.status()  # (the headline launches: tiles left to the fp32 fallback, faults)
-        # the other precisions / forms, timed the same way beside the headline one
-        from mdr_amd.actor import DeviceActor
-
-        beside = {}
-        for name, kw in (("fp32_f16_split", {"precision": "fp32", "fp32_form": "f16_split"}),
-                         ("fp32_bf16_split3", {"precision": "fp32", "fp32_form": "bf16_split3"}),
-                         ("bf16x3", {"precision": "bf16x3"})):
-            if kw["precision"] == args.precision and kw.get("fp32_form", args.fp32_form) == args.fp32_form:
-                continue
-            dx = DeviceActor(env, dactor.actor, **kw)
-            dx.select_actions(action=act_buf, prob=prob_buf, count_next=False)
             torch.cuda.synchronize()
             ev0.record(cur)
             for _ in range(K):
-                dx.select_actions(action=act_buf, prob=prob_buf, count_next=False)
+                dactor.select_actions(action=act_buf, prob=prob_buf, count_next=False)
             ev1.record(cur)
             torch.cuda.synchronize()
-            beside[name] = ev0.elapsed_time(ev1) / K
-        # (each DeviceActor loaded its weights into the shard: the headline actor again)
-        env.shard.set_option("actor_fp32_form", L.FP32_F16_SPLIT if args.fp32_form == "f16_split" else L.FP32_BF16_SPLIT3)
-        dactor.load_weights()
-        launches = K
-        kern_ms = max(gpu_ms / args.steps - actor_ms, 1e-6)  # the step kernel's share of a tick
-        bytes_launch = BYTES_PER_HOUSE_STEP * n_loc
-        steps_launch = 1
-    achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
-    traffic = pmc_traffic(kern, n_loc)
+            actor_ms = ev0.elapsed_time(ev1) / K
+            actor_status = dactor.status()  # (the headline launches: tiles left to the fp32 fallback, faults)
+            # the other precisions / forms, timed the same way beside the headline one
+            from mdr_amd.actor import DeviceActor
+
+            beside = {}
+            for name, kw in (("fp32_f16_split", {"precision": "fp32", "fp32_form": "f16_split"}),
+                             ("fp32_bf16_split3", {"precision": "fp32", "fp32_form": "bf16_split3"}),
+                             ("bf16x3", {"precision": "bf16x3"})):
+                if kw["precision"] == args.precision and kw.get("fp32_form", args.fp32_form) == args.fp32_form:
+                    continue
+                dx = DeviceActor(env, dactor.actor, **kw)
+                dx.select_actions(action=act_buf, prob=prob_buf, count_next=False)
+                torch.cuda.synchronize()
+                ev0.record(cur)
+                for _ in range(K):
+                    dx.select_actions(action=act_buf, prob=prob_buf, count_next=False)
+                ev1.record(cur)
+                torch.cuda.synchronize()
+                beside[name] = ev0.elapsed_time(ev1) / K
+            # (each DeviceActor loaded its weights into the shard: the headline actor again)
+            env.shard.set_option("actor_fp32_form", L.FP32_F16_SPLIT if args.fp32_form == "f16_split" else L.FP32_BF16_SPLIT3)
+            dactor.load_weights()
+            launches = K
+            kern_ms = max(gpu_ms / args.steps - actor_ms, 1e-6)  # the step kernel's share of a tick
+            bytes_launch = BYTES_PER_HOUSE_STEP * n_loc
+            steps_launch = 1
+        achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
+        traffic = pmc_traffic(kern, n_loc)
     out = {
         "metric": METRIC,
         "value": value,
@@ -595,6 +651,8 @@ def main():
         "higher_is_better": True,
         "scaling": "strong" if world > 1 and args.scaling == "strong" else "weak",
         "vs_baseline": None,
+        "full": args.full,
+        "outputs": dumped,
         "dtype": "f64",
         "data": "synthetic (device Philox population, reference noise model; fused Philox random actions)",
         "config": {"workload": (f"C4: {n_total:,} houses sharded over {world} GPUs ({n_loc:,} per GPU), random "
@@ -620,25 +678,27 @@ def main():
                                    (f" and {args.clock_warmup:.2f} s of non-environment device work"
                                     if args.clock_warmup > 0 else "") +
                                    (f"; a {args.host_spin_ms:g} ms idle host busy-loop" if args.host_spin_ms > 0 else "")},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kern,
-                     "kernel_avg_us": kern_ms * 1e3, "launches_timed": launches,
-                     "graph_us_per_launch": None if graph_ms is None else graph_ms * 1e3 / launches,
-                     "house_steps_per_launch": steps_launch * n_loc,
-                     "algorithmic_bytes_per_launch": bytes_launch,
-                     "bytes_per_house_step": bytes_launch / (steps_launch * n_loc),
-                     "timing": f"hipExtLaunchKernel start/stop events around each step-kernel launch of {max(args.kernel_reps, 1)} "
-                               f"{kt}-tick rollouts after the timed region and {args.kernel_warm_ticks} untimed kernel-only "
-                               "ticks (steady-state clock)",
-                     "valu": valu_roofline(kern, n_loc, kern_ms)},
     }
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": kern,
+                           "kernel_avg_us": kern_ms * 1e3, "launches_timed": launches,
+                           "graph_us_per_launch": None if graph_ms is None else graph_ms * 1e3 / launches,
+                           "house_steps_per_launch": steps_launch * n_loc,
+                           "algorithmic_bytes_per_launch": bytes_launch,
+                           "bytes_per_house_step": bytes_launch / (steps_launch * n_loc),
+                           "timing": f"hipExtLaunchKernel start/stop events around each step-kernel launch of {max(args.kernel_reps, 1)} "
+                                     f"{kt}-tick rollouts after the timed region and {args.kernel_warm_ticks} untimed kernel-only "
+                                     "ticks (steady-state clock)",
+                           "valu": valu_roofline(kern, n_loc, kern_ms)}
     if g_act is not None:
         out["data"] = "synthetic (device Philox population, reference noise model)"
         out["config"]["workload"] = ("C3: 1M houses, device GreedyMyopic (sort by -(T - target), budget = "
                                      "signal) on the post-step state, then env.step, every tick")
         out["config"]["action_mode"] = "greedy_myopic"
-        out["roofline"]["timing"] = ("HIP events around one mdr_greedy_rollout call of 20 greedy+step ticks after "
-                                     "the timed region (drivers computed before the first event)")
+        if args.full:
+            out["roofline"]["timing"] = ("HIP events around one mdr_greedy_rollout call of 20 greedy+step ticks "
+                                         "after the timed region (drivers computed before the first event)")
         gd = sh.greedy_diag()  # (after every timed call: it synchronises)
         out["greedy_select"] = {"calls": gd["calls"], "fallbacks": gd["fallbacks"],
                                 "mean_window_houses": gd["window_sum"] / max(gd["calls"] - gd["fallbacks"], 1),
@@ -653,7 +713,6 @@ def main():
         a = dactor.actor
         flops_house = 2 * sum(l.in_features * l.out_features for l in a.fc)  # 30,400 at F = 50
         flops_launch = flops_house * n_loc
-        tfs = flops_launch / (actor_ms * 1e-3) / 1e12
         prec_name = ("fp32 (fp16 hi/lo split, 3 products on v_mfma_f32_16x16x32_f16)" if args.precision == "fp32"
                      and args.fp32_form == "f16_split" else "fp32 (three-way bf16 split, 6 products)"
                      if args.precision == "fp32" else args.precision)
@@ -666,21 +725,23 @@ def main():
         out["config"]["actor"] = {"layers": [a.fc[0].in_features, 100, 100, 2], "precision": args.precision,
                                   "fp32_form": args.fp32_form if args.precision == "fp32" else None,
                                   "status": actor_status}
-        out["roofline"] = {"bound": "mfma", "achieved": tfs, "peak": BF16_PEAK_TFS, "unit": "TFLOP/s",
-                           "frac": tfs / BF16_PEAK_TFS, "traffic": None, "kernel": "mdr::k_actor",
-                           "kernel_avg_us": actor_ms * 1e3, "launches_timed": launches,
-                           "algorithmic_flops_per_launch": flops_launch, "flops_per_house": flops_house,
-                           "mfma_products_per_mac": {"bf16": 1, "bf16x3": 3,
-                                                     "fp32": 3 if args.fp32_form == "f16_split" else 6}[args.precision],
-                           "step_share": {"what": "launch-stream time per tick minus k_actor's time: the step "
-                                                  "kernel's share of a tick (not a kernel duration)",
-                                          "us_per_tick": kern_ms * 1e3}}
-        out["roofline"]["beside"] = {
-            name: {"kernel_avg_us": ms * 1e3, "achieved_tflops": flops_launch / (ms * 1e-3) / 1e12}
-            for name, ms in beside.items()}
-        out["roofline"]["beside"]["what"] = ("the same k_actor launches in the other arithmetic forms, timed the "
-                                             "same way (fp32 = the reference Actor's precision)")
-    if (dactor is None and g_act is None and rank == 0 and window > 0 and args.above_mall_houses > 0
+        if args.full:
+            tfs = flops_launch / (actor_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "achieved": tfs, "peak": BF16_PEAK_TFS, "unit": "TFLOP/s",
+                               "frac": tfs / BF16_PEAK_TFS, "traffic": None, "kernel": "mdr::k_actor",
+                               "kernel_avg_us": actor_ms * 1e3, "launches_timed": launches,
+                               "algorithmic_flops_per_launch": flops_launch, "flops_per_house": flops_house,
+                               "mfma_products_per_mac": {"bf16": 1, "bf16x3": 3,
+                                                         "fp32": 3 if args.fp32_form == "f16_split" else 6}[args.precision],
+                               "step_share": {"what": "launch-stream time per tick minus k_actor's time: the step "
+                                                      "kernel's share of a tick (not a kernel duration)",
+                                              "us_per_tick": kern_ms * 1e3}}
+            out["roofline"]["beside"] = {
+                name: {"kernel_avg_us": ms * 1e3, "achieved_tflops": flops_launch / (ms * 1e-3) / 1e12}
+                for name, ms in beside.items()}
+            out["roofline"]["beside"]["what"] = ("the same k_actor launches in the other arithmetic forms, timed the "
+                                                 "same way (fp32 = the reference Actor's precision)")
+    if (args.full and dactor is None and g_act is None and rank == 0 and window > 0 and args.above_mall_houses > 0
             and args.mode == "random"):
         out["roofline"]["above_mall"] = above_mall(args.above_mall_houses, args, kern)
     out["build"] = {"lib": os.path.relpath(L.LIB_PATH, os.path.dirname(os.path.abspath(__file__))),
