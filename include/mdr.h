@@ -215,6 +215,14 @@ size_t mdr_window_onb_bytes(int64_t n_local, int waves);
  * window launch over n_local houses; MDR_EARG otherwise.  Every k_count_window / k_step_window
  * launch checks its context's buffers with it, so a new launch geometry cannot overrun them. */
 int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size_t wah_bytes);
+/* Bytes of the per-tick, per-wave penalty partial rows ([32][tiles_padded][2] doubles, tiles of 128
+ * houses rounded up to whole 4-wave blocks) that a common-penalty window launch over n_local houses
+ * writes: ceil(ceil(n_local / 128) / 4) * 4 * 32 * 2 * 8.  0 for n_local < 0. */
+size_t mdr_window_pen_bytes(int64_t n_local);
+/* MDR_OK when penalty partial rows of pen_bytes cover a common-penalty window launch over n_local
+ * houses; MDR_EARG otherwise ("penalty partial" in mdr_last_error), also for n_local < 1.  Every
+ * such launch checks its context's buffer with it first. */
+int mdr_window_pen_check(int64_t n_local, size_t pen_bytes);
 
 /* ---- population ------------------------------------------------------------------------ */
 /* Synthetic population drawn on device from Philox4x32-10(seed, global house id): the reference
@@ -258,7 +266,8 @@ int mdr_counts_buffer(mdr_ctx* ctx, int64_t** dev_ptr, int* len);
  *   ctrl_out    : if non-NULL, the bang-bang (ctrl = MDR_CTRL_*) decision on the new state
  *   p_out       : if non-NULL, device double receiving the tick's cluster power
  *   ctrl = MDR_CTRL_GREEDY_KEYS: the next mdr_ctrl_greedy's keys (see MDR_CTRL_*)
- * For common penalty modes reward holds the raw penalty until mdr_reward_finalize. */
+ * For common penalty modes reward holds the raw penalty until mdr_reward_finalize (mdr_rollout
+ * finalises its rewards itself). */
 int mdr_step(mdr_ctx* ctx, const uint8_t* action, int action_mode, const mdr_tick* tick,
              double* reward, int lookahead, int ctrl, uint8_t* ctrl_out, double* p_out,
              void* stream);
@@ -276,13 +285,20 @@ int mdr_reward_finalize(mdr_ctx* ctx, const mdr_tick* tick, double* reward, void
  * (MDR_ACT_RANDOM / _ALWAYS_ON / _BANGBANG / _DEADBAND_BANGBANG) every tick is ONE launch (the
  * counts of tick t+1 come from tick t's lookahead); with MDR_ACT_BUFFER two.  use_graph != 0
  * captures the sequence in a hipGraph (cached per shape) and replays it.  p_out (device scalar,
- * may be NULL) receives the cluster power of the LAST tick, as mdr_step's p_out. */
+ * may be NULL) receives the cluster power of the LAST tick, as mdr_step's p_out.
+ * Common penalty modes (common_L2 / common_max_error / mixture): the rewards come out finalised —
+ * on the temporally blocked path (below) each window's step kernel writes per-wave {sum pen/N,
+ * max pen} partials every tick and two finish kernels (k_win_pen_reduce, k_win_reward_common)
+ * follow it; on the one-tick path every step is followed by mdr_penalty_partials /
+ * mdr_reward_finalize's kernels.  With rew_stride == 0 only the last tick's rewards are finalised
+ * (the row every tick overwrites).  Fixed reduction order: bit-reproducible from run to run.  A
+ * context with a communicator (or world > 1) returns MDR_EARG for these modes: per-step API. */
 int mdr_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                 int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                 double* p_out, int use_graph, void* stream);
 
-/* Open-loop sources (MDR_ACT_RANDOM / _ALWAYS_ON / _BUFFER) with individual_L2 and <= 4 capacity
- * classes run TEMPORALLY BLOCKED: windows of up to `ticks` steps per launch (k_step_window), the
+/* Open-loop sources (MDR_ACT_RANDOM / _ALWAYS_ON / _BUFFER) with <= 4 capacity classes (every
+ * penalty mode on an unsharded context; individual_L2 on a sharded one) run TEMPORALLY BLOCKED: windows of up to `ticks` steps per launch (k_step_window), the
  * state and parameters read and written once per window, rewards written every tick, each tick's
  * cluster power from counts the previous launch ran ahead (the FSM of an open-loop source does
  * not depend on the thermal state).  Bit-identical to the one-tick path.  ticks in 1..32
@@ -383,7 +399,8 @@ int mdr_greedy_state(mdr_ctx* ctx, uint64_t* out);
 /* Config C3's loop: n ticks of {mdr_ctrl_greedy with budget ticks[t].s_prev (the
  * signal before the tick's step, the one the observation carries) into action + t * act_stride,
  * then mdr_step of those actions with MDR_CTRL_GREEDY_KEYS (reward + t * rew_stride; common
- * penalty modes: + mdr_penalty_partials / mdr_reward_finalize)}; strides 0 = every tick overwrites.
+ * penalty modes: + mdr_penalty_partials / mdr_reward_finalize — closed-loop, so never the windowed
+ * finish of mdr_rollout)}; strides 0 = every tick overwrites.
  * Replaces the per-tick Python loop GreedyMyopic.get_action -> Environment.step
  * (greedy_myopic_controller.py:67-104, environment.py:86-106).  Single GPU only: a sharded context
  * (world > 1) returns MDR_ESTATE (its decision needs the caller's collectives: mdr_gq_shard_*). */

@@ -81,6 +81,9 @@ struct mdr_ctx {
   bool counts_ready = false;             // current slab filled (phase 1 or previous lookahead)
   double* d_pen_partial = nullptr;       // 2 per block of k_step_t
   double* d_partial2 = nullptr;
+  double* d_wpen = nullptr;              // common-penalty windows: {sum pen/N, max pen} [kWindowMax][tiles_padded][2]
+  size_t wpen_bytes = 0;
+  double* d_wres = nullptr;              // their per-tick {sum, max} [kWindowMax][2], then signal terms [kWindowMax]
   int pen_blocks = 0;
   // ---- options (mdr_set_option; defaults are the measured-fastest exact configuration)
   int tpw = 0;                           // MDR_OPT_STEP_TPW: k_step_pipe tiles per wave (0: k_step_t)
@@ -589,6 +592,14 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
   if (hipMalloc(&c->d_pen_partial, 2 * sizeof(double) * c->pen_blocks) != hipSuccess ||
       hipMalloc(&c->d_partial2, 2 * sizeof(double)) != hipSuccess)
     return cleanup(fail(MDR_ENOMEM, "penalty partials"));
+  if (cfg->penalty_mode != MDR_PEN_INDIVIDUAL_L2 && c->d_wslab) {
+    // windowed rollouts under a common penalty: the per-tick, per-wave partials (every wave of the
+    // grid writes its rows each launch: never cleared) and the per-tick {sum, max} + signal term
+    c->wpen_bytes = mdr_window_pen_bytes(cfg->n_local);
+    if (hipMalloc(&c->d_wpen, c->wpen_bytes) != hipSuccess ||
+        hipMalloc(&c->d_wres, 3 * kWindowMax * sizeof(double)) != hipSuccess)
+      return cleanup(fail(MDR_ENOMEM, "window penalty partials"));
+  }
   for (auto& e : c->ev)
     if (hipEventCreate(&e) != hipSuccess) return cleanup(fail(MDR_EHIP, "event"));
   for (int i = 0; i < kSlabs; ++i)
@@ -634,6 +645,8 @@ int mdr_destroy(mdr_ctx* c) {
   hipFree(c->d_wah2);
   hipFree(c->d_pen_partial);
   hipFree(c->d_partial2);
+  hipFree(c->d_wpen);
+  hipFree(c->d_wres);
   hipFree(c->d_ticks);
   for (auto& e : c->ev)
     if (e) hipEventDestroy(e);
@@ -887,7 +900,8 @@ static int capture_graph(mdr_ctx* c, F&& launches, hipGraphExec_t* out) {
   return MDR_OK;
 }
 
-// ---- windowed rollout (k_step_window): open-loop action sources, individual_L2
+// ---- windowed rollout (k_step_window): open-loop action sources; the common penalty modes run
+// its COMMON variant and two finish kernels per window (win_pen_finish), unsharded contexts only
 // SIMPLE = deadband 0, norm_temp 1, and reward weights whose signal / temperature penalties are
 // >= +0 (k_step_window forms -(a + s) as (-a) + (-s), exact for such operands)
 static bool win_simple(const mdr_ctx* c) {
@@ -895,12 +909,14 @@ static bool win_simple(const mdr_ctx* c) {
          c->kp.alpha_sig >= 0.0 && !std::signbit(c->kp.alpha_sig) && c->kp.norm_sig > 0.0;
 }
 
+static bool win_common(const mdr_ctx* c) { return c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2; }
+
 // (the lookahead's FSM runs on unsaturated seconds-since-off in a signed offset form: L <= 2^30 - 1,
 // dt <= 2^25, so a saturated value plus 33 ticks of dt and L - 32 dt stay inside int32 —
 // mdr_kernels.hip win_run_t)
 static bool window_ok(const mdr_ctx* c, int mode) {
-  return c->win > 0 && c->d_wslab && c->kp.n_cap <= kWindowCap && c->kp.penalty_mode == MDR_PEN_INDIVIDUAL_L2 &&
-         c->kp.L < (1 << 30) && c->kp.dt >= 0 && c->kp.dt <= (1 << 25) &&
+  return c->win > 0 && c->d_wslab && c->kp.n_cap <= kWindowCap && c->kp.L < (1 << 30) && c->kp.dt >= 0 &&
+         c->kp.dt <= (1 << 25) && (win_common(c) ? c->d_wpen != nullptr : true) &&
          (mode == MDR_ACT_RANDOM || mode == MDR_ACT_ALWAYS_ON || mode == MDR_ACT_BUFFER);
 }
 
@@ -929,6 +945,37 @@ extern "C" int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size
                               std::to_string(need) + " B");
   if (wah_bytes < (size_t)n_local * sizeof(uint32_t))
     return fail(MDR_EARG, "window launch: end-word buffer shorter than the shard");
+  return MDR_OK;
+}
+
+extern "C" size_t mdr_window_pen_bytes(int64_t n_local) {
+  if (n_local < 0) return 0;
+  const size_t tiles = ((size_t)n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
+  return (tiles + 3) / 4 * 4 * kWindowMax * 2 * sizeof(double);  // (step-window blocks hold 4 waves)
+}
+
+extern "C" int mdr_window_pen_check(int64_t n_local, size_t pen_bytes) {
+  if (n_local < 1) return fail(MDR_EARG, "window launch: no houses for the penalty partial rows");
+  const size_t need = mdr_window_pen_bytes(n_local);
+  if (pen_bytes < need)
+    return fail(MDR_EARG, "window launch: penalty partial rows of " + std::to_string(pen_bytes) +
+                              " B, the launch geometry writes " + std::to_string(need) + " B");
+  return MDR_OK;
+}
+
+// the finish of a common-penalty window of K ticks behind its k_step_window (stream order: the
+// kernel boundary publishes the step kernel's partials): per-tick {sum, max}, then the reward rows.
+// One shared row (rew_stride == 0): only the window's last tick is finalised.
+static int win_pen_finish(mdr_ctx* c, int K, double* reward, int64_t rew_stride, hipStream_t st) {
+  const int ntile = (int)win_grid(c) * 4;
+  double *res = c->d_wres, *sig = c->d_wres + 2 * kWindowMax;
+  const int j0 = rew_stride ? 0 : K - 1;
+  hipLaunchKernelGGL(k_win_pen_reduce, dim3(K - j0), dim3(256), 0, st,
+                     (const double*)c->d_wpen + (size_t)j0 * ntile * 2, ntile, res + 2 * j0);
+  LAUNCH_CHECK("k_win_pen_reduce");
+  hipLaunchKernelGGL(k_win_reward_common, dim3(blocks(c->kp.n, 256), K - j0), dim3(256), 0, st, c->kp,
+                     (const double*)res, (const double*)sig, j0, reward, rew_stride);
+  LAUNCH_CHECK("k_win_reward_common");
   return MDR_OK;
 }
 
@@ -974,29 +1021,38 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
     c->step_events->push_back(t1);
   }
   const KParams kp = c->kp;
-#define MDR_SW_L(A, SI, KA_, FO)                                                                          \
+  // the common penalty modes: the COMMON variant (SIMPLE = false), its partial rows checked first
+  const bool common = win_common(c);
+  WinPen wp{};
+  if (common) {
+    if (!c->d_wpen || !c->d_wres) return fail(MDR_ESTATE, "window launch: no penalty partial rows");
+    if (int rc = mdr_window_pen_check(c->kp.n, c->wpen_bytes)) return rc;
+    wp = WinPen{c->d_wpen, c->d_wres + 2 * kWindowMax};
+  }
+#define MDR_SW_L(A, SI, KA_, FO, CO)                                                                      \
   do {                                                                                                    \
     if (t0)                                                                                               \
-      hipExtLaunchKernelGGL((k_step_window<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, t0, t1, 0, kp, \
-                            action, act_stride, tk, K, la_K, rec, reward, rew_stride, onb, wah, next_slot, dv); \
+      hipExtLaunchKernelGGL((k_step_window<A, kWinHpt, SI, KA_, FO, CO>), dim3(grid), dim3(256), 0, st, t0, t1, 0, kp, \
+                            action, act_stride, tk, K, la_K, rec, reward, rew_stride, onb, wah, next_slot, dv, wp); \
     else                                                                                                  \
-      hipLaunchKernelGGL((k_step_window<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action,  \
-                         act_stride, tk, K, la_K, rec, reward, rew_stride, onb, wah, next_slot, dv);       \
+      hipLaunchKernelGGL((k_step_window<A, kWinHpt, SI, KA_, FO, CO>), dim3(grid), dim3(256), 0, st, kp, action, \
+                         act_stride, tk, K, la_K, rec, reward, rew_stride, onb, wah, next_slot, dv, wp);   \
   } while (0)
-#define MDR_SW_F(A, SI, KA_)                                                            \
-  do {                                                                                  \
-    if (c->thermal == MDR_THERMAL_AFFINE) MDR_SW_L(A, SI, KA_, MDR_THERMAL_AFFINE);     \
-    else MDR_SW_L(A, SI, KA_, MDR_THERMAL_EXACT);                                       \
+#define MDR_SW_F(A, SI, KA_, CO)                                                            \
+  do {                                                                                      \
+    if (c->thermal == MDR_THERMAL_AFFINE) MDR_SW_L(A, SI, KA_, MDR_THERMAL_AFFINE, CO);     \
+    else MDR_SW_L(A, SI, KA_, MDR_THERMAL_EXACT, CO);                                       \
   } while (0)
-#define MDR_SW_K(A, SI)                         \
+#define MDR_SW_K(A, SI, CO)                     \
   do {                                          \
-    if (ka) MDR_SW_F(A, SI, true);              \
-    else MDR_SW_F(A, SI, false);                \
+    if (ka) MDR_SW_F(A, SI, true, CO);          \
+    else MDR_SW_F(A, SI, false, CO);            \
   } while (0)
-#define MDR_SW_S(A)                             \
-  do {                                          \
-    if (win_simple(c)) MDR_SW_K(A, true);       \
-    else MDR_SW_K(A, false);                    \
+#define MDR_SW_S(A)                                  \
+  do {                                               \
+    if (common) MDR_SW_K(A, false, true);            \
+    else if (win_simple(c)) MDR_SW_K(A, true, false); \
+    else MDR_SW_K(A, false, false);                  \
   } while (0)
   if (mode == MDR_ACT_RANDOM) MDR_SW_S(MDR_ACT_RANDOM);
   else if (mode == MDR_ACT_ALWAYS_ON) MDR_SW_S(MDR_ACT_ALWAYS_ON);
@@ -1037,6 +1093,16 @@ static int window_launches(mdr_ctx* c, int n, const TickArgs* tk, const uint8_t*
   const int ncap = kp.n_cap;
   auto rec = [&](int w) {  // the slot's tick records, after its shards and reduced counts
     return reinterpret_cast<const double*>(slot(w) + (size_t)kWindowMax * kCountShards * ncap + (size_t)kWindowMax * ncap);
+  };
+  // the common penalty modes: the cluster's per-tick mean / max penalty would need an allreduce
+  // inside the sequence (sharded contexts keep the per-step API)
+  const bool common = win_common(c);
+  if (common && (shd || pipe || ka_red))
+    return fail(MDR_EARG, "window launches: common penalty modes on a sharded context need the per-step API");
+  // the rows a later window overwrites are not finalised (one shared row: the last window's only)
+  auto finish = [&](int w, int K, int t0) {
+    if (!common || (!rew_stride && w + 1 < nw)) return (int)MDR_OK;
+    return win_pen_finish(c, K, reward + (int64_t)t0 * rew_stride, rew_stride, st);
   };
   c->wslab_dirty = true;  // until the sequence is fully issued
   if (pipe) {
@@ -1108,6 +1174,7 @@ static int window_launches(mdr_ctx* c, int n, const TickArgs* tk, const uint8_t*
       if (int rc = launch_step_window(c, mode, true, a, act_stride, tk, K, la, rec(0), reward, rew_stride, c->d_onb,
                                       c->d_wah, slot(1), dv, st))
         return rc;
+      if (int rc = finish(0, K, 0)) return rc;
       if (n > K)
         if (int rc = stage_recs(host_ticks + K, n - K, const_cast<TickArgs*>(tk) + K, st)) return rc;
       t0 += K;
@@ -1124,6 +1191,7 @@ static int window_launches(mdr_ctx* c, int n, const TickArgs* tk, const uint8_t*
                                     reward + (int64_t)t0 * rew_stride, rew_stride, c->d_onb, c->d_wah, slot(w + 1),
                                     WinDrv{}, st))
       return rc;
+    if (int rc = finish(w, K, t0)) return rc;
     t0 += K;
   }
   c->wslab_dirty = false;
@@ -1172,6 +1240,14 @@ static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t ac
     int rc = launch_step(c, a, mode, TickArgs{}, c->d_ticks + t, r, la ? mode : 0, MDR_CTRL_NONE,
                          nullptr, t == n - 1 ? p_out : nullptr, st);
     if (rc) return rc;
+    if (win_common(c)) {  // step_tensor's common-penalty tail, the tick's drivers read from d_ticks
+      hipLaunchKernelGGL(k_pen_reduce, dim3(1), dim3(256), 0, st, c->d_pen_partial, c->pen_blocks, c->d_partial2);
+      LAUNCH_CHECK("k_pen_reduce");
+      hipLaunchKernelGGL(k_reward_finalize_dev, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp,
+                         (const TickArgs*)(c->d_ticks + t), (const unsigned long long*)slab_at(c, c->ring - 1),
+                         (const double*)c->d_partial2, r);
+      LAUNCH_CHECK("k_reward_finalize");
+    }
     if (c->step_events) {
       HIP_TRY(hipEventCreate(&e1));
       c->step_events->push_back(e1);
@@ -1194,8 +1270,8 @@ int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
   c->fz_ready = false;
   if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout: context not bound");
   if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, "mdr_rollout: bad action source");
-  if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, "mdr_rollout: common penalty modes need the per-step API");
+  if (win_common(c) && (has_comm(c) || c->world > 1))  // (their mean / max penalty would be shard-local)
+    return fail(MDR_EARG, "mdr_rollout: common penalty modes on a sharded context need the per-step API");
   hipStream_t st = S(stream);
   const bool win = window_ok(c, mode);
   const bool consec = consecutive(ticks, n);
@@ -1270,6 +1346,7 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
   // the matching mdr_rollout_sharded launches just the KA step kernel
   const bool sharded = has_comm(c);
   if (sharded && n > c->win) return MDR_OK;
+  if (win_common(c) && (sharded || c->world > 1)) return MDR_OK;  // (mdr_rollout / _sharded refuse these)
   hipStream_t st = S(stream);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = wslab_clean(c, st);

@@ -163,10 +163,26 @@ struct WinDrv {
 // SIMPLE: deadband 0 and norm_temp 1 (reward without branches / division); FORM: the per-tick
 // thermal update, MDR_THERMAL_EXACT (the reference's expression) or MDR_THERMAL_AFFINE (its
 // per-window transition coefficients, mdr_kernels.hip K1W)
-template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+// COMMON (common_L2 / common_max_error / mixture, SIMPLE = false only): every tick each wave also
+// writes {sum pen_i / N, max pen_i} over its tile to pen.part[tick][tile] (tiles padded to whole
+// blocks: gridDim.x * 4 per tick) and block 0 the tick's signal term to pen.sig[tick]; the reward
+// rows get the raw pen_i (mixture) or nothing, and k_win_pen_reduce + k_win_reward_common finish
+struct WinPen {
+  double* part;  // [kWindowMax][tiles_padded][2]
+  double* sig;   // [kWindowMax]
+};
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool COMMON = false>
 __global__ void k_step_window(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, int K,
                               int la_K, const double* rec, double* reward, int64_t rew_stride, uint64_t* onb,
-                              uint32_t* wah, unsigned long long* next_slot, WinDrv dv);
+                              uint32_t* wah, unsigned long long* next_slot, WinDrv dv, WinPen pen);
+// one block per tick j: res[j] = {sum, max} of part[j][0..ntile) in index order
+__global__ void k_win_pen_reduce(const double* part, int ntile, double* res);
+// reward rows j0 + blockIdx.y of a common-penalty window from res / sig (k_reward_finalize's expression)
+__global__ void k_win_reward_common(KParams p, const double* res, const double* sig, int j0, double* reward,
+                                    int64_t rew_stride);
+// k_reward_finalize with the tick's drivers in device memory (rollouts with staged drivers)
+__global__ void k_reward_finalize_dev(KParams p, const TickArgs* tkp, const unsigned long long* counts,
+                                      const double* partial2, double* reward);
 __global__ void k_win_reduce(KParams p, unsigned long long* slot, int nt, const TickArgs* tkp, double* p_out);
 __global__ void k_win_records(KParams p, unsigned long long* slot, int nt, const TickArgs* tkp, double* p_out);
 template <int ACT, int HPT>

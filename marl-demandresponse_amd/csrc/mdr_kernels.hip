@@ -1418,13 +1418,22 @@ __device__ __forceinline__ AffWin aff_window(double ua, double ca, double cm, do
 // FORM: MDR_THERMAL_EXACT runs the reference's expression per tick (rc_apply_win: bit-identical to
 // the one-tick kernels); MDR_THERMAL_AFFINE the per-window transition above (Kelvin state kept in
 // registers for the window).
-template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+// COMMON (the common penalty modes, rewards_calculator.py:46-181): the cluster's mean and max of the
+// per-house temperature penalty couple the houses once per tick.  Each tick the wave reduces its
+// tile's {sum pen_i / N, max pen_i} with a fixed xor butterfly (no atomics, no block barrier: the
+// order never depends on scheduling) and lane 0 stores the pair to pen.part[tick][tile]; every wave
+// of the grid stores all K pairs (an empty tile: zeros), so the buffer is never cleared.  Block 0
+// publishes the tick's signal term to pen.sig.  The reward row gets the raw pen_i (mixture) or
+// nothing; k_win_pen_reduce and k_win_reward_common, launched behind this kernel, finish it.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool COMMON>
 __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* __restrict__ action,
                                                      int64_t act_stride, const TickArgs* __restrict__ tkp, int K,
                                                      int la_K, const double* __restrict__ rec,
                                                      double* __restrict__ reward, int64_t rew_stride,
                                                      uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
-                                                     unsigned long long* __restrict__ next_slot, WinDrv dv) {
+                                                     unsigned long long* __restrict__ next_slot, WinDrv dv,
+                                                     WinPen wp) {
+  static_assert(!(COMMON && SIMPLE), "the common penalty modes use the general dead-band penalty");
   constexpr bool AFF = FORM == MDR_THERMAL_AFFINE;
   __shared__ unsigned s_cnt[4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6;
@@ -1432,6 +1441,9 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
   uint64_t* onb_w = onb + (size_t)t.tile * HPT * kWinMax;  // this wave's rows [kWinMax][HPT]
   // KA: lane j = tick j's negated signal penalty (its two loads go out first, beside the state's)
   uint32_t ns_lo = 0, ns_hi = 0;
+  if constexpr (COMMON && !KA) {  // thread j of block 0: tick j's signal term (rec[2] is its exact negation)
+    if (blockIdx.x == 0 && (int)threadIdx.x < K) wp.sig[threadIdx.x] = -rec[threadIdx.x * kWinRec + 2];
+  }
   if (KA) {
     const int l = (int)(threadIdx.x & 63) < K ? (int)(threadIdx.x & 63) : 0;
     double P;
@@ -1446,6 +1458,9 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
       if (dv.p_out && blockIdx.x == 0 && threadIdx.x == 0) *dv.p_out = rec[(K - 1) * kWinRec];  // (last window)
     }
     const double ns = win_nsig(p, P, dv.s_prev[l]);
+    if constexpr (COMMON) {  // (thread j of block 0 is lane j of its first wave: l = j)
+      if (blockIdx.x == 0 && (int)threadIdx.x < K) wp.sig[threadIdx.x] = -ns;
+    }
     ns_lo = (uint32_t)__double_as_longlong(ns);
     ns_hi = (uint32_t)((uint64_t)__double_as_longlong(ns) >> 32);
   }
@@ -1512,7 +1527,9 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
   for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[h];
   const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
   const double nalpha = -p.alpha_temp;
+  const bool mix = COMMON && p.penalty_mode == MDR_PEN_MIXTURE;  // COMMON: the raw pen_i goes to the reward row
   for (int j = 0; j < K; ++j) {
+    [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
     const double od_k = r_od, solar = r_sol, nsig = r_sig;
     const bool tick_ok = r_ok != 0;
     uint64_t on_m[HPT];
@@ -1552,6 +1569,7 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
       double pen = 0.0;
       if (hi_tg[h] < Tn) { const double x = Tn - hi_tg[h]; pen = x * x; }
       else if (lo_tg[h] > Tn) { const double x = lo_tg[h] - Tn; pen = x * x; }
+      if constexpr (COMMON) return pen;  // (deadband_l2's bits; finalised by k_win_reward_common)
       const double tpen = p.alpha_temp * pen;
       return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + -nsig);
     };
@@ -1569,7 +1587,8 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
           tk[h] = tkn;
           tmk[h] = tmkn;
           const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
-          if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          if constexpr (COMMON) pen_t[h] = r;
+          if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
         }
       };
       if (win_finite && tick_ok) houses(std::true_type());
@@ -1592,11 +1611,29 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
           T[h] = Tn;
           Tm[h] = Tmn;
           const double r = reward_of(h, Tn, 0.0, fast_c);
-          if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          if constexpr (COMMON) pen_t[h] = r;
+          if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
         }
       };
       if (fast) houses(std::true_type());
       else houses(std::false_type());
+    }
+    if constexpr (COMMON) {
+      // the tile's {sum pen_i / N, max pen_i} (the terms of k_step_t: divided one by one), reduced
+      // over the wave in a fixed butterfly; row j of the partials is [gridDim.x * 4 tiles][2]
+      double sacc = 0.0, macc = 0.0;
+#pragma unroll
+      for (int h = 0; h < HPT; ++h)
+        if (t.v[h]) { sacc += pen_t[h] / (double)p.n_global; macc = fmax(macc, pen_t[h]); }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        sacc += __shfl_xor(sacc, off);
+        macc = fmax(macc, __shfl_xor(macc, off));
+      }
+      if ((threadIdx.x & 63) == 0) {
+        const size_t ntile = (size_t)gridDim.x * (blockDim.x >> 6);
+        *reinterpret_cast<double2*>(wp.part + ((size_t)j * ntile + t.tile) * 2) = make_double2(sacc, macc);
+      }
     }
   }
   if constexpr (AFF) {
@@ -1631,11 +1668,16 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
 }
 
 
-#define MDR_INST_WIN_F(A, SI, KA_, FO)                                                                         \
-  template __global__ void k_step_window<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
-                                                                  int, int, const double*, double*, int64_t,   \
-                                                                  uint64_t*, uint32_t*, unsigned long long*, WinDrv);
+#define MDR_INST_WIN_C(A, SI, KA_, FO, CO)                                                                     \
+  template __global__ void k_step_window<A, kWinHpt, SI, KA_, FO, CO>(KParams, const uint8_t*, int64_t,        \
+                                                                      const TickArgs*, int, int, const double*, \
+                                                                      double*, int64_t, uint64_t*, uint32_t*,  \
+                                                                      unsigned long long*, WinDrv, WinPen);
+#define MDR_INST_WIN_F(A, SI, KA_, FO) MDR_INST_WIN_C(A, SI, KA_, FO, false)
+// (the common penalty modes: SIMPLE = false only)
 #define MDR_INST_WIN(A)                                                                                         \
+  MDR_INST_WIN_C(A, false, false, MDR_THERMAL_EXACT, true) MDR_INST_WIN_C(A, false, true, MDR_THERMAL_EXACT, true)   \
+  MDR_INST_WIN_C(A, false, false, MDR_THERMAL_AFFINE, true) MDR_INST_WIN_C(A, false, true, MDR_THERMAL_AFFINE, true) \
   MDR_INST_WIN_F(A, true, false, MDR_THERMAL_EXACT) MDR_INST_WIN_F(A, false, false, MDR_THERMAL_EXACT)          \
   MDR_INST_WIN_F(A, true, true, MDR_THERMAL_EXACT) MDR_INST_WIN_F(A, false, true, MDR_THERMAL_EXACT)            \
   MDR_INST_WIN_F(A, true, false, MDR_THERMAL_AFFINE) MDR_INST_WIN_F(A, false, false, MDR_THERMAL_AFFINE)        \
@@ -1742,24 +1784,90 @@ __global__ void __launch_bounds__(256) k_pen_reduce(const double* __restrict__ p
   if (threadIdx.x == 0) { partial2[0] = ss[0]; partial2[1] = sm[0]; }
 }
 
-// rewards for common_L2 / common_max_error / mixture (rewards_calculator.py:46-181)
-__global__ void __launch_bounds__(256) k_reward_finalize(KParams p, TickArgs tk,
-                                                         const unsigned long long* __restrict__ counts,
-                                                         const double* __restrict__ partial2,
-                                                         double* __restrict__ reward) {
-  const double P = wave_power(counts, p.p_on, p.n_cap);
-  const double x = (P - tk.s_prev) / (double)p.n_global;
-  const double sig_term = p.alpha_sig * (x * x) / p.norm_sig;
-  const double common_l2 = partial2[0], common_max = partial2[1];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  const double pen = reward[i];
+// the reward of a house under common_L2 / common_max_error / mixture from its own penalty, the
+// cluster's {mean, max} penalty and the tick's signal term (rewards_calculator.py:46-181)
+__device__ __forceinline__ double common_reward(const KParams& p, double pen, double common_l2, double common_max,
+                                                double sig_term) {
   double tp;
   if (p.penalty_mode == MDR_PEN_COMMON_L2) tp = common_l2;
   else if (p.penalty_mode == MDR_PEN_COMMON_MAX) tp = common_max;
   else tp = (p.alpha_ind_l2 * pen + p.alpha_common_l2 * common_l2 + p.alpha_common_max * common_max) /
             (p.alpha_ind_l2 + p.alpha_common_l2 + p.alpha_common_max);
-  reward[i] = -(p.alpha_temp * tp / p.norm_temp + sig_term);
+  return -(p.alpha_temp * tp / p.norm_temp + sig_term);
+}
+
+__device__ __forceinline__ void reward_finalize_body(const KParams& p, double s_prev,
+                                                     const unsigned long long* __restrict__ counts,
+                                                     const double* __restrict__ partial2,
+                                                     double* __restrict__ reward) {
+  const double P = wave_power(counts, p.p_on, p.n_cap);
+  const double x = (P - s_prev) / (double)p.n_global;
+  const double sig_term = p.alpha_sig * (x * x) / p.norm_sig;
+  const double common_l2 = partial2[0], common_max = partial2[1];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  reward[i] = common_reward(p, reward[i], common_l2, common_max, sig_term);
+}
+
+// rewards for common_L2 / common_max_error / mixture (rewards_calculator.py:46-181)
+__global__ void __launch_bounds__(256) k_reward_finalize(KParams p, TickArgs tk,
+                                                         const unsigned long long* __restrict__ counts,
+                                                         const double* __restrict__ partial2,
+                                                         double* __restrict__ reward) {
+  reward_finalize_body(p, tk.s_prev, counts, partial2, reward);
+}
+
+// the same with the tick's drivers in device memory (a rollout's staged ticks)
+__global__ void __launch_bounds__(256) k_reward_finalize_dev(KParams p, const TickArgs* __restrict__ tkp,
+                                                             const unsigned long long* __restrict__ counts,
+                                                             const double* __restrict__ partial2,
+                                                             double* __restrict__ reward) {
+  reward_finalize_body(p, tkp->s_prev, counts, partial2, reward);
+}
+
+// ---- finish of a common-penalty window (behind k_step_window<..., COMMON>: the kernel boundary
+// makes its plain-store partials visible)
+// One block per tick j: res[j] = {sum, max} of the tick's per-wave partials part[j][0 .. ntile),
+// thread t taking tiles t, t + 256, ... in index order, then k_pen_reduce's LDS tree (stride-1
+// rows of doubles: lanes of a wave read consecutive 8-B words, no bank conflict).  A fixed order:
+// the result is the same bits every run.
+__global__ void __launch_bounds__(256) k_win_pen_reduce(const double* __restrict__ part, int ntile,
+                                                        double* __restrict__ res) {
+  __shared__ double ss[256], sm[256];
+  const double2* row = reinterpret_cast<const double2*>(part) + (size_t)blockIdx.x * ntile;
+  double s = 0.0, m = 0.0;
+  for (int b = threadIdx.x; b < ntile; b += blockDim.x) {
+    const double2 v = row[b];
+    s += v.x;
+    m = fmax(m, v.y);
+  }
+  ss[threadIdx.x] = s;
+  sm[threadIdx.x] = m;
+  __syncthreads();
+  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      ss[threadIdx.x] += ss[threadIdx.x + w];
+      sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + w]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { res[2 * blockIdx.x] = ss[0]; res[2 * blockIdx.x + 1] = sm[0]; }
+}
+
+// Reward row of tick j = j0 + blockIdx.y of the window (blockIdx.x: 256 houses): k_reward_finalize's
+// expression from res[j] and sig[j].  mixture reads the row's raw pen_i and rewrites it in place;
+// the other two modes write a uniform row.  rew_stride == 0: every tick shares one row, which holds
+// the window's last tick's pen_i, so the caller launches that tick alone (j0 = K - 1, gridDim.y = 1).
+__global__ void __launch_bounds__(256) k_win_reward_common(KParams p, const double* __restrict__ res,
+                                                           const double* __restrict__ sig, int j0,
+                                                           double* __restrict__ reward, int64_t rew_stride) {
+  const int j = j0 + (int)blockIdx.y;
+  const double common_l2 = res[2 * j], common_max = res[2 * j + 1], sig_term = sig[j];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  double* r = reward + (int64_t)j * rew_stride + i;
+  const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
+  __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
 }
 
 // Reward of the last tick of an overlapped multi-GPU rollout (the k_step launches there write

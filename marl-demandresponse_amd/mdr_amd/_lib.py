@@ -135,6 +135,8 @@ SIGNATURES = {
     "mdr_set_option": (I, [VP, I, I64]),
     "mdr_window_onb_bytes": (C.c_size_t, [I64, I]),
     "mdr_window_geometry_check": (I, [I64, C.c_size_t, C.c_size_t]),
+    "mdr_window_pen_bytes": (C.c_size_t, [I64]),
+    "mdr_window_pen_check": (I, [I64, C.c_size_t]),
     "mdr_time_step_kernels": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, P(C.c_float), P(I)]),
     "mdr_rollout_begin": (I, [VP, I, U64, VP, I64, I, VP]),
     "mdr_populate": (I, [VP, P(mdr_pop_spec), VP]),

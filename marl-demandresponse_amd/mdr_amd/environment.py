@@ -591,12 +591,16 @@ class Environment:
         kernel arguments of the first step kernel (k_step_window<..., KA>); the later windows'
         drivers are staged behind it.  ``use_graph=True``: the drivers are staged first and the
         launch sequence is replayed as a cached hipGraph (measured slower for both short and long
-        calls, profiles/r02h_ab.log)."""
+        calls, profiles/r02h_ab.log).  The common penalty modes (common_L2, common_max_error,
+        mixture) take the same path on an unsharded environment: each window's step kernel writes
+        per-wave penalty partials every tick and two finish kernels form the rewards (a 1-D
+        ``rewards`` holds the last tick's); sharded environments keep ``step_tensor`` for them."""
         import torch
 
         sh = self._shard
-        if sh.penalty_mode != 0:
-            raise NotImplementedError("rollout supports individual_L2; use step_tensor for common penalties")
+        if sh.penalty_mode != 0 and self._comm is not None:
+            # (the cluster's per-tick mean / max penalty would need an allreduce inside the window sequence)
+            raise NotImplementedError("sharded rollout supports individual_L2; use step_tensor for common penalties")
         mode = ACTION_MODES[action_mode]
         if mode in (L.ACT_BANGBANG, L.ACT_DEADBAND_BANGBANG):
             raise NotImplementedError("bang-bang rollouts: use step_tensor(action_mode=..., lookahead=...)")
