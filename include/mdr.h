@@ -187,6 +187,11 @@ int mdr_params_changed(mdr_ctx* ctx);
  *                           three-launch form (a band miss costs more); 0 = the band form on every tick
  *   MDR_OPT_ACTOR_GENERIC   1 = k_actor runs its generic form for the reference's default obs layout too
  *                           (0, default: that layout runs the form specialised for it, mdr_actor.hip DEF)
+ *   MDR_OPT_ACTOR_GRID      v >= 1 = k_actor's grid is capped at min(v, CUs) blocks, so every wave walks more
+ *                           tiles (the same outputs bit for bit: the tests' way to many tiles per wave on
+ *                           a small cluster); 0 (default) = min(blocks with a tile per wave, CUs).  Every
+ *                           fused-actor launch (act, the rollout graph, the sharded interior / edge
+ *                           launches); the layer chain ignores it; a negative value is MDR_EARG
  *   MDR_OPT_ACTOR_FP32_FORM the fused actor's MDR_PREC_FP32 arithmetic: MDR_FP32_F16_SPLIT (default) =
  *                           fp16 hi/lo operands on the fp16 MFMA, 3 products per term, power-of-two
  *                           per-layer weight scales (activations must stay inside fp16's range:
@@ -200,7 +205,8 @@ int mdr_params_changed(mdr_ctx* ctx);
 enum { MDR_OPT_STEP_TPW = 1, MDR_OPT_FASTDIV = 2, MDR_OPT_WINDOW_PIPELINE = 3, MDR_OPT_SHARDED_OVERLAP = 4,
        MDR_OPT_GREEDY_SORT = 5, MDR_OPT_FORCE_HALO = 6, MDR_OPT_WINDOW_THERMAL = 7,
        MDR_OPT_HALO_OVERLAP = 9, MDR_OPT_ACTOR_GENERIC = 10, MDR_OPT_HALO_IN_COUNTS = 12,
-       MDR_OPT_GQ_BAND = 13, MDR_OPT_ACTOR_FP32_FORM = 14, MDR_OPT_GQ_FUSED = 15, MDR_OPT_GQ_ADAPTIVE = 16 };
+       MDR_OPT_GQ_BAND = 13, MDR_OPT_ACTOR_FP32_FORM = 14, MDR_OPT_GQ_FUSED = 15, MDR_OPT_GQ_ADAPTIVE = 16,
+       MDR_OPT_ACTOR_GRID = 17 };
 enum { MDR_FP32_F16_SPLIT = 0, MDR_FP32_BF16_SPLIT3 = 1 };
 /* (8 was MDR_OPT_ACTOR_PINGPONG, a k_actor schedule measured slower and retired in r04: rejected) */
 enum { MDR_THERMAL_EXACT = 0, MDR_THERMAL_AFFINE = 1 };
@@ -491,11 +497,12 @@ typedef struct mdr_actor_net {
 int mdr_actor_load_net(mdr_ctx* ctx, const mdr_actor_net* net, const float* const* w, const float* const* b,
                        void* stream);
 /* Synchronises; counts since the last call (zeroed by it).  out[0] = 32-house tiles of the fused
- * fp16-split form (MDR_PREC_FP32, MDR_FP32_F16_SPLIT) that met a non-finite logit, out[1] = the fused
- * kernel's arithmetic (1 bf16, 3 bf16x3, 4 the fp16 split, 6 the three-way bf16 split; 0 without an
- * actor), out[2] = tiles of the fp16 split whose values left fp16's range (a hidden activation >= 2^15
- * x the layer's weight scale, or an sso ratio >= 2^15 in the tile's rows) and whose logits were
- * computed in scalar fp32 instead. */
+ * fp16-split form (MDR_PREC_FP32, MDR_FP32_F16_SPLIT) that wrote a non-finite logit (nothing else is
+ * counted there), out[1] = the fused kernel's arithmetic (1 bf16, 3 bf16x3, 4 the fp16 split, 6 the
+ * three-way bf16 split; 0 without an actor), out[2] = every tile of the fp16 split whose values left
+ * the range that form carries (a hidden activation >= 2^15 x the layer's weight scale, or a
+ * seconds-since-off ratio >= 64 in the tile's rows or messages) and whose logits were computed in
+ * scalar fp32 instead, wherever the tile sits in its wave's loop. */
 int mdr_actor_status(mdr_ctx* ctx, int64_t* out, int n, void* stream);  /* out[3] */
 /* 1 when the loaded actor runs the fused kernel for this obs layout, 0 when it runs the chain. */
 int mdr_actor_fused(mdr_ctx* ctx, const mdr_obs_spec* obs);

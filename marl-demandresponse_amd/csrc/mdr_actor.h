@@ -20,6 +20,14 @@ constexpr int actor_max_waves(int prec, bool def) { return !def || prec == 6 ? 8
 constexpr int kActorF16Exp = 0;
 // ... and max |b1| s1 below 2^kActorF16Bias (layer 2's fp16 operand relu(layer 1) s1 stays in range)
 constexpr int kActorF16Bias = 13;
+// ... and the largest seconds-since-off ratio int(sso / L) a tile may hold, in its own rows or its
+// messages, and stay on the fp16 path.  The per-layer scale leaves a weight an absolute error of up to
+// 2^-25 (fp16's subnormal spacing is 2^-24, and a column of small weights — the ratio's, in a policy
+// whose first layer normalises it — has its lo parts there or below), which an input x multiplies:
+// measured on an actor whose first-layer columns are divided by the features' maxima, against the
+// float64 forward, 1.1e-7 at a ratio of 63, 3.7e-7 at 127, 2.9e-6 at 1,023, 7e-5 at 32,767 (torch fp32:
+// 7.5e-8; the fp32 forms' bound is twice torch's + 2e-7).  Tiles beyond it take the fp32 fallback.
+constexpr unsigned kActorF16Sso = 64;
 // the packed tail: b1 [kActorRows] | b2 [kActorRows] | W3^T [kActorRows][kActorNA] | b3 [kActorNA] | s1
 constexpr int kActorMaxU = 64;  // folded features (<= 8 own + 3 per message; <= 128 slots: <= 8 + 3 x 15)
 constexpr int kActorTailS1 = (2 + kActorNA) * kActorRows + kActorNA;
@@ -70,7 +78,9 @@ struct ActorOut {
   unsigned long long* count_next;  // count slab of the tick these actions drive, or null
   unsigned long long* prof;        // diagnostics: [grid][8] per-phase shader cycles, or null
   int tiles;                       // 32-house tiles to run: 0 all, 1 interior (not the first or last), 2 the
-                                   // first and last (the sharded ring halo's readers; mdr_actor_rollout_sharded)
+                                   // first and last (the sharded ring halo's readers; mdr_actor_rollout_sharded);
+                                   // fp16-split form: bits 2 and up = the launch's index among launch_actor's
+                                   // launches of 64 tiles per wave
   unsigned* ovf;                   // fp16-split form: [0] tiles that met a non-finite logit, [1] tiles whose
                                    // logits came from the scalar fp32 fallback (actor_tile_fp32), or null
 };

@@ -21,9 +21,11 @@
 //                     ah·bl + al·bh (3 MFMAs per term, the dropped al·bl and lo's rounding <= 2^-22
 //                     relative).  fp16's range is kept by power-of-two per-layer weight scales chosen
 //                     at pack time (exact: they fold into the biases and the fp32 output layer), so
-//                     small weights' lo parts stay out of fp16 subnormals; an activation beyond fp16's
-//                     range makes a non-finite logit, which the kernel counts (ActorOut.ovf,
-//                     mdr_actor_status).  MDR_OPT_ACTOR_FP32_FORM = 1 (kernel PREC 6): the three-way
+//                     small weights' lo parts stay out of fp16 subnormals; a tile whose values leave
+//                     the range this carries (tile_exact: a hidden value >= 2^15, a seconds-since-off
+//                     ratio >= kActorF16Sso) gets its logits in scalar fp32 from the raw weights
+//                     instead, and the kernel counts those tiles and any non-finite logit
+//                     (ActorOut.ovf, mdr_actor_status).  MDR_OPT_ACTOR_FP32_FORM = 1 (kernel PREC 6): the three-way
 //                     bf16 split x = hi + mid + lo (24 significant bits) and a·b ≈ ah·bh + ah·bm + am·bh
 //                     + ah·bl + al·bh + am·bm, 6 MFMAs per term, no range limit.
 //   MDR_PREC_BF16   — one bf16 product per term.
@@ -510,17 +512,22 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
   const uint32_t stride = gridDim.x * (uint32_t)nw;
   // the launch's tiles as virtual indices v < nv (out.tiles: all, the interior ones, or the first and
   // last — the sharded tick runs the interior while the ring halo is in flight)
-  const uint32_t nv = out.tiles == 1 ? ntile - 2u : out.tiles == 2 ? 2u : ntile;
+  // (PREC 4) the host runs a launch per 64 tiles of a wave (launch_actor: the fallback pass's mask is
+  // one 64-bit word): launch c = out.tiles >> 2 covers the virtual tiles [c 64 stride, (c + 1) 64 stride)
+  const int tkind = PREC == 4 ? out.tiles & 3 : out.tiles;
+  const uint32_t nv_all = tkind == 1 ? ntile - 2u : tkind == 2 ? 2u : ntile;
+  const uint32_t vbase = PREC == 4 ? (uint32_t)(out.tiles >> 2) * 64u * stride : 0u;
+  const uint32_t nv = PREC == 4 ? min(nv_all, vbase + 64u * stride) : nv_all;
   auto real_tile = [&](uint32_t v) -> uint32_t {
-    return out.tiles == 1 ? v + 1u : out.tiles == 2 ? (v == 0u ? 0u : ntile - 1u) : v;
+    return tkind == 1 ? v + 1u : tkind == 2 ? (v == 0u ? 0u : ntile - 1u) : v;
   };
   const int nsrc_max = ring ? lo + 32 + hi : 32;
   HouseRegs src{};
   int src_kind = 0;  // 0 none, 1 house, 2 halo
-  // (PREC 4) a row of this lane's current tile holds a seconds-since-off ratio int(sso / L) >= 2^15
-  // (a house off for more than 2^15 L seconds: beyond what fp16 carries with room to spare)
+  // (PREC 4) a row of this lane's current tile holds a seconds-since-off ratio int(sso / L) >=
+  // kActorF16Sso (mdr_actor.h: beyond what the per-layer weight scale carries at fp32's accuracy)
   bool xbig = false;
-  const uint32_t xthr = dv.L <= 131071u ? 32768u * dv.L : 0xFFFFFFFFu;
+  const uint32_t xthr = dv.L <= 0xFFFFFFFFu / kActorF16Sso ? kActorF16Sso * dv.L : 0xFFFFFFFFu;
 
   // source s of tile tl: ring = house b0 - lo + s (message source), table = house b0 + s (s < 32)
   auto source_of = [&](uint32_t tl, int s, HouseRegs& rg) -> int {
@@ -545,7 +552,7 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
       const int hh = j < 0 ? (int)(j + lo) : (int)(lo + (j - (int64_t)n));
       const float* src = o.halo_next && hh >= lo ? o.halo_next + (size_t)(hh - lo) * M : o.halo_msg + (size_t)hh * M;
       for (int m = 0; m < M; ++m) row[m] = src[m];
-      if (PREC == 4) xbig = xbig || src[1] >= 32768.f;  // (a message's sso ratio, msg_from_regs)
+      if (PREC == 4) xbig = xbig || src[1] >= (float)kActorF16Sso;  // (a message's sso ratio, msg_from_regs)
     } else if (kind == 1) {
       if (PREC == 4) xbig = xbig || hv_sso(rg.w) >= xthr;
       const int t = s - lo;
@@ -588,7 +595,7 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
           } else {
             msg_features(p, o, j, s_cf, row + k * d.m4, dv);
           }
-          if (PREC == 4) xbig = xbig || row[k * d.m4 + 1] >= 32768.f;  // (the message's sso ratio)
+          if (PREC == 4) xbig = xbig || row[k * d.m4 + 1] >= (float)kActorF16Sso;  // (the message's sso ratio)
         }
       }
     }
@@ -631,7 +638,7 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
     FragT hs[KS2][2][NS];
     // fp16-split form (PREC 4): layer 2's operand relu(layer 1) must stay inside fp16's range.  Layer 1
     // tracks its maximum (on the bits: non-negative floats order as integers); a tile holding a value
-    // >= 2^15, or an input beyond it (xbig), has its logits computed again in scalar fp32 from the raw
+    // >= 2^15, or an sso ratio >= kActorF16Sso (xbig), has its logits computed again in scalar fp32 from the raw
     // weights (actor_tile_fp32: rare), which stage Y uses instead (tile_exact).
     {
       uint32_t mbits = 0u;
@@ -815,7 +822,7 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
   };
 
   // ---- the wave's tiles: build(t0) | X(t0) | Y(t0) + build(t1) | X(t1) | ... | Y(t_last)
-  const uint32_t v0 = blockIdx.x * (uint32_t)nw + (uint32_t)wv;
+  const uint32_t v0 = vbase + blockIdx.x * (uint32_t)nw + (uint32_t)wv;  // (vbase: PREC 4, the launch's first tile)
   const int n_my = v0 < nv ? (int)((nv - 1u - v0) / stride + 1u) : 0;
   if (n_my > 0) {
     src_kind = source_of(real_tile(v0), lane, src);
@@ -834,8 +841,7 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
     const uint32_t next = vj + stride < nv ? real_tile(vj + stride) : ntile;  // (ntile: none)
     if (PROF && lane == 0) pacc[7] += 1;
     stage_x(tj, next);
-    const bool defer = PREC == 4 && tile_exact && j < 64;
-    if (PREC == 4 && tile_exact && !defer && lane == 0 && out.ovf) atomicAdd(out.ovf, 1u);  // (> 64 tiles a wave)
+    const bool defer = PREC == 4 && tile_exact;  // (j < 64: a launch has at most 64 tiles per wave)
     if (defer) exact_tiles |= 1ull << j;
     stage_y(tj, next, (j & 1) == 0, defer, false, make_float2(0.f, 0.f));
     if (j + 1 < n_my) stage_build(next);

@@ -93,6 +93,7 @@ struct mdr_ctx {
   bool greedy_sort = false;              // MDR_OPT_GREEDY_SORT: the full-sort greedy form only
   bool force_halo = false;               // MDR_OPT_FORCE_HALO: sharded actor halo exchange at world 1
   bool actor_generic = false;            // MDR_OPT_ACTOR_GENERIC: no default-layout k_actor form
+  int actor_grid = 0;                    // MDR_OPT_ACTOR_GRID: cap of k_actor's grid in blocks (0: n_cu)
   bool actor_fp32_bf16 = false;          // MDR_OPT_ACTOR_FP32_FORM: the three-way bf16 fp32 form (kernel PREC 6)
   bool halo_overlap = true;              // MDR_OPT_HALO_OVERLAP: sharded actor tick, halo beside the interior tiles
   bool halo_in_counts = true;            // MDR_OPT_HALO_IN_COUNTS: the next tick's ring halo rides in the count allreduce
@@ -694,6 +695,10 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
       break;
     case MDR_OPT_GQ_ADAPTIVE: c->gq_adaptive = value != 0; break;
     case MDR_OPT_ACTOR_GENERIC: c->actor_generic = value != 0; break;
+    case MDR_OPT_ACTOR_GRID:
+      if (value < 0) return fail(MDR_EARG, "mdr_set_option: ACTOR_GRID must be >= 0");
+      c->actor_grid = (int)std::min<int64_t>(value, (int64_t)c->n_cu);  // (0: no cap)
+      break;
     case MDR_OPT_ACTOR_FP32_FORM:
       if (value != MDR_FP32_F16_SPLIT && value != MDR_FP32_BF16_SPLIT3)
         return fail(MDR_EARG, "mdr_set_option: ACTOR_FP32_FORM must be MDR_FP32_F16_SPLIT or MDR_FP32_BF16_SPLIT3");
@@ -2514,7 +2519,8 @@ int launch_actor(mdr_ctx* c, const mdr_obs_spec* sp, const ObsArgs& o, const dou
   const int64_t ntile_all = (c->kp.n + 31) / 32;
   const int64_t nv = out.tiles == 1 ? ntile_all - 2 : out.tiles == 2 ? 2 : ntile_all;  // (ActorOut.tiles)
   const int64_t ntile = (nv + nw - 1) / nw;  // blocks with at least one tile per wave
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntile, (int64_t)c->n_cu));
+  const int64_t cap = c->actor_grid > 0 ? std::min(c->actor_grid, c->n_cu) : c->n_cu;  // (MDR_OPT_ACTOR_GRID)
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ntile, cap));
   static bool lds_attr = false;  // > 64 KiB of dynamic LDS must be opted into per kernel
   if (!lds_attr) {
     for (const void* k : {MDR_ACTOR_KERNELS(7, 2), MDR_ACTOR_KERNELS(7, 3), MDR_ACTOR_KERNELS(7, 4),
@@ -2542,16 +2548,25 @@ int launch_actor(mdr_ctx* c, const mdr_obs_spec* sp, const ObsArgs& o, const dou
     else MDR_LAUNCH_ACTOR_S(P, F, 8, 4);                         \
   } while (0)
   const int prec = actor_kprec(c);
-  if (out.prof) {
-    if (prec == 1) MDR_LAUNCH_ACTOR(1, true);
-    else if (prec == 4) MDR_LAUNCH_ACTOR(4, true);
-    else if (prec == 6) MDR_LAUNCH_ACTOR(6, true);
-    else MDR_LAUNCH_ACTOR(3, true);
-  } else {
-    if (prec == 1) MDR_LAUNCH_ACTOR(1, false);
-    else if (prec == 4) MDR_LAUNCH_ACTOR(4, false);
-    else if (prec == 6) MDR_LAUNCH_ACTOR(6, false);
-    else MDR_LAUNCH_ACTOR(3, false);
+  // the fp16-split form defers a wave's out-of-range tiles to its fallback pass through a 64-bit mask:
+  // one launch per 64 tiles of a wave (the same grid: launch k covers the virtual tiles [64 k grid nw,
+  // 64 (k + 1) grid nw), ActorOut.tiles bits 2 and up; one launch up to 64 n_cu nw tiles, 6.3M houses
+  // on 256 CUs at 12 waves).  The phase profile holds the last launch's waves.
+  const int64_t per = 64 * (int64_t)grid * nw;
+  const int nlaunch = prec == 4 ? (int)std::max<int64_t>(1, (nv + per - 1) / per) : 1;
+  for (int k = 0; k < nlaunch; ++k) {
+    out.tiles = out_in.tiles | (k << 2);
+    if (out.prof) {
+      if (prec == 1) MDR_LAUNCH_ACTOR(1, true);
+      else if (prec == 4) MDR_LAUNCH_ACTOR(4, true);
+      else if (prec == 6) MDR_LAUNCH_ACTOR(6, true);
+      else MDR_LAUNCH_ACTOR(3, true);
+    } else {
+      if (prec == 1) MDR_LAUNCH_ACTOR(1, false);
+      else if (prec == 4) MDR_LAUNCH_ACTOR(4, false);
+      else if (prec == 6) MDR_LAUNCH_ACTOR(6, false);
+      else MDR_LAUNCH_ACTOR(3, false);
+    }
   }
 #undef MDR_LAUNCH_ACTOR
 #undef MDR_LAUNCH_ACTOR_S

@@ -62,7 +62,7 @@ class DeviceActor:
     def __init__(self, env, actor, precision: str = "bf16x3", fp32_form: str = "f16_split"):
         """precision: "fp32" (the reference Actor's), "bf16x3" or "bf16".  fp32_form: the fused kernel's
         fp32 arithmetic — "f16_split" (fp16 hi/lo operands, 3 MFMAs per term, per-layer power-of-two
-        weight scales; ``status()`` counts tiles whose activations left fp16's range) or "bf16_split3"
+        weight scales; ``status()`` counts the tiles outside its range, which get fp32 logits) or "bf16_split3"
         (three-way bf16 operands, 6 MFMAs per term, no range limit)."""
         if precision not in L.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}")
@@ -95,7 +95,8 @@ class DeviceActor:
         torch.cuda.current_stream(dev).synchronize()  # (the copies are read by later launches only)
 
     def status(self):
-        """mdr_actor_status (synchronises): {range_faults, kernel_prec} — see ``Shard.actor_status``."""
+        """mdr_actor_status (synchronises): {range_faults: tiles with a non-finite logit, kernel_prec,
+        exact: tiles the fp16-split form computed in scalar fp32} — see ``Shard.actor_status``."""
         return self.env.shard.actor_status()
 
     def fused(self) -> bool:

@@ -122,7 +122,9 @@ class HipShard:
     def set_option(self, name: str, value: int):
         """mdr_set_option: an alternative launch form of the same computation (mdr.h MDR_OPT_*:
         step_tpw, fastdiv, window_pipeline, sharded_overlap, greedy_sort, force_halo, halo_overlap,
-        actor_generic, window_thermal, halo_in_counts, gq_band, actor_fp32_form)."""
+        actor_generic, window_thermal, halo_in_counts, gq_band, actor_fp32_form, gq_fused, gq_adaptive;
+        actor_grid: v >= 1 caps the fused actor's grid at min(v, CUs) blocks, 0 = the default grid,
+        the same outputs bit for bit — the tests' way to many tiles per wave; negative: MDR_EARG)."""
         L.check(self.lib.mdr_set_option(self.ctx, L.OPTIONS[name], int(value)), f"mdr_set_option({name})")
 
     def params_changed(self):
@@ -334,8 +336,10 @@ class HipShard:
 
     def actor_status(self):
         """mdr_actor_status (synchronises; counts since the last call): {range_faults: fused fp16-split
-        tiles that met a non-finite logit, kernel_prec: 1 bf16 / 3 bf16x3 / 4 fp16 split / 6 three-way
-        bf16, exact: tiles whose values left fp16's range, their logits computed in scalar fp32}."""
+        tiles that wrote a non-finite logit (nothing else: 0 unless the network itself overflows fp32),
+        kernel_prec: 1 bf16 / 3 bf16x3 / 4 fp16 split / 6 three-way bf16, exact: every tile whose
+        values left the fp16 path's range (a hidden value >= 2^15 after scaling, a seconds-since-off
+        ratio >= 64), its logits computed in scalar fp32 — whatever the tile's place in its wave}."""
         out = (C.c_int64 * 3)()
         L.check(self.lib.mdr_actor_status(self.ctx, out, 3, self.stream()), "mdr_actor_status")
         return {"range_faults": int(out[0]), "kernel_prec": int(out[1]), "exact": int(out[2])}

@@ -40,6 +40,19 @@ def philox_words(seed: int, grp, tick):
     return r[0], r[1]
 
 
+def u01f(seed: int, gid, tick) -> np.ndarray:
+    """philox_u01f (csrc/mdr_actor.hip): the actor's sampling uniform of global house `gid` at tick
+    `tick` — counter (gid lo, gid hi, tick lo, tick hi ^ 0xAC7), key (seed lo ^ 0x3C6EF372, seed hi),
+    float32(c0 >> 8) * 2^-24: a float32 in [0, 1), 24 bits.  Vectorised over gid (and tick)."""
+    gid = np.asarray(gid, np.uint64)
+    tick = np.broadcast_to(np.asarray(tick, np.uint64), gid.shape)
+    s = np.uint64(seed & 0xFFFFFFFFFFFFFFFF)
+    c0 = philox4x32_10(gid & _MASK, gid >> np.uint64(32), tick & _MASK,
+                       (tick >> np.uint64(32)) ^ np.uint64(0xAC7),
+                       (s & _MASK) ^ np.uint64(0x3C6EF372), s >> np.uint64(32))[0]
+    return (c0 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
 def random_actions(seed: int, gids, tick: int) -> np.ndarray:
     """MDR_ACT_RANDOM action of global houses `gids` at tick `tick`: bit (gid & 63) of the first
     64 bits of Philox4x32-10(seed; gid >> 6, tick)."""

@@ -32,6 +32,31 @@ def test_random_action_bit_layout():
     np.testing.assert_array_equal(P.random_actions(seed, gids[100:], tick), a[100:])
 
 
+def test_u01f_range_grid_and_vectorisation():
+    """u01f (the actor's sampling uniform, mdr_actor.hip philox_u01f): float32 values in [0, 1) that
+    are exact multiples of 2^-24, from word 0 of the documented counter / key; the array form equals
+    the scalar form house by house."""
+    seed, tick = 0x1234_5678_9ABC_DEF0, (5 << 32) | 77
+    gids = np.concatenate([np.arange(0, 4099, dtype=np.uint64),
+                           np.array([2**32 - 1, 2**32, 2**40 + 3], np.uint64)])  # (the gid's high word too)
+    u = P.u01f(seed, gids, tick)
+    assert u.dtype == np.float32 and u.shape == gids.shape
+    assert u.min() >= 0.0 and u.max() < 1.0
+    k = u.astype(np.float64) * 2.0 ** 24
+    np.testing.assert_array_equal(k, np.floor(k))  # exact multiples of 2^-24
+    assert 0.45 < u.mean() < 0.55
+    # the counter and key as documented, through the known-answer-checked block function
+    for i in (0, 1, 63, 64, 4098, 4099, 4100, 4101):
+        g = int(gids[i])
+        c0 = int(P.philox4x32_10(g & 0xFFFFFFFF, g >> 32, tick & 0xFFFFFFFF, (tick >> 32) ^ 0xAC7,
+                                 (seed & 0xFFFFFFFF) ^ 0x3C6EF372, seed >> 32)[0])
+        assert float(u[i]) == (c0 >> 8) / 2.0 ** 24
+        assert P.u01f(seed, np.uint64(g), tick) == u[i]  # scalar == vector element
+    # a shard offset does not change a house's uniform (keyed by global id); the tick does
+    np.testing.assert_array_equal(P.u01f(seed, gids[100:], tick), u[100:])
+    assert np.mean(P.u01f(seed, gids, tick + 1) == u) < 0.01
+
+
 def test_random_actions_are_fair():
     a = P.random_actions(99, np.arange(1 << 18, dtype=np.uint64), 3)
     assert abs(a.mean() - 0.5) < 4 * 0.5 / np.sqrt(a.size)
