@@ -535,6 +535,43 @@ int mdr_actor_rollout_sharded(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, 
                               int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                               void* stream);
 
+/* ---- replay snapshots: training data from the fused rollout ------------------------------ */
+/* The reference stores the normalised state of every agent every tick (training_manager.py:224-240,
+ * mappo.py:105-126): n_feat float32 per house-tick.  An obs row is a function of the house's and
+ * its neighbours' t_air, t_mass and hvac word, the tick's four obs scalars and parameters that are
+ * fixed between resets, so a snapshot keeps 8 + 8 + 4 B per house-tick and one scalar row per tick,
+ * and mdr_obs_gather rebuilds any transition's row on demand, bit-identical to mdr_obs of that tick.
+ * Single shard only (a neighbour's snapshot would live on another shard): a context with a
+ * communicator or world > 1 gives MDR_ESTATE. */
+typedef struct mdr_snap {
+  int32_t struct_bytes;   /* = sizeof(mdr_snap); anything else is MDR_EARG ("mdr_snap" in mdr_last_error) */
+  int32_t cap_rows;       /* ticks the slabs hold */
+  int64_t row_stride;     /* elements between rows, >= n_local */
+  double* t_air;          /* [cap_rows][row_stride], caller-owned device memory */
+  double* t_mass;         /* [cap_rows][row_stride] */
+  uint32_t* hvac;         /* [cap_rows][row_stride] */
+  double* scalars;        /* [cap_rows][4], mdr_obs_scalars rows, p filled on device */
+} mdr_snap;
+/* Row `row` <- the current t_air / t_mass / hvac of every local house and {p, s, solar, t_od} of
+ * sc (p_dev, when non-NULL, overrides sc->p with the device scalar, as in mdr_obs).  MDR_EARG: row
+ * outside [0, cap_rows), row_stride < n_local, a NULL slab. */
+int mdr_snapshot(mdr_ctx* ctx, const mdr_snap* snap, int row, const mdr_obs_scalars* sc, const double* p_dev,
+                 void* stream);
+/* mdr_actor_rollout that also records tick t's pre-step state and obs scalars (what its actor
+ * reads) into snapshot row row0 + t: one more kernel node per tick of the captured graph.
+ * snap == NULL is mdr_actor_rollout.  MDR_EARG: row0 < 0 or row0 + n_ticks > cap_rows,
+ * row_stride < n_local, a NULL slab. */
+int mdr_actor_rollout_snap(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const mdr_obs_scalars* obs_sc,
+                           const mdr_obs_spec* obs, uint8_t* action, int64_t act_stride, float* prob,
+                           int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                           int use_graph, const mdr_snap* snap, int row0, void* stream);
+/* float32 obs[m][n_feat]: row q is the obs row of house idx[q] % n_local at the tick of snapshot
+ * row idx[q] / n_local (idx: device int64[m]), over the first `rows` snapshot rows.  An idx outside
+ * [0, rows * n_local) is not dereferenced: its row is NaN.  MDR_EARG: rows outside [0, cap_rows],
+ * m < 0, a spec with halo_msg or msg_all set, a NULL slab. */
+int mdr_obs_gather(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_snap* snap, int rows, const int64_t* idx,
+                   int64_t m, float* obs, void* stream);
+
 /* ---- interpolated base power ---------------------------------------- */
 /* Replaces PowerInterpolator (server/app/core/environment/power_grid/interpolation.py:24-264) as
  * PowerGrid.power_step calls it every interp_update_period seconds (power_grid.py:149-161): the

@@ -2716,16 +2716,82 @@ int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars*
   return rc;
 }
 
-int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                      const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                      int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
-                      void* stream) {
+// ---- replay snapshots (mdr.h mdr_snap): argument checks and the k_snap launch
+static int check_snap_struct(const mdr_snap* sn, const char* who) {
+  if (sn->struct_bytes != (int32_t)sizeof(mdr_snap))
+    return fail(MDR_EARG, std::string(who) + ": mdr_snap.struct_bytes is not sizeof(mdr_snap)");
+  return MDR_OK;
+}
+
+// rows [row0, row0 + nrows) of the caller's slabs can take this context's houses
+static int check_snap(mdr_ctx* c, const mdr_snap* sn, int row0, int nrows, const char* who) {
+  if (has_comm(c) || c->world > 1)
+    return fail(MDR_ESTATE, std::string(who) + ": snapshots are single-shard (a neighbour's rows live on another shard)");
+  if (!sn->t_air || !sn->t_mass || !sn->hvac || !sn->scalars) return fail(MDR_EARG, std::string(who) + ": null snapshot slab");
+  if (sn->row_stride < c->kp.n) return fail(MDR_EARG, std::string(who) + ": mdr_snap.row_stride < n_local");
+  if (sn->cap_rows < 0 || row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > sn->cap_rows)
+    return fail(MDR_EARG, std::string(who) + ": snapshot rows outside [0, cap_rows)");
+  return MDR_OK;
+}
+
+static int launch_snap(mdr_ctx* c, const mdr_snap* sn, int row, const double* sc_dev, const double* p_dev,
+                       const mdr_obs_scalars& sc, hipStream_t st) {
+  const int64_t off = (int64_t)row * sn->row_stride;
+  const unsigned grid = std::max(1u, std::min(blocks((c->kp.n + 1) / 2, kSnapBlock), (unsigned)kSnapGrid));
+  hipLaunchKernelGGL(k_snap, dim3(grid), dim3(kSnapBlock), 0, st, c->kp, sn->t_air + off, sn->t_mass + off,
+                     sn->hvac + off, sn->scalars + 4 * (int64_t)row, p_dev, sc_dev, sc.p, sc.s, sc.solar, sc.t_od);
+  LAUNCH_CHECK("k_snap");
+  return MDR_OK;
+}
+
+int mdr_snapshot(mdr_ctx* c, const mdr_snap* sn, int row, const mdr_obs_scalars* sc, const double* p_dev,
+                 void* stream) {
+  if (sn)
+    if (int rc = check_snap_struct(sn, "mdr_snapshot")) return rc;
+  if (!c || !sn || !sc) return fail(MDR_EARG, "mdr_snapshot: null argument");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_snapshot: context not bound");
+  if (int rc = check_snap(c, sn, row, 1, "mdr_snapshot")) return rc;
+  return launch_snap(c, sn, row, nullptr, p_dev, *sc, S(stream));
+}
+
+int mdr_obs_gather(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, int rows, const int64_t* idx, int64_t m,
+                   float* obs, void* stream) {
+  if (sn)
+    if (int rc = check_snap_struct(sn, "mdr_obs_gather")) return rc;
+  if (!c || !sp || !sn || m < 0 || (m > 0 && (!idx || !obs))) return fail(MDR_EARG, "mdr_obs_gather: bad argument");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_obs_gather: context not bound");
+  if (int rc = check_obs_spec(sp, "mdr_obs_gather")) return rc;
+  if (sp->halo_msg || sp->msg_all) return fail(MDR_EARG, "mdr_obs_gather: single shard only (halo_msg / msg_all set)");
+  if (int rc = check_snap(c, sn, 0, rows, "mdr_obs_gather")) return rc;
+  if (m == 0) return MDR_OK;
+  ObsArgs o = obs_args(c, sp, nullptr);
+  const size_t tile = ((size_t)kGatherRows * sp->n_feat + 3) & ~(size_t)3;
+  const size_t nmsg = (size_t)(sp->comm_mode == MDR_COMM_RING ? sp->n_comm + 1 : 0) * o.msg_w;
+  const size_t bytes = (tile + kGatherRows * (nmsg + kObsConst)) * sizeof(float);
+  if (bytes > 64 * 1024) return fail(MDR_EARG, "mdr_obs_gather: obs row too wide for one LDS tile");
+  if ((m + kGatherRows - 1) / kGatherRows > 0x7fffffffLL)
+    return fail(MDR_EARG, "mdr_obs_gather: m too large for one launch");
+  hipLaunchKernelGGL(k_obs_gather, dim3(blocks(m, kGatherRows)), dim3(kGatherRows * kGatherLanes), bytes, S(stream),
+                     c->kp, o, sn->t_air, sn->t_mass, sn->hvac, sn->row_stride, sn->scalars, rows, idx, m, obs);
+  LAUNCH_CHECK("k_obs_gather");
+  return MDR_OK;
+}
+
+// mdr_actor_rollout (snap == NULL: its launches and graph keys) / mdr_actor_rollout_snap
+static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                              const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
+                              const mdr_snap* snap, int row0, void* stream, const char* who) {
   drop_begun(c);
-  if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1) return fail(MDR_EARG, "mdr_actor_rollout: bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_rollout: context not bound");
-  if (int rc = check_actor_obs(c, sp, "mdr_actor_rollout", S(stream))) return rc;
+  if (snap)
+    if (int rc = check_snap_struct(snap, who)) return rc;
+  if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (snap)
+    if (int rc = check_snap(c, snap, row0, n, who)) return rc;
+  if (int rc = check_actor_obs(c, sp, who, S(stream))) return rc;
   if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, "mdr_actor_rollout: common penalty modes need the per-step API");
+    return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
   hipStream_t st = S(stream);
   if (int rc = refresh_if_dirty(c, st)) return rc;
   if (int rc = stage_ticks(c, n, ticks, st)) return rc;
@@ -2743,6 +2809,9 @@ int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_sc
       ot.sc_dev = c->d_obs_sc + 4 * t;
       ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act, prob ? prob + (int64_t)t * prob_stride : nullptr,
                    nullptr, nullptr, slab_at(c, c->ring), nullptr};
+      // the state and scalars this tick's actor reads, into snapshot row row0 + t
+      if (snap)
+        if (int rc = launch_snap(c, snap, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{}, ls)) return rc;
       if (int rc = launch_actor(c, sp, ot, p_dev, 0, c->d_ticks + t, out, ls)) return rc;
       if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
                                reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, ls))
@@ -2760,6 +2829,10 @@ int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_sc
                            (int64_t)(uintptr_t)reward, rew_stride, (int64_t)(uintptr_t)p_dev,
                            (int64_t)(uintptr_t)sp->comm_table,
                            (int64_t)(uintptr_t)sp->halo_msg, sp->n_feat, (int64_t)(uintptr_t)c->d_actor};
+  if (snap)  // (longer keys: never equal to a rollout's without snapshots)
+    key.insert(key.end(), {(int64_t)(uintptr_t)snap->t_air, (int64_t)(uintptr_t)snap->t_mass,
+                           (int64_t)(uintptr_t)snap->hvac, (int64_t)(uintptr_t)snap->scalars, snap->row_stride,
+                           (int64_t)row0});
   auto it = c->actor_graphs.find(key);
   if (it == c->actor_graphs.end()) {
     hipGraphExec_t ex;
@@ -2772,6 +2845,22 @@ int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_sc
   ++c->graph_launches[1];
   c->counts_ready = false;
   return MDR_OK;
+}
+
+int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                      const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                      int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
+                      void* stream) {
+  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                            use_graph, nullptr, 0, stream, "mdr_actor_rollout");
+}
+
+int mdr_actor_rollout_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                           const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                           int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
+                           const mdr_snap* snap, int row0, void* stream) {
+  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                            use_graph, snap, row0, stream, "mdr_actor_rollout_snap");
 }
 
 // Sharded MA-PPO rollout (config C5): per tick

@@ -207,6 +207,16 @@ __global__ void k_halo_pack(KParams p, ObsArgs o, int lo, int hi, float* out);
 __global__ void k_halo_step_pack(KParams p, ObsArgs o, const uint8_t* action, const TickArgs* tkp, int lo, int hi,
                                  int rank, int world, float* rows);
 __global__ void k_msg_pack(KParams p, ObsArgs o, float* out);
+// replay snapshots (mdr_snapshot / mdr_actor_rollout_snap / mdr_obs_gather)
+constexpr int kSnapBlock = 256;     // k_snap: 16 B per lane and pass
+constexpr int kSnapGrid = 4096;     // its grid cap (a 2^20-house row: one 16-B vector per lane and array)
+constexpr int kGatherRows = 16;     // transitions per k_obs_gather block ...
+constexpr int kGatherLanes = 16;    // ... and the lanes staging each one's message sources
+__global__ void k_snap(KParams p, double* t_air, double* t_mass, uint32_t* hvac, double* sc_row, const double* p_dev,
+                       const double* sc_dev, double P, double s, double solar, double t_od);
+__global__ void k_obs_gather(KParams p, ObsArgs o, const double* s_air, const double* s_mass, const uint32_t* s_hvac,
+                             int64_t row_stride, const double* scalars, int rows, const int64_t* idx, int64_t m,
+                             float* obs);
 __global__ void k_greedy_keys(KParams p, double* key, int* idx);
 __global__ void k_greedy_gather(KParams p, const int* perm, double* psorted, uint8_t* lsorted);
 __global__ void k_greedy_walk(int64_t n, const double* incl, const double* psorted,

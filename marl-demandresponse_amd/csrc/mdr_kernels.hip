@@ -2078,6 +2078,111 @@ __global__ void k_msg_pack(KParams p, ObsArgs o, float* out) {
   if (i < p.n) msg_features(p, o, i, cf, out + i * o.msg_w, obs_div(p));
 }
 
+// ------------------------------------------------------------------------------ replay snapshots
+// A stored transition keeps the 20 B of a house's state the obs row depends on (t_air, t_mass, the
+// hvac word) and one scalar row per tick, in place of the reference's normalised state of every
+// agent every tick (training_manager.py:224-240, mappo.py:105-126); k_obs_gather rebuilds rows.
+//
+// n elements src -> dst: 16-B vectors grid-stride where both ends are 16-B aligned (+ a scalar
+// tail), scalars otherwise.
+template <typename T>
+__device__ __forceinline__ void snap_copy(const T* __restrict__ src, T* __restrict__ dst, int64_t n, int64_t gtid,
+                                          int64_t gthr) {
+  constexpr int V = 16 / (int)sizeof(T);
+  if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
+    const int64_t nv = n / V;
+    for (int64_t q = gtid; q < nv; q += gthr)
+      reinterpret_cast<uint4*>(dst)[q] = reinterpret_cast<const uint4*>(src)[q];
+    for (int64_t q = nv * V + gtid; q < n; q += gthr) dst[q] = src[q];
+  } else {
+    for (int64_t q = gtid; q < n; q += gthr) dst[q] = src[q];
+  }
+}
+
+// One snapshot row: the state arrays of all p.n houses into t_air / t_mass / hvac (the row's base
+// pointers), and sc_row = {P, s, solar, t_od} (mdr_obs_scalars layout; P from p_dev, the rest from
+// sc_dev's {-, s, solar, t_od} row, when given — what k_obs / k_actor of the same tick read).
+__global__ void __launch_bounds__(kSnapBlock) k_snap(KParams p, double* __restrict__ t_air, double* __restrict__ t_mass,
+                                                     uint32_t* __restrict__ hvac, double* __restrict__ sc_row,
+                                                     const double* __restrict__ p_dev,
+                                                     const double* __restrict__ sc_dev, double P, double s,
+                                                     double solar, double t_od) {
+  const int64_t gtid = (int64_t)blockIdx.x * kSnapBlock + threadIdx.x;
+  const int64_t gthr = (int64_t)gridDim.x * kSnapBlock;
+  snap_copy<double>(p.t_air, t_air, p.n, gtid, gthr);
+  snap_copy<double>(p.t_mass, t_mass, p.n, gtid, gthr);
+  snap_copy<uint32_t>(p.hvac, hvac, p.n, gtid, gthr);
+  if (gtid == 0) {
+    sc_row[0] = p_dev ? *p_dev : P;
+    sc_row[1] = sc_dev ? sc_dev[1] : s;
+    sc_row[2] = sc_dev ? sc_dev[2] : solar;
+    sc_row[3] = sc_dev ? sc_dev[3] : t_od;
+  }
+}
+
+// obs[q][0 .. F) = the row k_obs wrote for house idx[q] % p.n at the tick of snapshot row
+// idx[q] / p.n.  kGatherRows transitions per block, kGatherLanes lanes each: the lanes stage the
+// row's obs_consts and (ring) its K + 1 message sources from the snapshot row into the row's own
+// LDS areas, lane 0 assembles the row (mdr_obs_dev.h: the arithmetic of k_obs, so the same bits),
+// then the block flushes its contiguous output rows with 16-B stores.  An index outside
+// [0, rows * p.n) is not dereferenced: its row is NaN.  Single shard (o.halo_msg, o.msg_all null).
+__global__ void __launch_bounds__(kGatherRows* kGatherLanes)
+    k_obs_gather(KParams p, ObsArgs o, const double* __restrict__ s_air, const double* __restrict__ s_mass,
+                 const uint32_t* __restrict__ s_hvac, int64_t row_stride, const double* __restrict__ scalars,
+                 int rows, const int64_t* __restrict__ idx, int64_t m, float* __restrict__ obs) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int F = o.n_feat;
+  const int nmsg = (o.comm_mode == MDR_COMM_RING ? o.n_comm + 1 : 0) * o.msg_w;
+  float* tile = smem;                                                   // [kGatherRows][F]
+  float* msgs = smem + ((kGatherRows * F + 3) & ~3);                 // [kGatherRows][nmsg]
+  float* cf_all = msgs + kGatherRows * nmsg;                         // [kGatherRows][kObsConst]
+  const int r = threadIdx.x / kGatherLanes, lane = threadIdx.x % kGatherLanes;
+  const int64_t q0 = (int64_t)blockIdx.x * kGatherRows;
+  const int nb = (int)min((int64_t)kGatherRows, m - q0);
+  float* row = tile + r * F;
+  float* msg = msgs + r * nmsg;
+  float* cf = cf_all + r * kObsConst;
+  const int64_t i = r < nb ? idx[q0 + r] : -1;
+  const bool ok = i >= 0 && i < (int64_t)rows * p.n;
+  const int64_t t = ok ? i / p.n : 0, h = ok ? i % p.n : 0;
+  KParams pr = p;  // the houses as they were at snapshot row t
+  pr.t_air = const_cast<double*>(s_air) + t * row_stride;
+  pr.t_mass = const_cast<double*>(s_mass) + t * row_stride;
+  pr.hvac = const_cast<uint32_t*>(s_hvac) + t * row_stride;
+  ObsArgs orow = o;
+  orow.sc_dev = nullptr;
+  double P = 0.0;
+  if (ok) {
+    const double* sc = scalars + 4 * t;
+    P = sc[0];
+    orow.p = P;
+    orow.s = sc[1];
+    orow.solar = sc[2];
+    orow.t_od = sc[3];
+    obs_consts(pr, orow, P, cf, lane, kGatherLanes);
+  }
+  __syncthreads();
+  const ObsDiv dv = obs_div(pr);
+  if (ok) obs_stage_ring(pr, orow, h, 1, cf, msg, lane, kGatherLanes, dv);
+  __syncthreads();
+  if (ok) {
+    if (lane == 0) obs_build_row(pr, orow, h, 0, cf, msg, row, dv);
+  } else if (r < nb) {
+    for (int f = lane; f < F; f += kGatherLanes) row[f] = __int_as_float(0x7fc00000);
+  }
+  __syncthreads();
+  const int64_t nflt = (int64_t)nb * F;
+  float* dst = obs + q0 * F;
+  if ((((uintptr_t)dst) & 15) == 0) {
+    const int64_t n4 = nflt >> 2;
+    for (int64_t q = threadIdx.x; q < n4; q += blockDim.x)
+      reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(tile)[q];
+    for (int64_t q = (n4 << 2) + threadIdx.x; q < nflt; q += blockDim.x) dst[q] = tile[q];
+  } else {
+    for (int64_t q = threadIdx.x; q < nflt; q += blockDim.x) dst[q] = tile[q];
+  }
+}
+
 // --------------------------------------------------------------------------------------- greedy
 // GreedyMyopic.get_action (greedy_myopic_controller.py:67-104), device form:
 //   key_i = -(T_i - target_i), sorted ascending (stable radix sort; pandas' quicksort tie order

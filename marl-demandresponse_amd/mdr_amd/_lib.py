@@ -83,6 +83,13 @@ class mdr_obs_scalars(C.Structure):
     _fields_ = [("p", C.c_double), ("s", C.c_double), ("solar", C.c_double), ("t_od", C.c_double)]
 
 
+class mdr_snap(C.Structure):
+    """Replay snapshot slabs (mdr.h mdr_snap); ``struct_bytes`` is its own size check, so it is not
+    one of ABI_STRUCTS."""
+    _fields_ = [("struct_bytes", C.c_int32), ("cap_rows", C.c_int32), ("row_stride", C.c_int64),
+                ("t_air", C.c_void_p), ("t_mass", C.c_void_p), ("hvac", C.c_void_p), ("scalars", C.c_void_p)]
+
+
 class mdr_actor_spec(C.Structure):
     _fields_ = [("n_in", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32), ("n_act", C.c_int32),
                 ("precision", C.c_int32)]
@@ -174,6 +181,10 @@ SIGNATURES = {
     "mdr_actor_rollout": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64,
                               VP, I64, VP, I, VP]),
     "mdr_actor_rollout_sharded": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64, VP, I64, VP, VP]),
+    "mdr_snapshot": (I, [VP, P(mdr_snap), I, P(mdr_obs_scalars), VP, VP]),
+    "mdr_actor_rollout_snap": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64,
+                                   VP, I64, VP, I, P(mdr_snap), I, VP]),
+    "mdr_obs_gather": (I, [VP, P(mdr_obs_spec), P(mdr_snap), I, VP, I64, VP, VP]),
     "mdr_actor_profile": (I, [VP, P(mdr_obs_spec), P(mdr_obs_scalars), VP, P(D), VP]),
     "mdr_interp_load": (I, [VP, P(mdr_interp_spec)]),
     "mdr_interp_values": (I, [VP, VP, I, D, D, D, VP, VP]),

@@ -130,19 +130,32 @@ class DeviceActor:
         env._counts_ready = ("actor", action.data_ptr()) if count_next else 0
         return action, prob
 
-    def rollout(self, n_ticks: int, rewards=None, actions=None, probs=None, use_graph: bool = True):
+    def rollout(self, n_ticks: int, rewards=None, actions=None, probs=None, use_graph: bool = True, store=None):
         """n_ticks of (select_actions -> env.step) in one graph-captured C call (individual_L2;
         sharded: the library's C loop).  The common penalty modes (common_L2, common_max_error,
         mixture: rewards_calculator.py:29-203) need the cluster's penalty sum / max between the
         step and the reward, so they run tick by tick (select_actions -> step_tensor, whose penalty
         reduce — and allreduce when sharded — finishes every tick's rewards).  ``rewards`` float64
         [n_ticks, N] (or [N], overwritten each tick); ``actions`` u8 / ``probs`` f32 [n_ticks, N]
-        (or [N]) optional outputs."""
+        (or [N]) optional outputs.
+
+        ``store`` (mdr_amd.replay.RolloutStore): the ticks are appended to it as training
+        transitions — each tick's pre-step state snapshot is recorded inside the same graph
+        (mdr_actor_rollout_snap) and the store's next ``actions`` / ``probs`` / ``rewards`` rows are
+        the outputs (``rewards`` / ``actions`` / ``probs`` must then be None)."""
         torch = _torch()
         env = self.env
         sh = env.shard
+        row0 = 0
+        if store is not None:
+            if store.env is not env:
+                raise ValueError("the store belongs to another environment")
+            if rewards is not None or actions is not None or probs is not None:
+                raise ValueError("with a store, its own actions / probs / rewards rows are the outputs")
+            row0 = store.begin_rows(n_ticks)  # (ValueError: overflow, a reset since its rows were taken)
+            rewards, actions, probs = (x[row0:row0 + n_ticks] for x in (store.rewards, store.actions, store.probs))
         if sh.penalty_mode != 0 or (env.world > 1 and not getattr(env._comm, "native", False)):
-            return self._rollout_stepwise(n_ticks, rewards, actions, probs)
+            return self._rollout_stepwise(n_ticks, rewards, actions, probs, store)
         sharded = env.world > 1
         spec, _sc, keep = env.bound_obs_spec() if not sharded else (env.obs_spec(), None, [])
         self._check_obs(spec)
@@ -172,7 +185,12 @@ class DeviceActor:
                                          sl(rewards, rs), rs)
             else:
                 g = use_graph and (k == n_ticks or not (rs or as_ or ps))
-                sh.actor_rollout(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps, sl(rewards, rs), rs, g)
+                if store is not None:  # this window's snapshot rows follow the previous windows'
+                    sh.actor_rollout_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
+                                          sl(rewards, rs), rs, store.snap, row0 + done, g)
+                    store.commit_rows(k)
+                else:
+                    sh.actor_rollout(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps, sl(rewards, rs), rs, g)
             env._P_dev_valid = True
             env.finish_grid_step()
             done += k
@@ -183,11 +201,12 @@ class DeviceActor:
         return rewards
 
 
-    def _rollout_stepwise(self, n_ticks, rewards, actions, probs):
+    def _rollout_stepwise(self, n_ticks, rewards, actions, probs, store=None):
         """Per tick select_actions (sharded: the ring halo, ON counts of the actions) then
         step_tensor (count allreduce, step, and for the common penalty modes the penalty reduce +
         reward finalize) from Python — the same launches and exchanges as the C loop, plus the
-        penalty stages the C loops do not have."""
+        penalty stages the C loops do not have.  ``store``: ``env.snapshot`` appends each tick's
+        pre-step state before its select_actions."""
         torch = _torch()
         env = self.env
         sh = env.shard
@@ -199,6 +218,8 @@ class DeviceActor:
         for t in range(n_ticks):
             a = a_tmp if actions is None else (actions[t] if actions.dim() == 2 else actions)
             p = p_tmp if probs is None else (probs[t] if probs.dim() == 2 else probs)
+            if store is not None:
+                env.snapshot(store)
             self.select_actions(action=a, prob=p, count_next=True)
             env.step_tensor(a, rewards=rewards[t] if rewards.dim() == 2 else rewards)
         return rewards

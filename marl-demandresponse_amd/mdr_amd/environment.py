@@ -222,6 +222,9 @@ class Environment:
         hv = hp.hvac_prop
         rng = self.rng
         n = cp.nb_agents
+        # population epoch: targets, parameters and links are re-drawn below, so state snapshots
+        # taken before (mdr_amd.replay.RolloutStore) no longer reproduce their obs rows
+        self._pop_epoch = getattr(self, "_pop_epoch", 0) + 1
         self._offset, self._n_local = shard_range(n, self.rank, self.world)
         # Cluster.reset (cluster.py:49-69): pre-noise power / max power, comm graph, get_obs()
         pre = hv.cooling_capacity / hv.cop
@@ -821,6 +824,17 @@ class Environment:
             torch.cuda.current_stream(sh.device).synchronize()
         return out
 
+    def snapshot(self, store):
+        """Append the current pre-step state (t_air, t_mass, hvac) and obs scalars as one row of
+        ``store`` (mdr_amd.replay.RolloutStore): what ``obs_tensor()`` would be built from now.  The
+        per-tick API, for loops that do not use the fused rollout.  Returns the row index."""
+        row = store.begin_rows(1)
+        sc = L.mdr_obs_scalars(float(self._P_host), float(self.power_grid.current_signal),
+                               float(self._solar), float(self.current_od_temp))
+        self._shard.snapshot(store.snap, row, sc, use_p_dev=self._P_dev_valid)
+        store.commit_rows(1)
+        return row
+
     def _params_host(self):
         if self._host_params is None:
             self._host_params = self._shard.host_params()
@@ -911,6 +925,7 @@ class Environment:
 
     def load_state_dict(self, sd: dict) -> None:
         sh = self._shard
+        self._pop_epoch = getattr(self, "_pop_epoch", 0) + 1  # (parameters and links replaced)
         if list(sd["cap_values"]) != list(self._cap_values):
             self._ensure_shard(sd["cap_values"])
             self._cap_values = list(sd["cap_values"])

@@ -118,14 +118,18 @@ class DeviceMAPPO:
     """MAPPO with device actor rollouts, device transition storage and the PPO update on the GPU."""
 
     def __init__(self, env, config: Optional[MAPPOConfig] = None, num_action: int = 2, seed: int = 1,
-                 precision: str = "bf16x3", returns: str = "reference", sampler: str = "reference"):
+                 precision: str = "bf16x3", returns: str = "reference", sampler: str = "reference",
+                 collect_ticks: int = 0):
         """``sampler``: the minibatch permutation of each PPO epoch — "reference" (default) draws it
         from the global torch CPU generator exactly as the reference's SubsetRandomSampler does, so
         reference-seeded runs keep the reference's minibatch order and later CPU draws at any size;
         "device" (explicit opt-in) draws it on the GPU (torch.randperm on the device generator: no
         L-element host permutation and copy per epoch at C5's N x T transitions; another order);
         "auto" = "reference" up to 2^20 transitions and "device" beyond.  ``last_sampler`` records
-        which one the last update used."""
+        which one the last update used.
+
+        ``collect_ticks`` > 0 allocates a ``RolloutStore`` of that many ticks (``self.store``):
+        ``collect`` then fills it from the graph-captured rollout and ``update`` trains from it."""
         torch = _torch()
         if returns not in ("reference", "per_agent"):
             raise ValueError("returns must be 'reference' (the reference's buffer order) or 'per_agent'")
@@ -148,6 +152,11 @@ class DeviceMAPPO:
         self.critic_net_optimizer = torch.optim.Adam(self.critic_net.parameters(), self.cfg.lr_critic)
         self.device_actor = DeviceActor(env, self.actor_net, precision=precision)
         self.buffer = []  # per tick: (state, action, prob, reward, done)
+        self.store = None  # or the compact transitions of collect()
+        if collect_ticks > 0:
+            from .replay import RolloutStore
+
+            self.store = RolloutStore(env, collect_ticks)
         self.counter = 0
         self.training_step = 0
         self.last_actions = None
@@ -165,11 +174,30 @@ class DeviceMAPPO:
         """mappo.py:105-126 for all houses at once: device tensors obs float32 [N, F], rewards float
         [N] (the last select_actions' actions and probabilities).  ``next_observations`` is accepted
         for the reference's signature but not kept: update never reads it (mappo.py:128-217)."""
+        if self.store is not None and self.store.rows:
+            raise ValueError("store_transition after collect(): one update trains from one of the two buffers")
         self.buffer.append((observations, self.last_actions.clone(), self.last_probs.clone(),
                             rewards.clone(), bool(done)))
         self.counter += observations.shape[0]
 
+    def collect(self, n_ticks: int, done: bool = True):
+        """n_ticks of select_actions -> env.step as ``device_actor.rollout`` runs them (one captured
+        graph for individual_L2), stored as transitions: the state snapshots, actions, probabilities
+        and rewards go to ``self.store``; the last tick is marked done (training_manager.py:224-240
+        marks the epoch's last step).  Returns the ticks' reward rows (a view of the store)."""
+        if self.store is None:
+            raise ValueError("collect() needs DeviceMAPPO(..., collect_ticks=N)")
+        if self.buffer:
+            raise ValueError("collect() after store_transition: one update trains from one of the two buffers")
+        r = self.device_actor.rollout(n_ticks, store=self.store)
+        if done:
+            self.store.done[-1] = True
+        self.counter += n_ticks * self.env.n_local
+        return r
+
     def __len__(self) -> int:
+        if self.store is not None and self.store.rows:
+            return len(self.store)
         return sum(b[0].shape[0] for b in self.buffer)
 
     # ---------------------------------------------------------------- update
@@ -195,33 +223,46 @@ class DeviceMAPPO:
         if L < self.cfg.batch_size:
             return False
         cfg = self.cfg
-        state = torch.cat([b[0] for b in self.buffer]).float()
-        act = torch.cat([b[1] for b in self.buffer]).long().view(-1, 1)
-        old_prob = torch.cat([b[2] for b in self.buffer]).float().view(-1, 1)
-        n = self.buffer[0][0].shape[0]
-        acts = torch.stack([b[1] for b in self.buffer]).double()  # [T, N]
+        st = self.store if self.store is not None and self.store.rows else None
+        if st is not None:
+            # the collected rollout: each minibatch's obs rows are rebuilt from the state snapshots
+            T, n = st.rows, st.n_local
+            state = None
+            act = st.actions[:T].reshape(-1).long().view(-1, 1)
+            old_prob = st.probs[:T].reshape(-1).float().view(-1, 1)
+            acts = st.actions[:T].double()  # [T, N]
+            dev = st.rewards.device
+        else:
+            state = torch.cat([b[0] for b in self.buffer]).float()
+            act = torch.cat([b[1] for b in self.buffer]).long().view(-1, 1)
+            old_prob = torch.cat([b[2] for b in self.buffer]).float().view(-1, 1)
+            n = self.buffer[0][0].shape[0]
+            acts = torch.stack([b[1] for b in self.buffer]).double()  # [T, N]
+            dev = state.device
         n_glob = self.env.n
         tot = acts.sum(1, keepdim=True)
         if self.env.world > 1:
             self.env._comm.allreduce_sum(self.env.shard, tot)
         others = ((tot - acts) / max(n_glob - 1, 1)).float().reshape(-1, 1)  # mean of the other houses' actions
-        reward = torch.stack([b[3] for b in self.buffer])  # [T, N]
-        done = torch.tensor([b[4] for b in self.buffer], dtype=torch.float64, device=reward.device)
+        reward = st.rewards[:T] if st is not None else torch.stack([b[3] for b in self.buffer])  # [T, N]
+        done = torch.tensor(st.done if st is not None else [b[4] for b in self.buffer], dtype=torch.float64,
+                            device=reward.device)
         done_rows = done[:, None].expand(-1, n)
         Gt = self._returns(reward, done_rows, n).float()
-        critic_in = torch.cat([state, others], 1)
+        critic_in = torch.cat([state, others], 1) if st is None else None
         on_device = self.sampler == "device" or (self.sampler == "auto" and L > (1 << 20))
         self.last_sampler = "device" if on_device else "reference"
         for _ in range(cfg.ppo_update_time):
             # SubsetRandomSampler + BatchSampler(drop_last=False): a permutation (the global CPU
             # generator's, or the device generator's — see sampler), cut in order into batch_size chunks
-            perm = torch.randperm(L, device=state.device) if on_device else torch.randperm(L).to(state.device)
+            perm = torch.randperm(L, device=dev) if on_device else torch.randperm(L).to(dev)
             for k in range(0, L, cfg.batch_size):
                 idx = perm[k:k + cfg.batch_size]
                 Gt_index = Gt[idx].view(-1, 1)
-                V = self.critic_net(critic_in[idx])
+                state_idx = state[idx] if st is None else st.states(idx)
+                V = self.critic_net(critic_in[idx] if st is None else torch.cat([state_idx, others[idx]], 1))
                 advantage = (Gt_index - V).detach()
-                action_prob = self.actor_net(state[idx]).gather(1, act[idx])
+                action_prob = self.actor_net(state_idx).gather(1, act[idx])
                 ratio = action_prob / old_prob[idx]
                 clipped_ratio = torch.clamp(ratio, 1 - cfg.clip_param, 1 + cfg.clip_param)
                 action_loss = -torch.min(ratio * advantage, clipped_ratio * advantage).mean()
@@ -236,6 +277,8 @@ class DeviceMAPPO:
                 self.critic_net_optimizer.step()
                 self.training_step += 1
         del self.buffer[:]
+        if st is not None:
+            st.clear()
         self.device_actor.load_weights()  # the fused kernel's packed weights follow the update
         return True
 

@@ -381,6 +381,31 @@ class HipShard:
                                                    L.ptr(reward), rew_stride, L.ptr(self.p_dev), self.stream()),
                 "mdr_actor_rollout_sharded")
 
+    # ------------------------------------------------------------------ replay snapshots
+    def snapshot(self, snap, row: int, scalars, use_p_dev=True):
+        """mdr_snapshot: the current t_air / t_mass / hvac and obs scalars into row ``row`` of
+        ``snap`` (an ``mdr_snap``, see mdr_amd.replay.RolloutStore)."""
+        L.check(self.lib.mdr_snapshot(self.ctx, C.byref(snap), int(row), C.byref(scalars),
+                                      L.ptr(self.p_dev) if use_p_dev else 0, self.stream()), "mdr_snapshot")
+
+    def actor_rollout_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                           snap, row0: int, use_graph=True):
+        """``actor_rollout`` that also records tick t's pre-step state into row ``row0 + t`` of ``snap``
+        (mdr_actor_rollout_snap)."""
+        n = len(ticks)
+        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
+        assert obs_sc.shape == (n, 4)
+        L.check(self.lib.mdr_actor_rollout_snap(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
+                                                L.ptr(action), act_stride, L.ptr(prob), prob_stride, L.ptr(reward),
+                                                rew_stride, L.ptr(self.p_dev), int(use_graph), C.byref(snap),
+                                                int(row0), self.stream()), "mdr_actor_rollout_snap")
+
+    def obs_gather(self, spec, snap, rows: int, idx, out):
+        """out float32 [len(idx), n_feat] <- the obs rows of transitions ``idx`` (device int64:
+        tick * n_local + house) over the first ``rows`` snapshot rows (mdr_obs_gather)."""
+        L.check(self.lib.mdr_obs_gather(self.ctx, C.byref(spec), C.byref(snap), int(rows), L.ptr(idx),
+                                        int(idx.numel()), L.ptr(out), self.stream()), "mdr_obs_gather")
+
     def interp_load(self, grids, values, cfg):
         """Monte-Carlo table + axes to the device (mdr_interp_load, synchronous)."""
         grid = np.ascontiguousarray(np.concatenate([np.asarray(g, np.float64) for g in grids]))
