@@ -565,6 +565,28 @@ int mdr_actor_rollout_snap(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, con
                            const mdr_obs_spec* obs, uint8_t* action, int64_t act_stride, float* prob,
                            int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                            int use_graph, const mdr_snap* snap, int row0, void* stream);
+/* ---- per-tick stats rows: metrics and policy evaluation without a host round trip per tick ---- */
+/* out16 (device doubles) <- one row of the shard's post-step state: [0..11] mdr_cluster_stats' twelve
+ * values in its per-house expressions (Metrics.update, metrics_service.py:108-157; reward may be
+ * NULL: out16[4] = 0), [12] the cluster power after the step (p_dev, when non-NULL, overrides
+ * p_host with the device scalar, as in mdr_snapshot) — the post-step obs' cluster_hvac_power that
+ * TrainingManager.test reads (training_manager.py:279-291) —, [13..15] = 0.  Asynchronous: two kernel
+ * launches, a fixed summation order, no atomics.  Single shard: a communicator or world > 1 gives
+ * MDR_ESTATE.  MDR_EARG: ctx or out16 NULL. */
+int mdr_tick_stats(mdr_ctx* ctx, const double* reward, const double* p_dev, double p_host, double* out16,
+                   void* stream);
+/* mdr_actor_rollout_snap (snap may be NULL) that also writes tick t's row — the state after its
+ * step, its reward row, P — into stats[stats_row0 + t][16] (caller-owned device doubles,
+ * stats_rows rows), by two kernel nodes after tick t's step launch: what TrainingManager.start
+ * feeds Metrics.update every tick (training_manager.py:242-245) and what TrainingManager.test
+ * accumulates (training_manager.py:265-295), read by the host once per call.  stats == NULL is
+ * mdr_actor_rollout_snap: same launches, same graph keys.  MDR_EARG, before anything is launched:
+ * stats_row0 < 0 or stats_row0 + n_ticks > stats_rows.  MDR_ESTATE: a communicator or world > 1. */
+int mdr_actor_rollout_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const mdr_obs_scalars* obs_sc,
+                            const mdr_obs_spec* obs, uint8_t* action, int64_t act_stride, float* prob,
+                            int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                            int use_graph, const mdr_snap* snap, int row0, double* stats, int64_t stats_rows,
+                            int64_t stats_row0, void* stream);
 /* float32 obs[m][n_feat]: row q is the obs row of house idx[q] % n_local at the tick of snapshot
  * row idx[q] / n_local (idx: device int64[m]), over the first `rows` snapshot rows.  An idx outside
  * [0, rows * n_local) is not dereferenced: its row is NaN.  MDR_EARG: rows outside [0, cap_rows],

@@ -188,6 +188,7 @@ struct mdr_ctx {
   uint8_t* d_act = nullptr;    // [n_local] actor actions when the caller keeps none
   float* d_halo = nullptr;     // sharded actor rollout: packed edge rows | received ring halo
   double* d_stats = nullptr;   // k_cluster_stats block partials
+  double* d_tick_part = nullptr;  // k_tick_stats block partials (allocated zeroed, outside any capture)
   size_t halo_bytes = 0;
   std::map<std::vector<int64_t>, hipGraphExec_t> actor_graphs;
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
@@ -635,6 +636,7 @@ int mdr_destroy(mdr_ctx* c) {
   hipFree(c->d_act);
   hipFree(c->d_halo);
   hipFree(c->d_stats);
+  hipFree(c->d_tick_part);
   hipFree(c->d_obs_sc);
   hipFree(c->d_tables);
   hipFree(c->d_flags);
@@ -2716,6 +2718,50 @@ int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars*
   return rc;
 }
 
+// ---- per-tick stats rows (k_tick_stats + k_tick_stats_finish): scratch, checks, the two launches
+// the block partials belong to the context: allocated (zeroed) before any capture that uses them;
+// every launch overwrites the partials it then reads, so no node ever has to clear them
+static int tick_scratch(mdr_ctx* c) {
+  if (c->d_tick_part) return MDR_OK;
+  HIP_TRY(hipMalloc(&c->d_tick_part, sizeof(double) * kStats * kTickBlocks));
+  HIP_TRY(hipMemset(c->d_tick_part, 0, sizeof(double) * kStats * kTickBlocks));
+  return MDR_OK;
+}
+
+static int check_tick_stats_ctx(mdr_ctx* c, const char* who) {
+  if (has_comm(c) || c->world > 1)
+    return fail(MDR_ESTATE, std::string(who) + ": stats rows are single-shard (a row sums this shard's houses only)");
+  return MDR_OK;
+}
+
+static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* row,
+                             hipStream_t st) {
+  const unsigned nb = std::max(1u, std::min(blocks(blocks(c->kp.n, kTickHpt), kTickBlock), (unsigned)kTickBlocks));
+  const KParams& k = c->kp;
+  const bool vs = (((uintptr_t)k.t_air | (uintptr_t)k.t_mass | (uintptr_t)k.target | (uintptr_t)k.hvac) & 15) == 0;
+  const bool vr = reward && ((uintptr_t)reward & 15) == 0;
+#define MDR_LAUNCH_TICK(R, VS, VR) \
+  hipLaunchKernelGGL((k_tick_stats<R, VS, VR>), dim3(nb), dim3(kTickBlock), 0, st, c->kp, reward, c->d_tick_part)
+  if (!reward) { if (vs) MDR_LAUNCH_TICK(false, true, false); else MDR_LAUNCH_TICK(false, false, false); }
+  else if (vs) { if (vr) MDR_LAUNCH_TICK(true, true, true); else MDR_LAUNCH_TICK(true, true, false); }
+  else { if (vr) MDR_LAUNCH_TICK(true, false, true); else MDR_LAUNCH_TICK(true, false, false); }
+#undef MDR_LAUNCH_TICK
+  LAUNCH_CHECK("k_tick_stats");
+  hipLaunchKernelGGL(k_tick_stats_finish, dim3(1), dim3(kTickBlock), 0, st, c->d_tick_part, (int)nb, p_dev, p_host, row);
+  LAUNCH_CHECK("k_tick_stats_finish");
+  return MDR_OK;
+}
+
+int mdr_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* out16,
+                   void* stream) {
+  if (!out16) return fail(MDR_EARG, "mdr_tick_stats: null out16");
+  if (!c) return fail(MDR_EARG, "mdr_tick_stats: null ctx");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_tick_stats: context not bound");
+  if (int rc = check_tick_stats_ctx(c, "mdr_tick_stats")) return rc;
+  if (int rc = tick_scratch(c)) return rc;
+  return launch_tick_stats(c, reward, p_dev, p_host, out16, S(stream));
+}
+
 // ---- replay snapshots (mdr.h mdr_snap): argument checks and the k_snap launch
 static int check_snap_struct(const mdr_snap* sn, const char* who) {
   if (sn->struct_bytes != (int32_t)sizeof(mdr_snap))
@@ -2781,14 +2827,19 @@ int mdr_obs_gather(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, int r
 static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
                               const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
                               int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
-                              const mdr_snap* snap, int row0, void* stream, const char* who) {
+                              const mdr_snap* snap, int row0, double* stats, int64_t stats_rows, int64_t stats_row0,
+                              void* stream, const char* who) {
   drop_begun(c);
   if (snap)
     if (int rc = check_snap_struct(snap, who)) return rc;
+  if (stats && (stats_rows < 0 || stats_row0 < 0 || n < 0 || stats_row0 > stats_rows - n))
+    return fail(MDR_EARG, std::string(who) + ": stats_row0 .. stats_row0 + n_ticks outside [0, stats_rows)");
   if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
   if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
   if (snap)
     if (int rc = check_snap(c, snap, row0, n, who)) return rc;
+  if (stats)
+    if (int rc = check_tick_stats_ctx(c, who)) return rc;
   if (int rc = check_actor_obs(c, sp, who, S(stream))) return rc;
   if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
     return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
@@ -2816,10 +2867,17 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
       if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
                                reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, ls))
         return rc;
+      // the post-step state, this tick's reward row and P into stats row stats_row0 + t
+      if (stats)
+        if (int rc = launch_tick_stats(c, reward + (int64_t)t * rew_stride, p_dev, 0.0,
+                                       stats + (stats_row0 + t) * kTickRow, ls))
+          return rc;
     }
     return MDR_OK;
   };
   if (!action && !c->d_act) HIP_TRY(hipMalloc(&c->d_act, c->kp.n));  // context-owned action row
+  if (stats)
+    if (int rc = tick_scratch(c)) return rc;  // (before any capture)
   if (!use_graph) {
     const int rc = launches(st);
     c->counts_ready = false;
@@ -2833,6 +2891,10 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
     key.insert(key.end(), {(int64_t)(uintptr_t)snap->t_air, (int64_t)(uintptr_t)snap->t_mass,
                            (int64_t)(uintptr_t)snap->hvac, (int64_t)(uintptr_t)snap->scalars, snap->row_stride,
                            (int64_t)row0});
+  if (stats) {  // (20 entries: the snapshot fields, zero without one, then the stats rows)
+    if (!snap) key.insert(key.end(), {0, 0, 0, 0, 0, 0});
+    key.insert(key.end(), {(int64_t)(uintptr_t)stats, stats_row0});
+  }
   auto it = c->actor_graphs.find(key);
   if (it == c->actor_graphs.end()) {
     hipGraphExec_t ex;
@@ -2852,7 +2914,7 @@ int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_sc
                       int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
                       void* stream) {
   return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
-                            use_graph, nullptr, 0, stream, "mdr_actor_rollout");
+                            use_graph, nullptr, 0, nullptr, 0, 0, stream, "mdr_actor_rollout");
 }
 
 int mdr_actor_rollout_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -2860,7 +2922,17 @@ int mdr_actor_rollout_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_o
                            int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
                            const mdr_snap* snap, int row0, void* stream) {
   return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
-                            use_graph, snap, row0, stream, "mdr_actor_rollout_snap");
+                            use_graph, snap, row0, nullptr, 0, 0, stream, "mdr_actor_rollout_snap");
+}
+
+int mdr_actor_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                            const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                            int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
+                            const mdr_snap* snap, int row0, double* stats, int64_t stats_rows, int64_t stats_row0,
+                            void* stream) {
+  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                            use_graph, snap, row0, stats, stats_rows, stats_row0, stream,
+                            stats ? "mdr_actor_rollout_stats" : snap ? "mdr_actor_rollout_snap" : "mdr_actor_rollout");
 }
 
 // Sharded MA-PPO rollout (config C5): per tick

@@ -202,6 +202,15 @@ constexpr int kStats = 12;       // k_cluster_stats outputs (mdr.h mdr_cluster_s
 constexpr int kStatsBlocks = 512;
 __global__ void k_cluster_stats(KParams p, const double* reward, double* partial);
 __global__ void k_cluster_stats_final(const double* partial, int nblk, double* out);
+// per-tick stats rows (mdr_tick_stats / mdr_actor_rollout_stats)
+constexpr int kTickRow = 16;      // doubles per row: k_cluster_stats' 12, the cluster power, 3 zeros
+constexpr int kTickBlock = 256;
+constexpr int kTickHpt = 4;       // houses per lane and trip (two 16-B vectors per double array)
+constexpr int kTickBlocks = 1024; // grid cap (as kStatsBlocks caps k_cluster_stats): 2^20 houses per trip of the grid-stride loop
+// HAS_R: a reward row is given; VS / VR: the state arrays / the reward row are 16-B aligned
+template <bool HAS_R, bool VS, bool VR>
+__global__ void k_tick_stats(KParams p, const double* reward, double* partial);
+__global__ void k_tick_stats_finish(const double* partial, int nblk, const double* p_dev, double p_host, double* row);
 __global__ void k_obs(KParams p, ObsArgs o, const double* p_dev, float* obs);
 __global__ void k_halo_pack(KParams p, ObsArgs o, int lo, int hi, float* out);
 __global__ void k_halo_step_pack(KParams p, ObsArgs o, const uint8_t* action, const TickArgs* tkp, int lo, int hi,

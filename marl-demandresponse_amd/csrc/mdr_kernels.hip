@@ -1949,6 +1949,154 @@ __global__ void __launch_bounds__(64) k_cluster_stats_final(const double* __rest
   out[k] = v;
 }
 
+// ---- per-tick stats rows (mdr_tick_stats / mdr_actor_rollout_stats) --------------------------
+// The same twelve values as k_cluster_stats, per-house expressions unchanged, as one row of
+// kTickRow doubles per tick that a rollout's launch sequence writes and the host reads once per
+// call: Metrics.update without a per-tick round trip (metrics_service.py:108-157) and
+// TrainingManager.test's three means (training_manager.py:265-295).  row[12] = the cluster power
+// after the step, row[13..15] = 0.
+//
+// Order of every sum (fixed, so a row is reproducible and the in-graph rows are the stand-alone
+// call's bits): a lane adds its houses in index order (quads q = gtid, gtid + gthr, ..., then one
+// tail house); the 64 lanes of a wave by an xor butterfly (32, 16, ..., 1); the 4 waves of a block
+// in index order; k_tick_stats_finish: thread j adds block partials j, j + 256, ... in index order,
+// then the same butterfly and wave order.  No atomics; the kernel boundary is the hand-off.
+//
+// Loads: a lane takes kTickHpt = 4 consecutive houses per trip, as 16-B vectors (2 x double2 per
+// double array, one uint4 of hvac words) when the four state arrays are 16-B aligned (VS), and the
+// reward row the same when its base is (VR; row t of a [T, n] buffer with odd n is only 8-B
+// aligned: scalar loads of the same houses, so the sums do not depend on the alignment).  The host
+// picks the instantiation from the pointers it launches with: a run-time choice between the two
+// forms of one address pattern is folded by the compiler into the 8-B loads.
+template <bool HAS_R>
+__device__ __forceinline__ void tick_acc(double (&a)[kStats], double T, double Tm, double tg, uint32_t w, double r,
+                                         double N) {
+  const double e = T - tg / N;
+  const double d = T - tg;
+  a[0] += e;
+  a[1] += fabs(e);
+  a[2] = fmax(a[2], e);
+  a[3] += e * e;
+  if (HAS_R) a[4] += r / N;
+  a[5] += T;
+  a[6] += d;
+  a[7] += fabs(d);
+  a[8] += Tm;
+  a[9] += tg;
+  a[10] += hv_lock(w) ? 1.0 : 0.0;
+  a[11] += hv_on(w) ? 1.0 : 0.0;
+}
+
+// a[] of the block's 256 threads -> the block's values in threads 0 .. kStats-1 (return value)
+__device__ __forceinline__ double tick_block_reduce(double (&a)[kStats], double (*sh)[4]) {
+  // butterfly step outermost: the twelve exchanges of a step are independent and in flight
+  // together (slot-major, the 72 steps form one chain of cross-lane latencies)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    double o[kStats];
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) o[k] = __shfl_xor(a[k], off);
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) a[k] = k == 2 ? fmax(a[k], o[k]) : a[k] + o[k];
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) sh[k][wv] = a[k];
+  __syncthreads();
+  double v = 0.0;
+  if (threadIdx.x < kStats) {
+    const int k = threadIdx.x;
+    v = sh[k][0];
+    for (int w = 1; w < kTickBlock / 64; ++w) v = k == 2 ? fmax(v, sh[k][w]) : v + sh[k][w];
+  }
+  return v;
+}
+
+template <bool HAS_R, bool VS, bool VR>
+__global__ void __launch_bounds__(kTickBlock) k_tick_stats(KParams p, const double* __restrict__ reward,
+                                                           double* __restrict__ partial) {
+  __shared__ double sh[kStats][4];
+  double a[kStats];
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+  const double N = (double)p.n_global;
+  const int64_t gtid = (int64_t)blockIdx.x * kTickBlock + threadIdx.x;
+  const int64_t gthr = (int64_t)gridDim.x * kTickBlock;
+  const int64_t nq = p.n / kTickHpt;
+  for (int64_t q = gtid; q < nq; q += gthr) {
+    const int64_t i = q * kTickHpt;
+    double T[kTickHpt], Tm[kTickHpt], tg[kTickHpt], r[kTickHpt];
+    uint32_t w[kTickHpt];
+    if (VS) {
+#pragma unroll
+      for (int h = 0; h < kTickHpt; h += 2) {
+        const double2 t2 = *reinterpret_cast<const double2*>(p.t_air + i + h);
+        const double2 m2 = *reinterpret_cast<const double2*>(p.t_mass + i + h);
+        const double2 g2 = *reinterpret_cast<const double2*>(p.target + i + h);
+        T[h] = t2.x, T[h + 1] = t2.y;
+        Tm[h] = m2.x, Tm[h + 1] = m2.y;
+        tg[h] = g2.x, tg[h + 1] = g2.y;
+      }
+      const uint4 w4 = *reinterpret_cast<const uint4*>(p.hvac + i);
+      w[0] = w4.x, w[1] = w4.y, w[2] = w4.z, w[3] = w4.w;
+    } else {
+#pragma unroll
+      for (int h = 0; h < kTickHpt; ++h) T[h] = p.t_air[i + h], Tm[h] = p.t_mass[i + h], tg[h] = p.target[i + h], w[h] = p.hvac[i + h];
+    }
+    if (HAS_R) {
+      if (VR) {
+#pragma unroll
+        for (int h = 0; h < kTickHpt; h += 2) {
+          const double2 r2 = *reinterpret_cast<const double2*>(reward + i + h);
+          r[h] = r2.x, r[h + 1] = r2.y;
+        }
+      } else {
+#pragma unroll
+        for (int h = 0; h < kTickHpt; ++h) r[h] = reward[i + h];
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < kTickHpt; ++h) tick_acc<HAS_R>(a, T[h], Tm[h], tg[h], w[h], HAS_R ? r[h] : 0.0, N);
+  }
+  // ragged tail: the last n % 4 houses, one per lane of the first block
+  const int64_t i = nq * kTickHpt + gtid;
+  if (i < p.n) tick_acc<HAS_R>(a, p.t_air[i], p.t_mass[i], p.target[i], p.hvac[i], HAS_R ? reward[i] : 0.0, N);
+  const double v = tick_block_reduce(a, sh);
+  if (threadIdx.x < kStats) partial[(size_t)blockIdx.x * kStats + threadIdx.x] = v;
+}
+
+#define MDR_INST_TICK(R, VS, VR) \
+  template __global__ void k_tick_stats<R, VS, VR>(KParams, const double*, double*);
+MDR_INST_TICK(true, true, true)
+MDR_INST_TICK(true, true, false)
+MDR_INST_TICK(true, false, true)
+MDR_INST_TICK(true, false, false)
+MDR_INST_TICK(false, true, false)
+MDR_INST_TICK(false, false, false)
+#undef MDR_INST_TICK
+
+// partial[nblk][kStats] -> row[kTickRow]: every thread writes at most one slot of the row
+__global__ void __launch_bounds__(kTickBlock) k_tick_stats_finish(const double* __restrict__ partial, int nblk,
+                                                                  const double* __restrict__ p_dev, double p_host,
+                                                                  double* __restrict__ row) {
+  __shared__ double sh[kStats][4];
+  double a[kStats];
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += kTickBlock)
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) {
+      const double o = partial[(size_t)b * kStats + k];
+      a[k] = k == 2 ? fmax(a[k], o) : a[k] + o;
+    }
+  const double v = tick_block_reduce(a, sh);
+  const int k = threadIdx.x;
+  if (k < kStats) row[k] = v;
+  else if (k == kStats) row[k] = p_dev ? *p_dev : p_host;
+  else if (k < kTickRow) row[k] = 0.0;
+}
+
 // --------------------------------------------------------------------------------------- population
 // Synthetic population: the reference noise model (building.py:224-267, hvac.py:66-70) drawn
 // from Philox4x32-10 keyed by (seed, global house id) — identical for any sharding.

@@ -184,6 +184,9 @@ SIGNATURES = {
     "mdr_snapshot": (I, [VP, P(mdr_snap), I, P(mdr_obs_scalars), VP, VP]),
     "mdr_actor_rollout_snap": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64,
                                    VP, I64, VP, I, P(mdr_snap), I, VP]),
+    "mdr_tick_stats": (I, [VP, VP, VP, D, VP, VP]),
+    "mdr_actor_rollout_stats": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64,
+                                    VP, I64, VP, I, P(mdr_snap), I, VP, I64, I64, VP]),
     "mdr_obs_gather": (I, [VP, P(mdr_obs_spec), P(mdr_snap), I, VP, I64, VP, VP]),
     "mdr_actor_profile": (I, [VP, P(mdr_obs_spec), P(mdr_obs_scalars), VP, P(D), VP]),
     "mdr_interp_load": (I, [VP, P(mdr_interp_spec)]),

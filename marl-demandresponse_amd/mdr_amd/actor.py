@@ -130,7 +130,8 @@ class DeviceActor:
         env._counts_ready = ("actor", action.data_ptr()) if count_next else 0
         return action, prob
 
-    def rollout(self, n_ticks: int, rewards=None, actions=None, probs=None, use_graph: bool = True, store=None):
+    def rollout(self, n_ticks: int, rewards=None, actions=None, probs=None, use_graph: bool = True, store=None,
+                stats=None):
         """n_ticks of (select_actions -> env.step) in one graph-captured C call (individual_L2;
         sharded: the library's C loop).  The common penalty modes (common_L2, common_max_error,
         mixture: rewards_calculator.py:29-203) need the cluster's penalty sum / max between the
@@ -142,11 +143,20 @@ class DeviceActor:
         ``store`` (mdr_amd.replay.RolloutStore): the ticks are appended to it as training
         transitions — each tick's pre-step state snapshot is recorded inside the same graph
         (mdr_actor_rollout_snap) and the store's next ``actions`` / ``probs`` / ``rewards`` rows are
-        the outputs (``rewards`` / ``actions`` / ``probs`` must then be None)."""
+        the outputs (``rewards`` / ``actions`` / ``probs`` must then be None).
+
+        ``stats`` (mdr_amd.services.RolloutStats; combinable with ``store``): each tick's cluster
+        statistics of the post-step state, its rewards and the cluster power are appended to it as one
+        row, written by two more kernels after the tick's step inside the same graph
+        (mdr_actor_rollout_stats; the common penalty modes: mdr_tick_stats after each step_tensor)."""
         torch = _torch()
         env = self.env
         sh = env.shard
-        row0 = 0
+        row0 = srow0 = 0
+        if stats is not None:
+            if stats.env is not env:
+                raise ValueError("the stats rows belong to another environment")
+            srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
         if store is not None:
             if store.env is not env:
                 raise ValueError("the store belongs to another environment")
@@ -155,7 +165,7 @@ class DeviceActor:
             row0 = store.begin_rows(n_ticks)  # (ValueError: overflow, a reset since its rows were taken)
             rewards, actions, probs = (x[row0:row0 + n_ticks] for x in (store.rewards, store.actions, store.probs))
         if sh.penalty_mode != 0 or (env.world > 1 and not getattr(env._comm, "native", False)):
-            return self._rollout_stepwise(n_ticks, rewards, actions, probs, store)
+            return self._rollout_stepwise(n_ticks, rewards, actions, probs, store, stats)
         sharded = env.world > 1
         spec, _sc, keep = env.bound_obs_spec() if not sharded else (env.obs_spec(), None, [])
         self._check_obs(spec)
@@ -185,7 +195,15 @@ class DeviceActor:
                                          sl(rewards, rs), rs)
             else:
                 g = use_graph and (k == n_ticks or not (rs or as_ or ps))
-                if store is not None:  # this window's snapshot rows follow the previous windows'
+                if stats is not None:  # (and the store's snapshot rows, when both are given)
+                    if done == 0:
+                        stats.record_power(srow0)
+                    sh.actor_rollout_stats(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
+                                           sl(rewards, rs), rs, store.snap if store is not None else None,
+                                           row0 + done, stats.stats, srow0 + done, g)
+                    if store is not None:
+                        store.commit_rows(k)
+                elif store is not None:  # this window's snapshot rows follow the previous windows'
                     sh.actor_rollout_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
                                           sl(rewards, rs), rs, store.snap, row0 + done, g)
                     store.commit_rows(k)
@@ -193,6 +211,9 @@ class DeviceActor:
                     sh.actor_rollout(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps, sl(rewards, rs), rs, g)
             env._P_dev_valid = True
             env.finish_grid_step()
+            if stats is not None:  # tick t's post-step signal is tick t + 1's s_prev; the last one's is the grid's
+                post = list(ticks.s_prev[1:]) + [env.power_grid.current_signal]
+                stats.commit_rows(ticks.s_prev, ticks.t_od_prev, post, first=(done == 0))
             done += k
         if keep:
             torch.cuda.current_stream(sh.device).synchronize()
@@ -201,12 +222,13 @@ class DeviceActor:
         return rewards
 
 
-    def _rollout_stepwise(self, n_ticks, rewards, actions, probs, store=None):
+    def _rollout_stepwise(self, n_ticks, rewards, actions, probs, store=None, stats=None):
         """Per tick select_actions (sharded: the ring halo, ON counts of the actions) then
         step_tensor (count allreduce, step, and for the common penalty modes the penalty reduce +
         reward finalize) from Python — the same launches and exchanges as the C loop, plus the
         penalty stages the C loops do not have.  ``store``: ``env.snapshot`` appends each tick's
-        pre-step state before its select_actions."""
+        pre-step state before its select_actions; ``stats``: ``Shard.tick_stats`` appends each tick's
+        row after its step_tensor."""
         torch = _torch()
         env = self.env
         sh = env.shard
@@ -220,8 +242,15 @@ class DeviceActor:
             p = p_tmp if probs is None else (probs[t] if probs.dim() == 2 else probs)
             if store is not None:
                 env.snapshot(store)
+            if stats is not None:
+                if t == 0:
+                    stats.record_power(stats.rows)
+                s_prev, od = env.power_grid.current_signal, env.current_od_temp
             self.select_actions(action=a, prob=p, count_next=True)
-            env.step_tensor(a, rewards=rewards[t] if rewards.dim() == 2 else rewards)
+            r = env.step_tensor(a, rewards=rewards[t] if rewards.dim() == 2 else rewards)
+            if stats is not None:
+                sh.tick_stats(r, stats.stats[stats.begin_rows(1)])
+                stats.commit_rows([s_prev], [od], [env.power_grid.current_signal], first=(t == 0))
         return rewards
 
 

@@ -157,6 +157,9 @@ class DeviceMAPPO:
             from .replay import RolloutStore
 
             self.store = RolloutStore(env, collect_ticks)
+        self.stats = None  # collect(metrics=...): the ticks' stats rows (services.RolloutStats)
+        self.collected_ticks = 0
+        self._eval = {}  # evaluate(env=twin): the twin's actor binding, stats rows and outputs
         self.counter = 0
         self.training_step = 0
         self.last_actions = None
@@ -180,20 +183,93 @@ class DeviceMAPPO:
                             rewards.clone(), bool(done)))
         self.counter += observations.shape[0]
 
-    def collect(self, n_ticks: int, done: bool = True):
+    def collect(self, n_ticks: int, done: bool = True, metrics=None, time_step0: Optional[int] = None):
         """n_ticks of select_actions -> env.step as ``device_actor.rollout`` runs them (one captured
         graph for individual_L2), stored as transitions: the state snapshots, actions, probabilities
         and rewards go to ``self.store``; the last tick is marked done (training_manager.py:224-240
-        marks the epoch's last step).  Returns the ticks' reward rows (a view of the store)."""
+        marks the epoch's last step).  Returns the ticks' reward rows (a view of the store).
+
+        ``metrics`` (mdr_amd.services.DeviceMetrics): the ticks also feed it as
+        ``metrics_service.update`` does every step (training_manager.py:242-245) — their stats rows
+        are written inside the same graph (``self.stats``, a RolloutStats of the store's capacity)
+        and accumulated by one ``update_rollout`` as time steps ``time_step0`` .. (default: the
+        ticks collected so far)."""
         if self.store is None:
             raise ValueError("collect() needs DeviceMAPPO(..., collect_ticks=N)")
         if self.buffer:
             raise ValueError("collect() after store_transition: one update trains from one of the two buffers")
-        r = self.device_actor.rollout(n_ticks, store=self.store)
+        stats = None
+        if metrics is not None:
+            if self.stats is None:
+                from .services import RolloutStats
+
+                self.stats = RolloutStats(self.env, self.store.capacity)
+            stats = self.stats
+            stats.clear()
+        r = self.device_actor.rollout(n_ticks, store=self.store, stats=stats)
         if done:
             self.store.done[-1] = True
         self.counter += n_ticks * self.env.n_local
+        if metrics is not None:
+            metrics.update_rollout(stats, self.collected_ticks if time_step0 is None else time_step0)
+        self.collected_ticks += n_ticks
         return r
+
+    # ---------------------------------------------------------------- evaluation
+    def evaluate(self, n_ticks: int, env=None, return_actions: bool = False):
+        """TrainingManager.test (training_manager.py:265-295): the policy run for ``n_ticks`` on a
+        reset copy of the env.  ``env`` None: ``copy.deepcopy(self.env)`` as the reference does; a
+        caller-kept twin may be passed instead, whose context, actor binding and rollout graph are
+        then reused by later calls.  The copy is ``reset`` (which advances the shared RNG, as in the
+        reference), a ``DeviceActor`` over the same ``actor_net`` and precision runs
+        ``rollout(n_ticks, stats=...)`` in the copy's context, and the three means the reference logs
+        (metrics_service.py:259-282) are formed from the post-step rows:
+
+          "Mean test return"             sum_t sum_i reward_i / N / T
+          "Test mean temperature error"  sum_t sum_i |T_i - target_i| / N / T
+          "Test mean signal error"       sum_t N |s_post - P_post| / N^2 / T
+
+        The training env's device state, tick, date, P, graphs and packed weights are not touched.
+        ``return_actions``: also the ticks' actions, uint8 [n_ticks, n_local]."""
+        import copy
+
+        from .services import S_ABS_DIFF, S_POWER, S_REW, RolloutStats
+
+        torch = _torch()
+        if n_ticks < 1:
+            raise ValueError("n_ticks must be at least 1")
+        ev = copy.deepcopy(self.env) if env is None else env
+        if ev is self.env:
+            raise ValueError("evaluate() resets its env: pass a copy, not the training env")
+        ev.reset(return_obs=False)
+        kept = self._eval.get(id(ev)) if env is not None else None
+        if kept is None or kept["env"] is not ev or kept["stats"].capacity < n_ticks:
+            kept = {"env": ev, "actor": DeviceActor(ev, self.actor_net, precision=self.device_actor.precision),
+                    "stats": RolloutStats(ev, n_ticks),
+                    "rewards": torch.empty(ev.n_local, dtype=torch.float64, device=ev.shard.device), "actions": None}
+            if env is not None:
+                self._eval[id(ev)] = kept
+        else:
+            kept["actor"].load_weights()  # (the policy may have been updated since the twin's last run)
+        stats = kept["stats"]
+        stats.clear()
+        acts = None
+        if return_actions:
+            acts = kept["actions"]
+            if acts is None or acts.shape[0] != n_ticks:
+                acts = kept["actions"] = torch.empty((n_ticks, ev.n_local), dtype=torch.uint8, device=ev.shard.device)
+        # (one reward row, overwritten every tick: tick t's stats nodes read it before tick t + 1's step)
+        kept["actor"].rollout(n_ticks, rewards=kept["rewards"], actions=acts, stats=stats)
+        rows, post = stats.host(), stats.prev()["signal_post"]
+        n = ev.n
+        ret = temp = sig = 0.0
+        for t in range(n_ticks):
+            ret += rows[t, S_REW]
+            temp += rows[t, S_ABS_DIFF] / n
+            sig += n * (np.abs(post[t] - rows[t, S_POWER]) / n ** 2)
+        out = {"Mean test return": float(ret / n_ticks), "Test mean temperature error": float(temp / n_ticks),
+               "Test mean signal error": float(sig / n_ticks)}
+        return (out, acts) if return_actions else out
 
     def __len__(self) -> int:
         if self.store is not None and self.store.rows:

@@ -8,6 +8,8 @@ the state (``mdr_cluster_stats``, 12 sums/counts), so a tick costs O(1) host wor
 per-house UI list is materialised only when read.
 
   DeviceMetrics  Metrics               server/app/services/metrics_service.py:71-257
+  RolloutStats   (the obs dicts Metrics.update and TrainingManager.test read, as one device row per
+                 tick written inside a rollout: ``mdr_tick_stats``)  training_manager.py:242-245,265-295
   UISummary      ClientManagerService  server/app/services/client_manager_service.py:12-245
   ServerLoop     ControllerManager     server/app/services/controller_manager.py:93-260
 
@@ -61,6 +63,93 @@ def cluster_stats(env, rewards=None) -> np.ndarray:
     return out.cpu().numpy()
 
 
+# mdr_tick_stats rows: the 12 slots above, the cluster power after the step, three zeros
+S_POWER = 12
+TICK_ROW = 16
+
+
+class RolloutStats:
+    """Fixed-capacity device storage of one ``mdr_tick_stats`` row per tick of ``env``, written
+    inside a rollout's launch sequence (``DeviceActor.rollout(stats=...)``) and read by the host once
+    per call (``host()``): what ``Metrics.update`` (metrics_service.py:108-157) and
+    ``TrainingManager.test`` (training_manager.py:265-295) take from the per-house obs dicts.  The
+    tensor never moves, so rollout graphs captured with its pointer are replayed.
+
+    Per stored tick the host keeps the scalars that tick's obs carried and the driver window
+    already knows — the pre-step ``reg_signal`` and ``OD_temp`` — and the post-step signal.  The
+    pre-step cluster power of a call's first tick is copied on the device, without a
+    synchronisation, from the env's ``P`` scalar; every later tick's is the previous row's slot 12.
+    One shard only (a row sums the shard's own houses)."""
+
+    def __init__(self, env, capacity_ticks: int):
+        import torch
+
+        if capacity_ticks < 1:
+            raise ValueError("capacity_ticks must be at least 1")
+        if env.world > 1:
+            raise ValueError("RolloutStats: sharded environments are not supported (a row sums this "
+                             "shard's houses only)")
+        self.env = env
+        cap = self.capacity = int(capacity_ticks)
+        # one allocation, one download: [cap, 16] rows, then the cap pre-step powers
+        self._buf = torch.zeros(cap * (TICK_ROW + 1), dtype=torch.float64, device=env.shard.device)
+        self.stats = self._buf[:cap * TICK_ROW].view(cap, TICK_ROW)
+        self._p_first = self._buf[cap * TICK_ROW:]
+        self.clear()
+
+    def clear(self) -> None:
+        self.rows = 0
+        self.reg_signal, self.od_temp, self.signal_post, self._first = [], [], [], []
+        self._host = None
+
+    def begin_rows(self, k: int) -> int:
+        """The first of the next ``k`` rows, after checking that they fit; nothing is appended until
+        ``commit_rows``."""
+        if self.rows + k > self.capacity:
+            raise ValueError(f"RolloutStats: {self.rows} + {k} ticks overflow the capacity of {self.capacity}")
+        return self.rows
+
+    def record_power(self, row: int) -> None:
+        """The cluster power before tick ``row`` (the first of a call) from the env's device scalar:
+        an asynchronous device copy on the current stream, outside any graph."""
+        env = self.env
+        if env._P_dev_valid:
+            self._p_first[row:row + 1].copy_(env.shard.p_dev, non_blocking=True)
+        else:
+            self._p_first[row:row + 1].fill_(float(env._P_host))
+
+    def commit_rows(self, reg_signal, od_temp, signal_post, first: bool) -> None:
+        """Append the host scalars of the ``len(reg_signal)`` ticks whose rows were just launched;
+        ``first``: the first of them starts a call (its pre-step power is ``record_power``'s)."""
+        k = len(reg_signal)
+        self.reg_signal.extend(float(x) for x in reg_signal)
+        self.od_temp.extend(float(x) for x in od_temp)
+        self.signal_post.extend(float(x) for x in signal_post)
+        self._first.extend([bool(first)] + [False] * (k - 1))
+        self.rows += k
+        self._host = None
+
+    def host(self) -> np.ndarray:
+        """The filled rows as float64 [rows, 16] on the host (one download, one synchronisation)."""
+        if self._host is None:
+            h = self._buf.cpu().numpy()
+            cap = self.capacity
+            rows = h[:cap * TICK_ROW].reshape(cap, TICK_ROW)[:self.rows].copy()
+            p_prev = np.empty(self.rows, np.float64)
+            p_prev[1:] = rows[:-1, S_POWER]
+            first = np.asarray(self._first, bool)
+            p_prev[first] = h[cap * TICK_ROW:][:self.rows][first]
+            self._host = (rows, p_prev)
+        return self._host[0]
+
+    def prev(self) -> dict:
+        """Per stored tick, float64 [rows] each: the pre-step obs scalars ``reg_signal``, ``OD_temp``
+        and ``cluster_hvac_power`` (``observe(env)`` before the step) and the post-step ``signal_post``."""
+        self.host()
+        return {"reg_signal": np.asarray(self.reg_signal, np.float64), "OD_temp": np.asarray(self.od_temp, np.float64),
+                "cluster_hvac_power": self._host[1], "signal_post": np.asarray(self.signal_post, np.float64)}
+
+
 class DeviceMetrics:
     """``Metrics`` (metrics_service.py:71-257) fed by device reductions instead of a per-house loop."""
 
@@ -87,8 +176,24 @@ class DeviceMetrics:
         """Metrics.update(obs_dict, next_obs_dict, rewards_dict, time_step): ``prev`` holds the
         pre-step obs scalars {"reg_signal", "OD_temp", "cluster_hvac_power"} (observe(env) before
         the step); ``env`` is the post-step environment and ``rewards`` its device reward tensor."""
-        n = self.nb_agents
         st = cluster_stats(env, rewards)
+        self._accumulate(st, prev["reg_signal"], prev["OD_temp"], prev["cluster_hvac_power"],
+                         env.cluster.current_power_consumption, time_step)
+
+    def update_rollout(self, stats: "RolloutStats", time_step0: int, row0: int = 0) -> None:
+        """``update`` for the stored ticks ``row0 ..`` of ``stats`` (time steps ``time_step0``,
+        ``time_step0 + 1``, ...): the same arithmetic in the same order, from the rows a rollout wrote
+        on the device — one synchronisation and one host pass per call instead of one per tick."""
+        rows, prev = stats.host(), stats.prev()
+        for r in range(row0, stats.rows):
+            st = rows[r]
+            self._accumulate(st, float(prev["reg_signal"][r]), float(prev["OD_temp"][r]),
+                             float(prev["cluster_hvac_power"][r]), float(st[S_POWER]), time_step0 + r - row0)
+
+    def _accumulate(self, st, reg_signal, od_temp, cons_prev, cons_post, time_step: int) -> None:
+        """One tick of Metrics.update (metrics_service.py:131-157) from its cluster statistics."""
+        n = self.nb_agents
+        prev = {"reg_signal": reg_signal, "OD_temp": od_temp, "cluster_hvac_power": cons_prev}
         self.cumul_temp_offset += st[S_TERR]
         self.cumul_temp_error += st[S_ABS_TERR]
         self.max_temp_error = max(self.max_temp_error, float(st[S_MAX_TERR]))
@@ -96,7 +201,7 @@ class DeviceMetrics:
         if time_step >= self.start_stats_from:
             self.cumul_squared_error_temp += st[S_SQ_TERR]
         # the same per-house signal error for every house (metrics_service.py:140-145)
-        signal_error = (prev["reg_signal"] - env.cluster.current_power_consumption) / (n ** 2)
+        signal_error = (prev["reg_signal"] - cons_post) / (n ** 2)
         self.cumul_signal_offset += n * signal_error
         self.cumul_signal_error += n * np.abs(signal_error)
         self.cumul_OD_temp += prev["OD_temp"]

@@ -400,6 +400,29 @@ class HipShard:
                                                 rew_stride, L.ptr(self.p_dev), int(use_graph), C.byref(snap),
                                                 int(row0), self.stream()), "mdr_actor_rollout_snap")
 
+    # ------------------------------------------------------------------ per-tick stats rows
+    def tick_stats(self, reward, out, use_p_dev=True, p_host: float = 0.0):
+        """out (device float64 [16]) <- mdr_tick_stats of the current (post-step) state: the 12
+        mdr_cluster_stats values (+ reward or None), the cluster power (the device scalar, or
+        ``p_host``), three zeros.  Asynchronous."""
+        L.check(self.lib.mdr_tick_stats(self.ctx, L.ptr(reward), L.ptr(self.p_dev) if use_p_dev else 0,
+                                        float(p_host), L.ptr(out), self.stream()), "mdr_tick_stats")
+
+    def actor_rollout_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                            snap, row0: int, stats, stats_row0: int, use_graph=True):
+        """``actor_rollout_snap`` (``snap`` may be None) that also writes tick t's stats row into
+        ``stats[stats_row0 + t]`` (device float64 [rows, 16]) inside the same launch sequence
+        (mdr_actor_rollout_stats)."""
+        n = len(ticks)
+        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
+        assert obs_sc.shape == (n, 4)
+        L.check(self.lib.mdr_actor_rollout_stats(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
+                                                 L.ptr(action), act_stride, L.ptr(prob), prob_stride, L.ptr(reward),
+                                                 rew_stride, L.ptr(self.p_dev), int(use_graph),
+                                                 C.byref(snap) if snap is not None else None, int(row0),
+                                                 L.ptr(stats), int(stats.shape[0]), int(stats_row0), self.stream()),
+                "mdr_actor_rollout_stats")
+
     def obs_gather(self, spec, snap, rows: int, idx, out):
         """out float32 [len(idx), n_feat] <- the obs rows of transitions ``idx`` (device int64:
         tick * n_local + house) over the first ``rows`` snapshot rows (mdr_obs_gather)."""
