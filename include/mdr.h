@@ -496,6 +496,23 @@ typedef struct mdr_actor_net {
 } mdr_actor_net;
 int mdr_actor_load_net(mdr_ctx* ctx, const mdr_actor_net* net, const float* const* w, const float* const* b,
                        void* stream);
+/* The head after the actor's output layer, for every later actor call of the context (mdr_actor_act,
+ * mdr_actor_rollout[_snap|_stats], mdr_actor_rollout_sharded, mdr_actor_profile; fused kernel and
+ * layer chain alike).  MDR_HEAD_SOFTMAX (the default after mdr_create): softmax + Categorical sampling,
+ * MAPPO.select_actions.  MDR_HEAD_Q: the net is the reference's DQN_network (network.py:84-103, the
+ * same MLP without the softmax), its two outputs are the Q-values, and the action is DQN.select_actions'
+ * epsilon-greedy choice (server/app/core/agents/trainables/dqn.py:93-105): with probability epsilon a
+ * uniformly random action, otherwise torch.argmax's (a tie gives 0; a NaN counts as the maximum, the
+ * first one wins).  epsilon = 0 is the DQNController (server/app/core/agents/controllers/
+ * rl_controllers.py:143-159).  The draws are the house's Philox word of the tick, the one the softmax
+ * head samples from: explore iff its 24-bit uniform (word >> 8) < epsilon, random action = bit 0 of the
+ * word.  Outputs under MDR_HEAD_Q: action = the chosen action, prob = its Q-value, probs = (Q0, Q1).
+ * epsilon is written to a context-owned device float on `stream` and loaded by every actor launch:
+ * captured rollout graphs follow later values, and a call that changes only epsilon keeps them.  The
+ * head is part of the rollout graph keys, so a graph captured under one head is never replayed under
+ * the other.  MDR_EARG, before any HIP call: ctx NULL, an unknown head, epsilon outside [0, 1] or NaN. */
+enum { MDR_HEAD_SOFTMAX = 0, MDR_HEAD_Q = 1 };
+int mdr_actor_set_head(mdr_ctx* ctx, int head, float epsilon, void* stream);
 /* Synchronises; counts since the last call (zeroed by it).  out[0] = 32-house tiles of the fused
  * fp16-split form (MDR_PREC_FP32, MDR_FP32_F16_SPLIT) that wrote a non-finite logit (nothing else is
  * counted there), out[1] = the fused kernel's arithmetic (1 bf16, 3 bf16x3, 4 the fp16 split, 6 the

@@ -70,10 +70,13 @@ struct ActorDims {
   int lds_total;
 };
 
+// the output layer's head (mdr.h MDR_HEAD_*; actor_head in mdr_actor.hip)
+constexpr int kHeadSoftmax = 0, kHeadQ = 1;
+
 struct ActorOut {
-  uint8_t* action;               // [n] sampled action (u8), or null
-  float* prob;                   // [n] probability of the sampled action, or null
-  float* probs;                  // [n][n_act] all action probabilities, or null
+  uint8_t* action;               // [n] chosen action (u8), or null
+  float* prob;                   // [n] probability (Q head: Q-value) of the chosen action, or null
+  float* probs;                  // [n][n_act] all action probabilities (Q head: the Q-values), or null
   float* obs;                    // [n][n_in] the observation rows, or null
   unsigned long long* count_next;  // count slab of the tick these actions drive, or null
   unsigned long long* prof;        // diagnostics: [grid][8] per-phase shader cycles, or null
@@ -83,6 +86,9 @@ struct ActorOut {
                                    // launches of 64 tiles per wave
   unsigned* ovf;                   // fp16-split form: [0] tiles that met a non-finite logit, [1] tiles whose
                                    // logits came from the scalar fp32 fallback (actor_tile_fp32), or null
+  int head;                        // kHeadSoftmax (0, what an initialiser list that stops earlier gives) or
+                                   // kHeadQ; launch_actor / launch_actor_chain set it from the context
+  const float* eps;                // kHeadQ: the device float holding epsilon (read by the launch)
 };
 
 __global__ void k_actor_pack(ActorDims d, ActorFold fo, const float* w1, const float* b1, const float* w2,
@@ -97,5 +103,6 @@ __global__ void k_dense(const float* X, int ldx, int K, int64_t n, const float* 
                         int ldy, int relu_on);
 __global__ void k_actor_head(KParams p, const float* X, int ldx, int K, const float* W3, const float* b3,
                              uint64_t tick0, const TickArgs* tkp, ActorOut out);
+__global__ void k_actor_eps(float* dst, float eps);
 
 }  // namespace mdr

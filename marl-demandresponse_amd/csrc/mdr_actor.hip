@@ -227,11 +227,44 @@ __device__ __forceinline__ T lds_frag(const unsigned char* base, int frag, int l
   return reinterpret_cast<const T*>(base)[frag * 64 + lane];
 }
 
-__device__ __forceinline__ float philox_u01f(uint64_t seed, uint64_t gid, uint64_t tick) {
+// word x of house gid's Philox block of a tick: its top 24 bits are the house's uniform (word_u01f),
+// bit 0 the Q head's random action (the uniform discards it)
+__device__ __forceinline__ uint32_t philox_word(uint64_t seed, uint64_t gid, uint64_t tick) {
   const u32x4 c = philox4x32_10(u32x4{(uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)tick,
                                       (uint32_t)(tick >> 32) ^ 0xAC7u},
                                 (uint32_t)seed ^ 0x3C6EF372u, (uint32_t)(seed >> 32));
-  return (float)(c.x >> 8) * (1.0f / 16777216.0f);  // [0, 1), 24 bits
+  return c.x;
+}
+__device__ __forceinline__ float word_u01f(uint32_t x) {
+  return (float)(x >> 8) * (1.0f / 16777216.0f);  // [0, 1), 24 bits
+}
+
+// The head of the output layer (ActorOut.head) on one house's two output values and Philox word.
+//   MDR_HEAD_SOFTMAX: softmax over the 2 actions (fp32, max-subtracted like torch; one reciprocal of
+//     the sum, as ATen's vectorised softmax) + Categorical(probs).sample(): action 0 iff u < p0.
+//   MDR_HEAD_Q: z are the Q-values (DQN_network, network.py:84-103: no softmax); epsilon-greedy
+//     (dqn.py:93-105): explore iff u < eps with the random action bit 0 of the word, otherwise
+//     torch.argmax's action (a tie gives 0, a NaN counts as the maximum, the first one wins).
+// eps: the Q head's epsilon in [0, 1], or a negative value for the softmax head (actor_eps: one
+// launch-uniform value carries both).
+// p0, p1: what ActorOut.probs holds (probabilities / Q-values); returns the action.
+__device__ __forceinline__ float actor_eps(const ActorOut& out) {
+  return out.head == kHeadQ ? *out.eps : -1.f;
+}
+__device__ __forceinline__ int actor_head(float eps, float z0, float z1, uint32_t xw, float& p0, float& p1) {
+  const float u = word_u01f(xw);
+  if (eps >= 0.f) {  // the Q head (wave-uniform)
+    p0 = z0;
+    p1 = z1;
+    const int greedy = (z1 > z0 || (z1 != z1 && z0 == z0)) ? 1 : 0;
+    return u < eps ? (int)(xw & 1u) : greedy;
+  }
+  const float zmax = fmaxf(z0, z1);
+  const float e0 = __expf(z0 - zmax), e1 = __expf(z1 - zmax);
+  const float rse = 1.f / (e0 + e1);
+  p0 = e0 * rse;
+  p1 = e1 * rse;
+  return u < p0 ? 0 : 1;
 }
 
 // LDS written by some lanes of a wave and read by others: the wave's LDS operations execute in
@@ -754,8 +787,9 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
     __builtin_amdgcn_s_setprio(0);
     PSTAMP(4);
   };
-  // Y: output layer (fp32 VALU) + softmax + sampling + stores (+ the ON counts of the new actions)
-  float u_next = 0.f;  // the sampling uniforms of this wave's next tile (stage_y, odd tiles)
+  // Y: output layer (fp32 VALU) + the head (softmax + sampling, or Q + epsilon-greedy: actor_head) +
+  // stores (+ the ON counts of the new actions)
+  uint32_t x_next = 0u;  // the Philox words of this wave's next tile (stage_y, odd tiles)
   // skip: the tile's outputs come later (a tile_exact tile in the main loop; its uniforms for the next
   // tile are still drawn)
   // exact: the logits are zx (the fallback pass), lanes < 32 (house = lane)
@@ -778,26 +812,24 @@ __global__ void __launch_bounds__(64 * actor_max_waves(PREC, DEF)) k_actor(KPara
     const bool upper = (lane & 16) != 0;
     const float z0 = (PREC == 4 && exact ? zx.x : upper ? z[1][0] : z[0][0]) + b3[0];
     const float z1 = (PREC == 4 && exact ? zx.y : upper ? z[1][1] : z[0][1]) + b3[1];
-    // softmax over the 2 actions (fp32, max-subtracted like torch; one reciprocal of the sum, as
-    // ATen's vectorised softmax) + Categorical sample
-    const float zmax = fmaxf(z0, z1);
-    const float e0 = __expf(z0 - zmax), e1 = __expf(z1 - zmax);
-    const float rse = 1.f / (e0 + e1);
-    const float p0 = e0 * rse, p1 = e1 * rse;
     const bool valid = r < nb;
     const uint32_t i = b0 + (uint32_t)r;
-    // Categorical(probs).sample(): action 0 iff u < p0.  The uniform of house i is
-    // philox(seed, goff + i, tick); every other tile, lanes 32..63 draw the next tile's (the same
-    // counters: one Philox pass per two tiles), kept in u_next
-    float u;
+    // The Philox word of house i is philox(seed, goff + i, tick); every other tile, lanes 32..63
+    // draw the next tile's (the same counters: one Philox pass per two tiles), kept in x_next (the
+    // whole word: the Q head's random action is its bit 0, below the uniform's 24 bits)
+    uint32_t xw;
     if (fresh) {
       const uint32_t ih = (lane < 32 ? b0 : next * 32u) + (uint32_t)r;
-      u = philox_u01f(p.seed, (uint64_t)p.goff + ih, tick);
-      u_next = __shfl(u, r + 32);
+      xw = philox_word(p.seed, (uint64_t)p.goff + ih, tick);
+      x_next = (uint32_t)__shfl((int)xw, r + 32);
     } else {
-      u = u_next;
+      xw = x_next;
     }
-    const int act = u < p0 ? 0 : 1;
+    // (the Q head's epsilon comes from device memory, so a captured rollout graph follows
+    // mdr_actor_set_head's later values; one scalar load per tile rather than a value kept live across
+    // the tile loop, which cost several instantiations a stack slot: DESIGN.md §3.4.3)
+    float p0, p1;
+    const int act = actor_head(actor_eps(out), z0, z1, xw, p0, p1);
     const float pa = act ? p1 : p0;
     const bool writer = valid && lane < 32 && !skip;
     if (PREC == 4 && out.ovf) {  // a non-finite logit (mdr_actor_status)
@@ -932,9 +964,10 @@ __global__ void __launch_bounds__(256) k_dense(const float* __restrict__ X, int 
   }
 }
 
-// The output layer (fp32 FMAs over the last hidden layer, W3 [2][K] row-major, b3 [2]), softmax and
-// Categorical sampling of k_actor's stage Y — the same uniform philox(seed, goff + i, tick) per
-// house — the stores, and the ON counts of the new actions; one thread per house.
+// The output layer (fp32 FMAs over the last hidden layer, W3 [2][K] row-major, b3 [2]), the head of
+// k_actor's stage Y (actor_head: softmax + Categorical sampling, or Q-values + epsilon-greedy) — the
+// same Philox word philox(seed, goff + i, tick) per house — the stores, and the ON counts of the new
+// actions; one thread per house.
 __global__ void __launch_bounds__(256) k_actor_head(KParams p, const float* __restrict__ X, int ldx, int K,
                                                     const float* __restrict__ W3, const float* __restrict__ b3,
                                                     uint64_t tick0, const TickArgs* tkp, ActorOut out) {
@@ -955,12 +988,10 @@ __global__ void __launch_bounds__(256) k_actor_head(KParams p, const float* __re
   }
   z0 += b3[0];
   z1 += b3[1];
-  const float zmax = fmaxf(z0, z1);
-  const float e0 = __expf(z0 - zmax), e1 = __expf(z1 - zmax);
-  const float rse = 1.f / (e0 + e1);
-  const float p0 = e0 * rse, p1 = e1 * rse;
-  const float u = philox_u01f(p.seed, (uint64_t)p.goff + (uint64_t)(valid ? i : 0), tick);
-  const int act = u < p0 ? 0 : 1;
+  const float eps = actor_eps(out);
+  const uint32_t xw = philox_word(p.seed, (uint64_t)p.goff + (uint64_t)(valid ? i : 0), tick);
+  float p0, p1;
+  const int act = actor_head(eps, z0, z1, xw, p0, p1);
   if (valid) {
     if (out.probs) *reinterpret_cast<float2*>(out.probs + 2 * (size_t)i) = make_float2(p0, p1);
     if (out.action) out.action[i] = (uint8_t)act;
@@ -978,6 +1009,11 @@ __global__ void __launch_bounds__(256) k_actor_head(KParams p, const float* __re
       atomicAdd(&out.count_next[(blockIdx.x % kCountShards) * p.n_cap + threadIdx.x],
                 (unsigned long long)s_hist[threadIdx.x]);
   }
+}
+
+// mdr_actor_set_head: the Q head's epsilon into the context's device float, in stream order
+__global__ void k_actor_eps(float* dst, float eps) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = eps;
 }
 
 template __global__ void k_dense<1>(const float*, int, int, int64_t, const float*, const float*, int, float*, int, int);

@@ -181,6 +181,8 @@ struct mdr_ctx {
   mdr_actor_spec actor{};                // (the two-hidden-layer view the fused kernel packs from)
   mdr_actor_net net{};                   // the loaded actor: layers, widths, precision
   bool actor_ready = false;
+  int actor_head = MDR_HEAD_SOFTMAX;     // mdr_actor_set_head: the output layer's head (in the actor graph keys)
+  float* d_eps = nullptr;                // ... and the Q head's epsilon, read by every launch (never in a key)
   float* d_chain = nullptr;              // the chain's rows: obs [n][F] | hidden ping-pong 2 x [n][wmax4]
   size_t chain_cap = 0;
   int n_cu = 0;
@@ -561,6 +563,8 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
   if (hipMalloc(&c->d_tickets, kTicketWords * sizeof(unsigned)) != hipSuccess ||
       hipMemset(c->d_tickets, 0, kTicketWords * sizeof(unsigned)) != hipSuccess)
     return cleanup(fail(MDR_ENOMEM, "tickets"));
+  if (hipMalloc(&c->d_eps, sizeof(float)) != hipSuccess || hipMemset(c->d_eps, 0, sizeof(float)) != hipSuccess)
+    return cleanup(fail(MDR_ENOMEM, "epsilon"));
   k.params_bad = c->d_flags;
   {
     // the fast division is provably exact for dt < 2^20 s and |q_on| < 2^40 W (mdr_device.h)
@@ -640,6 +644,7 @@ int mdr_destroy(mdr_ctx* c) {
   hipFree(c->d_obs_sc);
   hipFree(c->d_tables);
   hipFree(c->d_flags);
+  hipFree(c->d_eps);
   hipFree(c->d_slab);
   hipFree(c->d_wslab);
   hipFree(c->d_onb);
@@ -2471,8 +2476,11 @@ int actor_ensure_packed(mdr_ctx* c, const mdr_obs_spec* sp, hipStream_t st) {
 // The general actor as a chain of launches (mdr_actor.hip "chain"): obs rows (into out.obs when the
 // caller keeps them), one k_dense per hidden layer (ping-pong row buffers), k_actor_head.
 int launch_actor_chain(mdr_ctx* c, const mdr_obs_spec* sp, const ObsArgs& o, const double* p_dev, uint64_t tick,
-                       const TickArgs* tkp, const ActorOut& out, hipStream_t st) {
-  if (out.prof) return fail(MDR_EARG, "mdr_actor_profile: the chained actor has no phase profile");
+                       const TickArgs* tkp, const ActorOut& out_in, hipStream_t st) {
+  if (out_in.prof) return fail(MDR_EARG, "mdr_actor_profile: the chained actor has no phase profile");
+  ActorOut out = out_in;
+  out.head = c->actor_head;  // (mdr_actor_set_head)
+  out.eps = c->d_eps;
   const mdr_actor_net& a = c->net;
   const int64_t n = c->kp.n;
   const int F = sp->n_feat;
@@ -2515,6 +2523,8 @@ int launch_actor(mdr_ctx* c, const mdr_obs_spec* sp, const ObsArgs& o, const dou
   if (!actor_fused_ok(c, sp)) return launch_actor_chain(c, sp, o, p_dev, tick, tkp, out_in, st);
   ActorOut out = out_in;
   out.ovf = reinterpret_cast<unsigned*>(c->d_flags) + 1;  // (mdr_actor_status; read by the fp16 form only)
+  out.head = c->actor_head;  // (mdr_actor_set_head)
+  out.eps = c->d_eps;
   ActorDims d;
   int nw = 0;
   if (int rc = actor_plan(c, sp, &d, &nw)) return rc;
@@ -2648,6 +2658,16 @@ int mdr_actor_load(mdr_ctx* c, const mdr_actor_spec* a, const float* w1, const f
   const float* w[3] = {w1, w2, w3};
   const float* b[3] = {b1, b2, b3};
   return mdr_actor_load_net(c, &net, w, b, stream);
+}
+
+int mdr_actor_set_head(mdr_ctx* c, int head, float epsilon, void* stream) {
+  if (!c) return fail(MDR_EARG, "mdr_actor_set_head: null context");
+  if (head != MDR_HEAD_SOFTMAX && head != MDR_HEAD_Q) return fail(MDR_EARG, "mdr_actor_set_head: unknown head");
+  if (!(epsilon >= 0.f && epsilon <= 1.f)) return fail(MDR_EARG, "mdr_actor_set_head: epsilon outside [0, 1]");
+  hipLaunchKernelGGL(k_actor_eps, dim3(1), dim3(64), 0, S(stream), c->d_eps, epsilon);
+  LAUNCH_CHECK("k_actor_eps");
+  c->actor_head = head;
+  return MDR_OK;
 }
 
 int mdr_actor_status(mdr_ctx* c, int64_t* out, int n, void* stream) {
@@ -2886,7 +2906,10 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
   std::vector<int64_t> key{n, (int64_t)(uintptr_t)action, act_stride, (int64_t)(uintptr_t)prob, prob_stride,
                            (int64_t)(uintptr_t)reward, rew_stride, (int64_t)(uintptr_t)p_dev,
                            (int64_t)(uintptr_t)sp->comm_table,
-                           (int64_t)(uintptr_t)sp->halo_msg, sp->n_feat, (int64_t)(uintptr_t)c->d_actor};
+                           (int64_t)(uintptr_t)sp->halo_msg, sp->n_feat | ((int64_t)c->actor_head << 32),
+                           (int64_t)(uintptr_t)c->d_actor};
+  // (the head, mdr_actor_set_head, is baked into the captured launches, so it is part of the key above
+  // n_feat — MDR_HEAD_SOFTMAX = 0 leaves the softmax keys as they were; epsilon is not: the kernels load it)
   if (snap)  // (longer keys: never equal to a rollout's without snapshots)
     key.insert(key.end(), {(int64_t)(uintptr_t)snap->t_air, (int64_t)(uintptr_t)snap->t_mass,
                            (int64_t)(uintptr_t)snap->hvac, (int64_t)(uintptr_t)snap->scalars, snap->row_stride,

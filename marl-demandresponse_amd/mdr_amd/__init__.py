@@ -7,7 +7,12 @@ constructing an ``Environment`` loads the library and fails loudly if it (or a G
 from . import config
 from .config import EnvironmentProperties
 
-__all__ = ["Environment", "EnvironmentProperties", "config", "load_library"]
+__all__ = ["Environment", "EnvironmentProperties", "config", "load_library", "DeviceDQN", "DQNConfig",
+           "ReplayStore", "make_qnet"]
+
+# names imported on first use (their modules pull in torch): name -> module
+_LAZY = {"Environment": "environment", "DeviceDQN": "dqn", "DQNConfig": "dqn", "ReplayStore": "replay",
+         "make_qnet": "actor"}
 
 
 def load_library():
@@ -17,8 +22,8 @@ def load_library():
 
 
 def __getattr__(name):
-    if name == "Environment":
-        from .environment import Environment
+    if name in _LAZY:
+        import importlib
 
-        return Environment
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
     raise AttributeError(name)

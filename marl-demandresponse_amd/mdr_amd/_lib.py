@@ -27,6 +27,7 @@ OPTIONS = {"step_tpw": 1, "fastdiv": 2, "window_pipeline": 3, "sharded_overlap":
            "gq_band": 13, "actor_fp32_form": 14, "gq_fused": 15, "gq_adaptive": 16, "actor_grid": 17}
 THERMAL_EXACT, THERMAL_AFFINE = 0, 1
 FP32_F16_SPLIT, FP32_BF16_SPLIT3 = 0, 1  # MDR_OPT_ACTOR_FP32_FORM
+HEADS = {"softmax": 0, "q": 1}  # MDR_HEAD_* (mdr_actor_set_head)
 
 
 class MdrLibraryError(RuntimeError):
@@ -132,6 +133,7 @@ SIGNATURES = {
     "mdr_graph_info": (I, [VP, P(I64), I]),
     "mdr_graph_memset_probe": (I, [VP, P(I64), I, VP]),
     "mdr_actor_status": (I, [VP, P(I64), I, VP]),
+    "mdr_actor_set_head": (I, [VP, I, C.c_float, VP]),
     "mdr_greedy_fused_diag": (I, [VP, P(U64)]),
     "mdr_greedy_fused_stamps": (I, [VP, I, P(U64)]),
     "mdr_create": (I, [P(VP), P(mdr_config)]),

@@ -56,19 +56,60 @@ def make_actor(num_state: int, num_action: int = 2, layers=(100, 100), seed: Opt
     return Actor()
 
 
-class DeviceActor:
-    """``MAPPO.select_actions`` for every house of an Environment shard in one launch."""
+def make_qnet(num_state: int, num_action: int = 2, layers=(100, 100), seed: Optional[int] = 1):
+    """The reference DQN_network (network.py:84-103) as a torch module: the Actor's MLP without the
+    softmax, its outputs the Q-values; parameter names ``fc.N``, so a reference ``DQN.pth`` loads
+    unchanged.  ``seed`` reproduces ``torch.manual_seed(seed)`` before construction (dqn.py:54-75)."""
+    torch = _torch()
+    nn = torch.nn
 
-    def __init__(self, env, actor, precision: str = "bf16x3", fp32_form: str = "f16_split"):
+    class QNet(nn.Module):
+        def __init__(self):
+            super().__init__()
+            ls = json.loads(layers) if isinstance(layers, str) else list(layers)
+            self.layers = [int(x) for x in ls]
+            self.fc = nn.ModuleList([nn.Linear(num_state, self.layers[0])])
+            self.fc.extend([nn.Linear(self.layers[i], self.layers[i + 1]) for i in range(len(self.layers) - 1)])
+            self.fc.append(nn.Linear(self.layers[-1], num_action))
+
+        def forward(self, x):
+            for i in range(len(self.layers)):
+                x = torch.nn.functional.relu(self.fc[i](x))
+            return self.fc[len(self.layers)](x)
+
+    if seed is not None:
+        torch.manual_seed(seed)
+    return QNet()
+
+
+class DeviceActor:
+    """``MAPPO.select_actions`` (head "softmax") or ``DQN.select_actions`` (head "q") for every house
+    of an Environment shard in one launch."""
+
+    def __init__(self, env, actor, precision: str = "bf16x3", fp32_form: str = "f16_split", head: str = "softmax",
+                 epsilon: float = 0.0):
         """precision: "fp32" (the reference Actor's), "bf16x3" or "bf16".  fp32_form: the fused kernel's
         fp32 arithmetic — "f16_split" (fp16 hi/lo operands, 3 MFMAs per term, per-layer power-of-two
         weight scales; ``status()`` counts the tiles outside its range, which get fp32 logits) or "bf16_split3"
-        (three-way bf16 operands, 6 MFMAs per term, no range limit)."""
+        (three-way bf16 operands, 6 MFMAs per term, no range limit).
+
+        head: "softmax" — the net's two outputs are logits, the action is a Categorical sample and
+        ``prob`` / ``probs`` are probabilities; "q" — they are Q-values (``make_qnet``), the action is
+        epsilon-greedy (dqn.py:93-105: with probability ``epsilon`` a random action, otherwise the
+        argmax) and ``prob`` / ``probs`` hold the chosen action's Q-value / both Q-values.
+        ``epsilon`` = 0 is the reference's DQNController (rl_controllers.py:143-159).  The head and
+        epsilon belong to this actor, not to the env: ``select_actions`` and ``rollout`` apply them to
+        the env's context whenever it holds another actor's (``_apply_head``), so actors of both heads
+        can share an env."""
         if precision not in L.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}")
         forms = {"f16_split": L.FP32_F16_SPLIT, "bf16_split3": L.FP32_BF16_SPLIT3}
         if fp32_form not in forms:
             raise ValueError(f"fp32_form must be one of {sorted(forms)}")
+        if head not in L.HEADS:
+            raise ValueError(f"head must be one of {sorted(L.HEADS)}")
+        self.head = head
+        self.epsilon = self._check_epsilon(epsilon)
         env.shard.set_option("actor_fp32_form", forms[fp32_form])
         self.fp32_form = fp32_form
         if not 1 <= len(actor.layers) <= L.ACTOR_MAX_LAYERS:
@@ -93,6 +134,28 @@ class DeviceActor:
             net.hidden[i] = h
         sh.actor_load_net(net, ws, bs)
         torch.cuda.current_stream(dev).synchronize()  # (the copies are read by later launches only)
+
+    @staticmethod
+    def _check_epsilon(eps) -> float:
+        eps = float(eps)
+        if not 0.0 <= eps <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("epsilon must be in [0, 1]")
+        return eps
+
+    def set_epsilon(self, eps: float) -> None:
+        """The Q head's exploration rate from the next launch or graph replay on (a device scalar the
+        kernels load: no graph is captured again)."""
+        if self.head != "q":
+            raise ValueError("set_epsilon: only the q head has an epsilon")
+        self.epsilon = self._check_epsilon(eps)
+
+    def _apply_head(self) -> None:
+        """This actor's head and epsilon into the env's context, unless it holds them already
+        (another DeviceActor of the env, or set_epsilon, may have changed them since)."""
+        sh = self.env.shard
+        want = (self.head, self.epsilon if self.head == "q" else 0.0)
+        if sh.actor_head != want:
+            sh.actor_set_head(*want)
 
     def status(self):
         """mdr_actor_status (synchronises): {range_faults: tiles with a non-finite logit, kernel_prec,
@@ -119,6 +182,7 @@ class DeviceActor:
         sh = env.shard
         spec, sc, keep = env.bound_obs_spec()
         self._check_obs(spec)
+        self._apply_head()
         n = env.n_local
         if action is None:
             action = torch.empty(n, dtype=torch.uint8, device=sh.device)
@@ -152,6 +216,7 @@ class DeviceActor:
         torch = _torch()
         env = self.env
         sh = env.shard
+        self._apply_head()
         row0 = srow0 = 0
         if stats is not None:
             if stats.env is not env:
@@ -163,7 +228,9 @@ class DeviceActor:
             if rewards is not None or actions is not None or probs is not None:
                 raise ValueError("with a store, its own actions / probs / rewards rows are the outputs")
             row0 = store.begin_rows(n_ticks)  # (ValueError: overflow, a reset since its rows were taken)
-            rewards, actions, probs = (x[row0:row0 + n_ticks] for x in (store.rewards, store.actions, store.probs))
+            # (a store without probability rows, replay.ReplayStore: probs stays None)
+            rewards, actions, probs = (None if x is None else x[row0:row0 + n_ticks]
+                                       for x in (store.rewards, store.actions, store.probs))
         if sh.penalty_mode != 0 or (env.world > 1 and not getattr(env._comm, "native", False)):
             return self._rollout_stepwise(n_ticks, rewards, actions, probs, store, stats)
         sharded = env.world > 1

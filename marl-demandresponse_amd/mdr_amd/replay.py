@@ -128,3 +128,204 @@ class RolloutStore:
         if idx.numel():
             sh.obs_gather(self._spec, self.snap, self.rows, idx, out)
         return out
+
+
+class TickRing:
+    """Slot arithmetic of ``ReplayStore``: a ring of ``capacity + 1`` tick slots, no device state.
+
+    Slot s holds one tick's pre-step snapshot, actions and rewards; the slot after the newest tick
+    (``head``) holds the trailing snapshot of the post-step state, which is the newest tick's next
+    state — and, being written over the slot of the oldest tick once the ring is full, what drops
+    that tick, like ``deque(maxlen)`` (buffer.py:14-33).  So at most ``capacity`` ticks are valid."""
+
+    def __init__(self, capacity: int):
+        if capacity < 1:
+            raise ValueError("capacity_ticks must be at least 1")
+        self.capacity = int(capacity)
+        self.slots = self.capacity + 1
+        self.head = 0   # the slot the next tick is written to (now: the trailing snapshot's)
+        self.count = 0  # valid ticks
+
+    def clear(self) -> None:
+        self.head = self.count = 0
+
+    def segments(self, k: int):
+        """The runs of consecutive slots the next ``k`` ticks take: [(slot0, ticks)], one run, or two
+        when they cross the ring's end."""
+        if not 1 <= k <= self.capacity:
+            raise ValueError(f"a collect takes 1 to {self.capacity} ticks (the ring's capacity), not {k}")
+        first = min(k, self.slots - self.head)
+        return [(self.head, first)] + ([(0, k - first)] if k > first else [])
+
+    def commit(self, k: int) -> None:
+        self.head = (self.head + k) % self.slots
+        self.count = min(self.count + k, self.capacity)
+
+    @property
+    def oldest(self) -> int:
+        return (self.head - self.count) % self.slots
+
+    def valid_slots(self):
+        """The slots of the valid ticks, oldest first."""
+        return [(self.oldest + j) % self.slots for j in range(self.count)]
+
+    def next_slot(self, s: int) -> int:
+        return (s + 1) % self.slots
+
+
+class ReplayStore:
+    """Device replay memory of (s, a, r, s') for DQN from the fused rollout: ``RolloutStore``'s state
+    snapshots in a ring (``TickRing``) of ``capacity_ticks + 1`` tick slots, no ``probs`` slab.  The
+    next state of a transition is the same house's row in the ring-next slot, so a stored transition
+    is 8 + 8 + 4 (snapshot) + 1 (action) + 8 (reward) = 29 B, against the reference's two float32
+    state rows (buffer.py:14-33, dqn.py:107-123).
+
+    Transitions are addressed by a logical index, oldest first: ``tick_rank * n_local + house`` with
+    tick_rank 0 the oldest valid tick — the order of the reference's deque.  The same limits as
+    ``RolloutStore`` (one shard, fixed links, refusal after ``reset()`` until ``clear()``); and the env
+    may only be stepped by ``collect`` while the store holds ticks (the trailing snapshot is the next
+    collect's first state)."""
+
+    nbytes_per_house_tick = 8 + 8 + 4 + 1 + 8  # t_air, t_mass, hvac, action, reward
+
+    def __init__(self, env, capacity_ticks: int):
+        import torch
+
+        self.ring = TickRing(capacity_ticks)
+        self.env = env
+        RolloutStore._check_supported(self)
+        dev = env.shard.device
+        S, n = self.ring.slots, env.n_local
+        self.capacity, self.n_local = self.ring.capacity, n
+        self.t_air = torch.empty((S, n), dtype=torch.float64, device=dev)
+        self.t_mass = torch.empty((S, n), dtype=torch.float64, device=dev)
+        self.hvac = torch.empty((S, n), dtype=torch.int32, device=dev)
+        self.scalars = torch.empty((S, 4), dtype=torch.float64, device=dev)
+        self.actions = torch.empty((S, n), dtype=torch.uint8, device=dev)
+        self.rewards = torch.empty((S, n), dtype=torch.float64, device=dev)
+        self.probs = None  # (DeviceActor.rollout's store protocol: no probability rows)
+        self.snap = L.mdr_snap(C.sizeof(L.mdr_snap), S, n, L.ptr(self.t_air), L.ptr(self.t_mass),
+                               L.ptr(self.hvac), L.ptr(self.scalars))
+        self._epoch = None
+        self._spec = None
+        self._table = None
+        self._tick = None  # the env tick the trailing snapshot was taken at
+        self._collecting = False
+
+    # ---------------------------------------------------------------- validity (RolloutStore's rules)
+    @property
+    def rows(self) -> int:
+        return self.ring.count
+
+    _check_supported = RolloutStore._check_supported
+    _bind = RolloutStore._bind
+    _check_epoch = RolloutStore._check_epoch
+
+    def clear(self) -> None:
+        self.ring.clear()
+        self._tick = None
+
+    def __len__(self) -> int:
+        return self.ring.count * self.n_local
+
+    # ---------------------------------------------------------------- DeviceActor.rollout's store protocol
+    def begin_rows(self, k: int) -> int:
+        """The first of the next ``k`` slots, which must be consecutive (``collect`` splits a run that
+        crosses the ring's end)."""
+        self._check_epoch("append rows")
+        if not self._collecting:
+            raise ValueError("ReplayStore: rollouts fill it through collect() (ring segments, trailing snapshot)")
+        if self.ring.head + k > self.ring.slots:
+            raise ValueError("ReplayStore: rows of one rollout call must not cross the ring's end")
+        return self.ring.head
+
+    def commit_rows(self, k: int) -> None:
+        self.ring.commit(k)
+
+    # ---------------------------------------------------------------- collect
+    def collect(self, device_actor, n_ticks: int, use_graph: bool = True):
+        """``n_ticks`` of ``device_actor.rollout`` into the ring — two rollout calls when they cross
+        its end, so that the rows of one call are consecutive — then the trailing snapshot of the
+        post-step state (``mdr_snapshot``) into the slot after the newest tick."""
+        if device_actor.env is not self.env:
+            raise ValueError("the store belongs to another environment")
+        self._check_epoch("append rows")
+        if self.ring.count and self._tick != self.env._tick:
+            raise ValueError("ReplayStore: the environment was stepped outside collect() since the trailing "
+                             "snapshot was taken (it is the newest tick's next state); clear() the store")
+        segs = self.ring.segments(n_ticks)
+        self._collecting = True
+        try:
+            for _slot0, k in segs:
+                device_actor.rollout(k, store=self, use_graph=use_graph)
+        except Exception:
+            self.clear()  # (a partial run has no trailing snapshot: nothing of it is kept)
+            raise
+        finally:
+            self._collecting = False
+        self._trailing_snapshot()
+
+    def _trailing_snapshot(self) -> None:
+        env = self.env
+        sc = L.mdr_obs_scalars(float(env._P_host), float(env.power_grid.current_signal),
+                               float(env._solar), float(env.current_od_temp))
+        env.shard.snapshot(self.snap, self.ring.head, sc, use_p_dev=env._P_dev_valid)
+        self._tick = env._tick
+
+    # ---------------------------------------------------------------- sampling and gathers
+    def sample_indices(self, batch: int, sampler: str = "reference"):
+        """``batch`` logical transition indices drawn with replacement from the valid transitions:
+        "reference" — ``random.choices(range(len), k=batch)`` of the global Python RNG, the draws of
+        ReplayBuffer.sample (buffer.py:28-30) on a deque of the same length; "device" —
+        ``torch.randint`` on the GPU.  Device int64."""
+        import random
+
+        import torch
+
+        n = len(self)
+        if n == 0:
+            raise ValueError("ReplayStore: empty")
+        dev = self.env.shard.device
+        if sampler == "reference":
+            return torch.tensor(random.choices(range(n), k=batch), dtype=torch.int64, device=dev)
+        if sampler == "device":
+            return torch.randint(n, (batch,), dtype=torch.int64, device=dev)
+        raise ValueError("sampler must be 'reference' or 'device'")
+
+    def _physical(self, idx, shift: int = 0):
+        """slot * n_local + house of logical indices (``shift`` = 1: the ring-next slot, the next
+        state's); an index outside the valid transitions maps to -1 (a NaN row, like RolloutStore)."""
+        import torch
+
+        dev = self.env.shard.device
+        idx = torch.as_tensor(idx, device=dev).to(torch.int64).reshape(-1)
+        n, S = self.n_local, self.ring.slots
+        slot = (torch.div(idx, n, rounding_mode="floor") + (self.ring.oldest + shift)) % S
+        phys = slot * n + idx % n
+        return torch.where((idx >= 0) & (idx < len(self)), phys, torch.full_like(phys, -1)).contiguous()
+
+    def _gather(self, phys):
+        import torch
+
+        self._check_epoch("gather states")
+        sh = self.env.shard
+        out = torch.empty((phys.numel(), self._spec.n_feat), dtype=torch.float32, device=sh.device)
+        if phys.numel():
+            sh.obs_gather(self._spec, self.snap, self.ring.slots, phys, out)
+        return out
+
+    def states(self, idx):
+        """float32 [len(idx), n_feat]: the obs rows of the transitions' states (one k_obs_gather)."""
+        return self._gather(self._physical(idx))
+
+    def next_states(self, idx):
+        """... of their next states: the same house in the ring-next slot (one k_obs_gather)."""
+        return self._gather(self._physical(idx, 1))
+
+    def actions_at(self, idx):
+        """int64 [len(idx)]: the transitions' actions."""
+        return self.actions.reshape(-1)[self._physical(idx)].long()
+
+    def rewards_at(self, idx):
+        """float64 [len(idx)]: the transitions' rewards."""
+        return self.rewards.reshape(-1)[self._physical(idx)]

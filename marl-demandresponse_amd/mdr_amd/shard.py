@@ -65,6 +65,7 @@ class HipShard:
         cfg.seed = seed & 0xFFFFFFFFFFFFFFFF
         self.cfg = cfg
         self.penalty_mode = cfg.penalty_mode
+        self.actor_head = ("softmax", 0.0)  # the context's head and epsilon (actor_set_head; mdr_create's default)
         ctx = C.c_void_p()
         L.check(self.lib.mdr_create(C.byref(ctx), C.byref(cfg)), "mdr_create")
         self.ctx = ctx
@@ -333,6 +334,15 @@ class HipShard:
         w = (C.c_void_p * n)(*[L.ptr(t) for t in weights])
         b = (C.c_void_p * n)(*[L.ptr(t) for t in biases])
         L.check(self.lib.mdr_actor_load_net(self.ctx, C.byref(net), w, b, self.stream()), "mdr_actor_load_net")
+
+    def actor_set_head(self, head: str, epsilon: float = 0.0):
+        """mdr_actor_set_head: the head of every later actor call of this context — "softmax"
+        (MAPPO's Categorical sampling) or "q" (DQN's epsilon-greedy over the two Q-values; ``epsilon``
+        goes to a device float on the current stream, so captured rollout graphs follow it).
+        ``self.actor_head`` records what the context holds."""
+        L.check(self.lib.mdr_actor_set_head(self.ctx, L.HEADS[head], float(epsilon), self.stream()),
+                "mdr_actor_set_head")
+        self.actor_head = (head, float(epsilon))
 
     def actor_status(self):
         """mdr_actor_status (synchronises; counts since the last call): {range_faults: fused fp16-split
