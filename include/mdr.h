@@ -201,7 +201,11 @@ int mdr_params_changed(mdr_ctx* ctx);
  *                           = the reference's update as a per-house affine transition formed once
  *                           per window (4 FMAs per temperature per tick; ~1e-13 K per tick from the
  *                           reference order), MDR_THERMAL_EXACT = the reference's expression in its
- *                           operation order every tick (bit-identical to the one-tick kernels) */
+ *                           operation order every tick (bit-identical to the one-tick kernels).
+ *                           Open-loop sources only: the closed-loop windows of the bang-bang
+ *                           sources (k_step_closed) always run the EXACT form and ignore it — a
+ *                           decision compares T with a threshold, so a last-bit difference could
+ *                           flip an action and fork the trajectory */
 enum { MDR_OPT_STEP_TPW = 1, MDR_OPT_FASTDIV = 2, MDR_OPT_WINDOW_PIPELINE = 3, MDR_OPT_SHARDED_OVERLAP = 4,
        MDR_OPT_GREEDY_SORT = 5, MDR_OPT_FORCE_HALO = 6, MDR_OPT_WINDOW_THERMAL = 7,
        MDR_OPT_HALO_OVERLAP = 9, MDR_OPT_ACTOR_GENERIC = 10, MDR_OPT_HALO_IN_COUNTS = 12,
@@ -254,7 +258,8 @@ int mdr_populate(mdr_ctx* ctx, const mdr_pop_spec* spec, void* stream);
  * accumulated into the context's count slab for this tick (int64[kCountShards * n_cap], sharded
  * to spread atomics).  P = sum_k count_k * cap_k / cop is exact and order independent.  State
  * is not modified.  (cluster.py:82-88)  Not needed when the previous mdr_step ran with a
- * lookahead action source. */
+ * lookahead action source.  MDR_ACT_BANGBANG / _DEADBAND_BANGBANG evaluate the controller on the
+ * current state (the decision mdr_step takes from the pre-step state). */
 int mdr_power_counts(mdr_ctx* ctx, const uint8_t* action, int action_mode, uint64_t tick,
                      void* stream);
 /* Device pointer + element count of the current tick's count slab: the buffer a multi-GPU caller
@@ -287,9 +292,13 @@ int mdr_reward_finalize(mdr_ctx* ctx, const mdr_tick* tick, double* reward, void
 
 /* ---- several ticks in one call (single GPU) --------------------------------------------- */
 /* n_ticks consecutive steps; ticks[] in host memory.  action / reward advance by act_stride /
- * rew_stride elements per tick (0 = reuse one buffer).  With an in-kernel action source
- * (MDR_ACT_RANDOM / _ALWAYS_ON / _BANGBANG / _DEADBAND_BANGBANG) every tick is ONE launch (the
- * counts of tick t+1 come from tick t's lookahead); with MDR_ACT_BUFFER two.  use_graph != 0
+ * rew_stride elements per tick (0 = reuse one buffer).  Where the temporally blocked paths below
+ * (mdr_set_rollout_window) do not apply, with an in-kernel action source (MDR_ACT_RANDOM /
+ * _ALWAYS_ON / _BANGBANG / _DEADBAND_BANGBANG) every tick is ONE launch (the first tick's counts from
+ * a phase-1 launch, the counts of tick t+1 from tick t's lookahead); with MDR_ACT_BUFFER two.
+ * MDR_ACT_BANGBANG / _DEADBAND_BANGBANG (bangbang_controllers.py:25-65) are closed-loop: every tick's
+ * action is taken from the state the tick before left, bit for bit the loop of mdr_step(action_mode
+ * = lookahead = the source).  use_graph != 0
  * captures the sequence in a hipGraph (cached per shape) and replays it.  p_out (device scalar,
  * may be NULL) receives the cluster power of the LAST tick, as mdr_step's p_out.
  * Common penalty modes (common_L2 / common_max_error / mixture): the rewards come out finalised —
@@ -307,8 +316,18 @@ int mdr_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t*
  * penalty mode on an unsharded context; individual_L2 on a sharded one) run TEMPORALLY BLOCKED: windows of up to `ticks` steps per launch (k_step_window), the
  * state and parameters read and written once per window, rewards written every tick, each tick's
  * cluster power from counts the previous launch ran ahead (the FSM of an open-loop source does
- * not depend on the thermal state).  Bit-identical to the one-tick path.  ticks in 1..32
- * (default 32), 0 = one launch per tick.  Applies to mdr_rollout and
+ * not depend on the thermal state).  Bit-identical to the one-tick path under MDR_THERMAL_EXACT.
+ * The bang-bang sources (MDR_ACT_BANGBANG / _DEADBAND_BANGBANG) run blocked too in mdr_rollout,
+ * under individual_L2 with <= 4 capacity classes: a closed-loop window (k_step_closed) keeps
+ * controller, lockout FSM and thermal update in registers for its ticks, writes each tick's raw
+ * temperature penalty to the reward row and counts its ON houses; k_win_reduce then forms every
+ * tick's cluster power and a finish kernel (k_closed_reward) rewrites the rows in place (with
+ * rew_stride == 0 only the last tick's).  Always the EXACT thermal form (MDR_OPT_WINDOW_THERMAL is
+ * ignored): bit-identical to the one-tick path.  What falls back to one launch per tick inside the
+ * call: the bang-bang sources under the common penalty modes, any source with more than 4 capacity
+ * classes, and ticks = 0.  mdr_rollout_sharded returns MDR_EARG for the bang-bang sources (the
+ * window's cluster power would need an allreduce inside the launch sequence): per-step API.
+ * ticks in 1..32 (default 32), 0 = one launch per tick.  Applies to mdr_rollout and
  * mdr_rollout_sharded; drops cached rollout graphs. */
 int mdr_set_rollout_window(mdr_ctx* ctx, int ticks);
 
@@ -318,14 +337,16 @@ int mdr_set_rollout_window(mdr_ctx* ctx, int ticks);
  * mdr_rollout with the same n_ticks, action source, action buffer and first tick id (and
  * consecutive tick ids) uses them and launches the first window's step kernel with the drivers as
  * kernel arguments; any other entry point called in between discards them.  A no-op for rollouts
- * that do not take the temporally blocked path.  On a context with an RCCL communicator it also
+ * that do not take the open-loop temporally blocked path (the bang-bang sources among them: every
+ * tick's ON set depends on the thermal state, so nothing can be counted ahead).  On a context with an RCCL communicator it also
  * allreduces the counts (single-window rollouts; the match is mdr_rollout_sharded). */
 int mdr_rollout_begin(mdr_ctx* ctx, int n_ticks, uint64_t tick0, const uint8_t* action, int64_t act_stride,
                       int action_mode, void* stream);
 
 /* Measurement (no reference counterpart): mdr_rollout's launch sequence issued directly (no graph)
  * with an event pair around every step-kernel launch; *ms = the summed step-kernel time,
- * *launches = step launches (windows, or ticks on the one-tick path).  Advances the state like
+ * *launches = step launches (windows — k_step_window or k_step_closed —, or ticks on the one-tick
+ * path).  Advances the state like
  * mdr_rollout; synchronises the stream. */
 int mdr_time_step_kernels(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                           int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,

@@ -283,10 +283,9 @@ int default_tpw(int64_t n) { return n <= 1572864 ? 2 : 4; }
 // phase 1 into the current slab
 int launch_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, const TickArgs* tkp,
                   hipStream_t st) {
-  int m = mode;
-  if (m == MDR_ACT_BANGBANG || m == MDR_ACT_DEADBAND_BANGBANG)
-    return fail(MDR_EARG, "phase 1 with a bang-bang action source: use mdr_step lookahead or a BUFFER");
-  hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, action, m,
+  static_assert(MDR_ACT_BANGBANG == kActBangBang && MDR_ACT_DEADBAND_BANGBANG == kActDeadband,
+                "the kernels take the bang-bang sources by their public ids");
+  hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, action, mode,
                      tick, tkp, slab_at(c, c->ring));
   LAUNCH_CHECK("k_power_counts");
   return MDR_OK;
@@ -926,10 +925,20 @@ static bool win_common(const mdr_ctx* c) { return c->kp.penalty_mode != MDR_PEN_
 // (the lookahead's FSM runs on unsaturated seconds-since-off in a signed offset form: L <= 2^30 - 1,
 // dt <= 2^25, so a saturated value plus 33 ticks of dt and L - 32 dt stay inside int32 —
 // mdr_kernels.hip win_run_t)
-static bool window_ok(const mdr_ctx* c, int mode) {
+static bool window_geom_ok(const mdr_ctx* c) {
   return c->win > 0 && c->d_wslab && c->kp.n_cap <= kWindowCap && c->kp.L < (1 << 30) && c->kp.dt >= 0 &&
-         c->kp.dt <= (1 << 25) && (win_common(c) ? c->d_wpen != nullptr : true) &&
+         c->kp.dt <= (1 << 25);
+}
+
+static bool window_ok(const mdr_ctx* c, int mode) {
+  return window_geom_ok(c) && (win_common(c) ? c->d_wpen != nullptr : true) &&
          (mode == MDR_ACT_RANDOM || mode == MDR_ACT_ALWAYS_ON || mode == MDR_ACT_BUFFER);
+}
+
+// the closed-loop window (k_step_closed): the bang-bang sources under individual_L2, the same
+// window, class and L / dt conditions; everything else of theirs runs one launch per tick
+static bool closed_ok(const mdr_ctx* c, int mode) {
+  return window_geom_ok(c) && !win_common(c) && (mode == MDR_ACT_BANGBANG || mode == MDR_ACT_DEADBAND_BANGBANG);
 }
 
 // the window slots' shard part is zero between rollouts (k_win_reduce zeroes what it reads);
@@ -1224,14 +1233,70 @@ static bool pipe_buffers(mdr_ctx* c) {
   return true;
 }
 
+// n ticks of a bang-bang source as ceil(n / win) closed-loop windows of near-equal size
+// (window_launches' split), the drivers staged in tk.  Per window: k_step_closed (state in registers
+// for the K ticks, raw pen_i to the reward rows, the ticks' ON counts into the count slot),
+// k_win_reduce (P and the signal penalty into the tick records; it zeroes the shards it sums, so the
+// one slot serves every window: stream order puts the next window's adds behind it) and
+// k_closed_reward over the window's rows.  One shared row (rew_stride == 0): only the last window's
+// last tick is finalised.  Kernels only, so the sequence can be captured.
+static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, double* reward, int64_t rew_stride,
+                           double* p_out, hipStream_t st) {
+  const int nw = (n + c->win - 1) / c->win;
+  const int base = n / nw, rem = n % nw;
+  const KParams kp = c->kp;
+  const int ncap = kp.n_cap;
+  unsigned long long* slot = c->d_wslab;
+  const double* rec = reinterpret_cast<const double*>(win_red_ptr(c, slot) + (size_t)kWindowMax * ncap);
+  const unsigned grid = win_grid(c);
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  int t0 = 0;
+  for (int w = 0; w < nw; ++w) {
+    const int K = base + (w < rem ? 1 : 0);
+    double* r = reward + (int64_t)t0 * rew_stride;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (c->step_events) {
+      HIP_TRY(hipEventCreate(&e0));
+      c->step_events->push_back(e0);
+      HIP_TRY(hipEventCreate(&e1));
+      c->step_events->push_back(e1);
+    }
+#define MDR_CLOSED(C)                                                                                          \
+  do {                                                                                                         \
+    if (e0)                                                                                                    \
+      hipExtLaunchKernelGGL((k_step_closed<C, kWinHpt>), dim3(grid), dim3(256), 0, st, e0, e1, 0, kp, tk + t0, K, r, \
+                            rew_stride, slot);                                                                 \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_step_closed<C, kWinHpt>), dim3(grid), dim3(256), 0, st, kp, tk + t0, K, r, rew_stride, \
+                         slot);                                                                                \
+  } while (0)
+    if (mode == MDR_ACT_BANGBANG) MDR_CLOSED(kActBangBang);
+    else MDR_CLOSED(kActDeadband);
+#undef MDR_CLOSED
+    LAUNCH_CHECK("k_step_closed");
+    hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot, K, tk + t0,
+                       w == nw - 1 ? p_out : nullptr);
+    LAUNCH_CHECK("k_win_reduce");
+    if (rew_stride || w == nw - 1) {
+      const int j0 = rew_stride ? 0 : K - 1;
+      hipLaunchKernelGGL(k_closed_reward, dim3(blocks(kp.n, 256), K - j0), dim3(256), 0, st, kp, rec, j0, r,
+                         rew_stride);
+      LAUNCH_CHECK("k_closed_reward");
+    }
+    t0 += K;
+  }
+  c->wslab_dirty = false;
+  return MDR_OK;
+}
+
 // The launch sequence of a rollout with staged drivers (d_ticks), so a captured graph is reusable:
-// the window sequence, or one step launch per tick (+ phase 1 where no lookahead counts ahead).
+// the window sequence (open-loop sources), the closed-loop window sequence (bang-bang sources under
+// individual_L2), or one step launch per tick (+ phase 1 where no lookahead counts ahead).
 static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t act_stride, int mode,
                             double* reward, int64_t rew_stride, double* p_out, hipStream_t st) {
   if (window_ok(c, mode))
     return window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, false, st);
-  if (mode == MDR_ACT_BANGBANG || mode == MDR_ACT_DEADBAND_BANGBANG)
-    return fail(MDR_EARG, "rollout: bang-bang sources need the per-step API (mdr_step with a lookahead)");
+  if (closed_ok(c, mode)) return closed_launches(c, n, c->d_ticks, mode, reward, rew_stride, p_out, st);
   if (int rc = zero_slabs(c, st)) return rc;
   c->ring = 0;
   const bool la = lookahead_ok(mode);

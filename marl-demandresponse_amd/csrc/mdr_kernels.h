@@ -180,6 +180,15 @@ __global__ void k_win_pen_reduce(const double* part, int ntile, double* res);
 // reward rows j0 + blockIdx.y of a common-penalty window from res / sig (k_reward_finalize's expression)
 __global__ void k_win_reward_common(KParams p, const double* res, const double* sig, int j0, double* reward,
                                     int64_t rew_stride);
+// The closed-loop window of the bang-bang sources (CTRL = kActBangBang / kActDeadband): K ticks of
+// controller -> FSM -> thermal update in registers, the raw pen_i to reward row j, the ticks' ON
+// counts into `slot` (this window's); k_win_reduce and k_closed_reward follow it.  Always the
+// reference's thermal expression (MDR_OPT_WINDOW_THERMAL does not apply).
+template <int CTRL, int HPT>
+__global__ void k_step_closed(KParams p, const TickArgs* tkp, int K, double* reward, int64_t rew_stride,
+                              unsigned long long* slot);
+// reward rows j0 + blockIdx.y of a closed-loop window from their raw pen_i and the tick records
+__global__ void k_closed_reward(KParams p, const double* rec, int j0, double* reward, int64_t rew_stride);
 // k_reward_finalize with the tick's drivers in device memory (rollouts with staged drivers)
 __global__ void k_reward_finalize_dev(KParams p, const TickArgs* tkp, const unsigned long long* counts,
                                       const double* partial2, double* reward);

@@ -46,7 +46,8 @@ __global__ void k_zero_u64(unsigned long long* __restrict__ dst, int64_t n) {
 }
 
 // --------------------------------------------------------------------------------------- K0
-// Phase 1: FSM only -> ON count per capacity class (cluster.py:82-88).  Reads 6 B per house.
+// Phase 1: FSM only -> ON count per capacity class (cluster.py:82-88).  Reads 6 B per house
+// (22 B with a bang-bang source: its decision needs the air temperature and the target).
 __global__ void __launch_bounds__(256) k_power_counts(KParams p, const uint8_t* __restrict__ action,
                                                       int action_mode, uint64_t tick0,
                                                       const TickArgs* tkp,
@@ -58,6 +59,9 @@ __global__ void __launch_bounds__(256) k_power_counts(KParams p, const uint8_t* 
   uint32_t hw[kPcHouses];
   int cls[kPcHouses];
   bool a[kPcHouses];
+  // the bang-bang sources: the controller on the current state (pick_action of the step kernels)
+  const bool bb = action_mode == kActBangBang || action_mode == kActDeadband;
+  double T[kPcHouses], tg[kPcHouses];
 #pragma unroll
   for (int u = 0; u < kPcHouses; ++u) {
     const int64_t c0 = ((int64_t)blockIdx.x * kPcHouses + u) * blockDim.x;
@@ -69,16 +73,24 @@ __global__ void __launch_bounds__(256) k_power_counts(KParams p, const uint8_t* 
     }
     hw[u] = 0u;
     cls[u] = -1;
+    T[u] = tg[u] = 0.0;
     if (i < p.n) {
       if (action_mode == MDR_ACT_BUFFER) a[u] = action[i] != 0;
       hw[u] = p.hvac[i];
       cls[u] = p.cap_idx[i];
+      if (bb) {
+        T[u] = p.t_air[i];
+        tg[u] = p.target[i];
+      }
     }
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int u = 0; u < kPcHouses; ++u) {
+    if (bb)
+      a[u] = action_mode == kActBangBang ? ctrl_bangbang(T[u], tg[u])
+                                         : ctrl_deadband(T[u], tg[u], p.deadband, hv_on(hw[u]));
     const bool on = cls[u] >= 0 && hv_on(hvac_fsm(hw[u], a[u], p.dt, p.L));
     for (int k = 0; k < p.n_cap; ++k) {
       const unsigned long long m = __ballot(on && cls[u] == k);
@@ -1667,6 +1679,143 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
   }
 }
 
+// --------------------------------------------------------------------------------------- K1C
+// Temporally blocked step for the CLOSED-LOOP bang-bang sources (BangBangController /
+// DeadbandBangBangController, bangbang_controllers.py:25-65): one launch steps a window of K <= 32
+// ticks.  A bang-bang action reads the house's own air temperature and nothing else, and no house
+// depends on another inside a tick except through the cluster power P(t), which enters only the
+// reward's signal term.  So controller -> lockout FSM -> thermal update stay in registers for the K
+// ticks (the order of the one-tick kernels: the action from the pre-step state, pick_action), the
+// state is loaded and written once per window, and per tick the wave
+//   * stores the raw temperature penalty pen_i to reward row j (no wave knows P(j) yet), and
+//   * counts the tick's ON houses per capacity class (ballot + popcount against the tile's class
+//     masks, scalar work) into lane j of a per-class register (v_writelane).
+// After the K ticks lane j puts tick j's counts into the wave's LDS row and the block adds its rows
+// to THIS window's count slot (win_flush).  k_win_reduce (unchanged) then sums the shards and writes
+// each tick's P and negated signal penalty into the tick records, and k_closed_reward rewrites the
+// reward rows in place.  No ON-mask rows, no end-word buffer.
+// The thermal update is always the reference's expression (rc_apply_win, the per-window
+// coefficients being the one-tick expressions): a decision compares T with a threshold, so a form
+// that differs in the last bits (MDR_THERMAL_AFFINE) could flip an action and fork the trajectory.
+// Bit-identical to the k_step_t loop with lookahead = the source: same operations in the same order
+// per house, P a sum of exact integer counts.
+template <int CTRL, int HPT>
+__global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* __restrict__ tkp, int K,
+                                                     double* __restrict__ reward, int64_t rew_stride,
+                                                     unsigned long long* __restrict__ slot) {
+  static_assert(CTRL == kActBangBang || CTRL == kActDeadband, "a bang-bang action source");
+  __shared__ unsigned s_cnt[4][kWinMax * kWinCap];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const WinTile<HPT> t(p);
+
+  // ---- state + parameters, once per window
+  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
+  uint32_t w[HPT];
+  int cls[HPT];
+  const bool params_ok = !*p.params_bad && p.fast_tick_ok;
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    const uint32_t i = t.idx[h];
+    T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
+    ca[h] = p.ca[i]; cm[h] = p.cm[i];
+    w[h] = p.hvac[i];
+    cls[h] = p.cap_idx[i];
+  }
+  double q_on[kWinCap];
+#pragma unroll
+  for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
+  double qc[HPT];  // heat when ON
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    qc[h] = q_on[0];
+#pragma unroll
+    for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
+  }
+  uint64_t clm[HPT][kWinCap];  // class membership lane masks (houses of the shard only)
+  win_classes<HPT>(t, cls, clm);
+  RcWin rw[HPT];
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    if (params_ok) {
+      rw[h] = rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
+    } else {  // IEEE division (identical bits; parameters outside the fast-division range)
+      rw[h].k = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
+      rw[h].rCa.nb = -ca[h];
+      rw[h].rc.nb = -ua[h];
+      rw[h].rd.nb = -(rw[h].k.r2 - rw[h].k.r1);
+      rw[h].UaHm = ua[h] + hm[h];
+    }
+  }
+
+  // ---- the K ticks; the tick's drivers are wave-uniform (scalar loads), read one tick ahead
+  uint32_t cnt_v[kWinCap] = {0u, 0u, 0u, 0u};  // lane j: tick j's ON houses of the tile per class
+  const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
+  TickArgs nx = tkp[0];
+  for (int j = 0; j < K; ++j) {
+    const TickArgs tk = nx;
+    nx = tkp[j + 1 < K ? j + 1 : j];
+    const double od_k = tk.t_od_prev + 273.0;  // rc_apply_t's od_k
+    const bool tick_ok = fabs(tk.t_od_prev) < 1048576.0 && fabs(tk.solar) < 1099511627776.0;
+    uint64_t ok_m = ~0ull;
+#pragma unroll
+    for (int h = 0; h < HPT; ++h)
+      ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
+    const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
+    // only the last row of a shared reward row (rew_stride == 0) is ever finalised
+    const bool store = rew_stride != 0 || j == K - 1;
+    char* rrow = reinterpret_cast<char*>(reward + (int64_t)j * rew_stride);
+    uint64_t on_m[HPT];
+    auto houses = [&](auto fast_c) {
+      constexpr bool F = decltype(fast_c)::value;
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        const bool a = t.v[h] && (CTRL == kActBangBang ? ctrl_bangbang(T[h], tg[h])
+                                                       : ctrl_deadband(T[h], tg[h], p.deadband, hv_on(w[h])));
+        w[h] = hvac_fsm(w[h], a, p.dt, p.L);
+        const bool on = hv_on(w[h]);
+        on_m[h] = __builtin_amdgcn_ballot_w64(on);
+        const double q = on ? qc[h] : 0.0;
+        double Tn, Tmn;
+        rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, tk.solar, od_k, Tn, Tmn);
+        T[h] = Tn;
+        Tm[h] = Tmn;
+        const double pen = deadband_l2(tg[h], p.deadband, Tn);
+        if (store && t.v[h]) __builtin_nontemporal_store(pen, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+      }
+    };
+    if (fast) houses(std::true_type());
+    else houses(std::false_type());
+#pragma unroll
+    for (int c = 0; c < kWinCap; ++c) {
+      uint32_t k = 0u;
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) k += (uint32_t)__popcll(on_m[h] & clm[h][c]);
+      cnt_v[c] = writelane_u32(cnt_v[c], k, j);
+    }
+  }
+
+  // ---- state back, once per window
+#pragma unroll
+  for (int h = 0; h < HPT; ++h)
+    if (t.v[h]) {
+      const uint32_t i = t.i0 + 64u * h;
+      p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w[h];
+    }
+
+  // ---- the window's ON counts into its slot (the lookahead's tail of k_step_window)
+  if (lane < K) {
+#pragma unroll
+    for (int c = 0; c < kWinCap; ++c) s_cnt[wv][lane * kWinCap + c] = cnt_v[c];
+  }
+  __syncthreads();
+  win_flush(p, K, s_cnt, slot);
+}
+
+template __global__ void k_step_closed<kActBangBang, kWinHpt>(KParams, const TickArgs*, int, double*, int64_t,
+                                                              unsigned long long*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt>(KParams, const TickArgs*, int, double*, int64_t,
+                                                              unsigned long long*);
+
 
 #define MDR_INST_WIN_C(A, SI, KA_, FO, CO)                                                                     \
   template __global__ void k_step_window<A, kWinHpt, SI, KA_, FO, CO>(KParams, const uint8_t*, int64_t,        \
@@ -1868,6 +2017,21 @@ __global__ void __launch_bounds__(256) k_win_reward_common(KParams p, const doub
   double* r = reward + (int64_t)j * rew_stride + i;
   const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
   __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
+}
+
+// Finish of a closed-loop window (behind k_step_closed and k_win_reduce): reward row j = j0 +
+// blockIdx.y holds the raw pen_i and is rewritten in place with the one-tick kernels' individual_L2
+// expression; the signal term is the exact negation of the tick record's rec[2] (win_nsig), so the
+// sum has the bits of k_step_t's.  rew_stride == 0: the caller launches the last tick alone.
+__global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* __restrict__ rec, int j0,
+                                                       double* __restrict__ reward, int64_t rew_stride) {
+  const int j = j0 + (int)blockIdx.y;
+  const double sig_term = -rec[j * kWinRec + 2];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  double* r = reward + (int64_t)j * rew_stride + i;
+  const double tpen = p.alpha_temp * *r;
+  __builtin_nontemporal_store(-((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term), r);
 }
 
 // Reward of the last tick of an overlapped multi-GPU rollout (the k_step launches there write

@@ -597,7 +597,13 @@ class Environment:
         calls, profiles/r02h_ab.log).  The common penalty modes (common_L2, common_max_error,
         mixture) take the same path on an unsharded environment: each window's step kernel writes
         per-wave penalty partials every tick and two finish kernels form the rewards (a 1-D
-        ``rewards`` holds the last tick's); sharded environments keep ``step_tensor`` for them."""
+        ``rewards`` holds the last tick's); sharded environments keep ``step_tensor`` for them.
+        ``action_mode='bangbang'`` / ``'deadband_bangbang'`` (unsharded): closed-loop windows under
+        individual_L2 with <= 4 capacity classes (k_step_closed: controller, lockout FSM and thermal
+        update in registers for up to 32 ticks, two short kernels finish each window's rewards),
+        otherwise one step launch per tick inside the call; either way bit for bit the
+        ``step_tensor(None, action_mode=c, lookahead=c)`` loop.  The drivers are staged first
+        (there is no early count to launch: every tick's ON set depends on the thermal state)."""
         import torch
 
         sh = self._shard
@@ -605,8 +611,9 @@ class Environment:
             # (the cluster's per-tick mean / max penalty would need an allreduce inside the window sequence)
             raise NotImplementedError("sharded rollout supports individual_L2; use step_tensor for common penalties")
         mode = ACTION_MODES[action_mode]
-        if mode in (L.ACT_BANGBANG, L.ACT_DEADBAND_BANGBANG):
-            raise NotImplementedError("bang-bang rollouts: use step_tensor(action_mode=..., lookahead=...)")
+        if mode in (L.ACT_BANGBANG, L.ACT_DEADBAND_BANGBANG) and self._comm is not None:
+            # (the window's cluster power would need an allreduce inside the closed-loop kernel's launch sequence)
+            raise NotImplementedError("sharded bang-bang rollouts: use step_tensor(action_mode=..., lookahead=...)")
         if rewards is None:
             rewards = torch.empty((n_ticks, self._n_local), dtype=torch.float64, device=sh.device)
         rew_stride = 0 if rewards.dim() == 1 else self._n_local  # 1-D: every tick overwrites it
