@@ -233,6 +233,14 @@ size_t mdr_window_pen_bytes(int64_t n_local);
  * houses; MDR_EARG otherwise ("penalty partial" in mdr_last_error), also for n_local < 1.  Every
  * such launch checks its context's buffer with it first. */
 int mdr_window_pen_check(int64_t n_local, size_t pen_bytes);
+/* Bytes of the per-tick block partials ([32][blocks][12] doubles, a block = 4 tiles of 128 houses)
+ * that a closed-loop window launch with stats rows (mdr_rollout_stats) over n_local houses writes:
+ * ceil(ceil(n_local / 128) / 4) * 32 * 12 * 8.  0 for n_local < 0. */
+size_t mdr_window_stats_bytes(int64_t n_local);
+/* MDR_OK when stats partial rows of `bytes` cover such a launch over n_local houses; MDR_EARG
+ * otherwise ("stats partial" in mdr_last_error), also for n_local < 1.  Every such launch checks
+ * its context's buffer with it first. */
+int mdr_window_stats_check(int64_t n_local, size_t bytes);
 
 /* ---- population ------------------------------------------------------------------------ */
 /* Synthetic population drawn on device from Philox4x32-10(seed, global house id): the reference
@@ -311,6 +319,33 @@ int mdr_reward_finalize(mdr_ctx* ctx, const mdr_tick* tick, double* reward, void
 int mdr_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                 int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                 double* p_out, int use_graph, void* stream);
+/* mdr_rollout that also writes tick t's stats row — mdr_tick_stats' 16 doubles of the state after
+ * its step, its rewards and P — into stats[row0 + t][16] (caller-owned device doubles; the caller
+ * answers for row0 + n_ticks rows), inside the launch sequence: the baseline controllers'
+ * Metrics.update (metrics_service.py:108-157) and TrainingManager.test means
+ * (training_manager.py:265-295) at rollout speed.  stats == NULL is mdr_rollout, launch for launch.
+ *   - closed-loop windows (MDR_ACT_BANGBANG / _DEADBAND_BANGBANG under individual_L2, <= 4 capacity
+ *     classes, window > 0): the window kernel itself forms every tick's block partials
+ *     (k_step_closed<..., STATS>) and one more kernel per window (k_closed_stats) writes its rows.
+ *     Slots 2, 10, 11, 12 are mdr_tick_stats' bits; the sums are formed in another fixed order, and
+ *     slot 4 from sum_i pen_i and the tick's signal term: -((alpha_temp sum pen [/ norm_temp] + n sig)
+ *     / N), the same with rew_stride == 0;
+ *   - one launch per tick (the bang-bang sources otherwise, any source with mdr_set_rollout_window(0)
+ *     or > 4 capacity classes): mdr_tick_stats' two kernels behind every tick's step and finalise
+ *     kernels, bit for bit mdr_tick_stats after mdr_step;
+ *   - the open-loop window rollout (k_step_window) writes no rows: MDR_EARG.
+ * use_graph: the graph is cached per (mdr_rollout's key, stats, row0).  MDR_EARG: row0 < 0.
+ * MDR_ESTATE: a communicator or world > 1 (a row sums this shard's houses only). */
+int mdr_rollout_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
+                      int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
+                      double* p_out, double* stats, int row0, int use_graph, void* stream);
+/* Which of the three cases above mdr_rollout_stats would take for this action source on this
+ * context as it stands (window, penalty mode, capacity classes); nothing is launched:
+ * MDR_STATS_CLOSED_WINDOWS, MDR_STATS_PER_TICK, or the MDR_EARG / MDR_ESTATE it would return (so a
+ * caller can refuse before it advances its own drivers). */
+#define MDR_STATS_CLOSED_WINDOWS 1
+#define MDR_STATS_PER_TICK 2
+int mdr_rollout_stats_path(mdr_ctx* ctx, int action_mode);
 
 /* Open-loop sources (MDR_ACT_RANDOM / _ALWAYS_ON / _BUFFER) with <= 4 capacity classes (every
  * penalty mode on an unsharded context; individual_L2 on a sharded one) run TEMPORALLY BLOCKED: windows of up to `ticks` steps per launch (k_step_window), the

@@ -61,9 +61,11 @@ struct GraphKey {
   void* rew;
   int64_t rew_stride;
   void* p_out;
+  void* stats = nullptr;  // mdr_rollout_stats: the rows' buffer and the first row (baked into the launches)
+  int row0 = 0;
   bool operator<(const GraphKey& o) const {
-    return std::tie(n_ticks, mode, act, act_stride, rew, rew_stride, p_out) <
-           std::tie(o.n_ticks, o.mode, o.act, o.act_stride, o.rew, o.rew_stride, o.p_out);
+    return std::tie(n_ticks, mode, act, act_stride, rew, rew_stride, p_out, stats, row0) <
+           std::tie(o.n_ticks, o.mode, o.act, o.act_stride, o.rew, o.rew_stride, o.p_out, o.stats, o.row0);
   }
 };
 
@@ -84,6 +86,9 @@ struct mdr_ctx {
   double* d_wpen = nullptr;              // common-penalty windows: {sum pen/N, max pen} [kWindowMax][tiles_padded][2]
   size_t wpen_bytes = 0;
   double* d_wres = nullptr;              // their per-tick {sum, max} [kWindowMax][2], then signal terms [kWindowMax]
+  double* d_wstat = nullptr;             // closed-loop windows with stats rows: block partials [kWindowMax][grid][kStats]
+  size_t wstat_bytes = 0;                //   (allocated by the first mdr_rollout_stats, outside any capture)
+  double* d_stat_p = nullptr;            // mdr_rollout_stats per tick without a caller's p_out: the tick's P
   int pen_blocks = 0;
   // ---- options (mdr_set_option; defaults are the measured-fastest exact configuration)
   int tpw = 0;                           // MDR_OPT_STEP_TPW: k_step_pipe tiles per wave (0: k_step_t)
@@ -654,6 +659,8 @@ int mdr_destroy(mdr_ctx* c) {
   hipFree(c->d_partial2);
   hipFree(c->d_wpen);
   hipFree(c->d_wres);
+  hipFree(c->d_wstat);
+  hipFree(c->d_stat_p);
   hipFree(c->d_ticks);
   for (auto& e : c->ev)
     if (e) hipEventDestroy(e);
@@ -984,6 +991,22 @@ extern "C" int mdr_window_pen_check(int64_t n_local, size_t pen_bytes) {
   return MDR_OK;
 }
 
+// k_step_closed<..., STATS = true>: every block stores kStats doubles per tick of a window
+extern "C" size_t mdr_window_stats_bytes(int64_t n_local) {
+  if (n_local < 0) return 0;
+  const size_t tiles = ((size_t)n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
+  return (tiles + 3) / 4 * kWindowMax * kStats * sizeof(double);  // (a block holds 4 waves, a tile each)
+}
+
+extern "C" int mdr_window_stats_check(int64_t n_local, size_t bytes) {
+  if (n_local < 1) return fail(MDR_EARG, "window launch: no houses for the stats partial rows");
+  const size_t need = mdr_window_stats_bytes(n_local);
+  if (bytes < need)
+    return fail(MDR_EARG, "window launch: stats partial rows of " + std::to_string(bytes) +
+                              " B, the launch geometry writes " + std::to_string(need) + " B");
+  return MDR_OK;
+}
+
 // the finish of a common-penalty window of K ticks behind its k_step_window (stream order: the
 // kernel boundary publishes the step kernel's partials): per-tick {sum, max}, then the reward rows.
 // One shared row (rew_stride == 0): only the window's last tick is finalised.
@@ -1240,8 +1263,13 @@ static bool pipe_buffers(mdr_ctx* c) {
 // one slot serves every window: stream order puts the next window's adds behind it) and
 // k_closed_reward over the window's rows.  One shared row (rew_stride == 0): only the last window's
 // last tick is finalised.  Kernels only, so the sequence can be captured.
+// stats (mdr_rollout_stats): row t of the rollout goes to stats + t * kTickRow — the STATS
+// instantiation of k_step_closed (block partials per tick into d_wstat, checked against the launch
+// geometry first) and, last of the window, k_closed_stats over its K ticks.
 static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, double* reward, int64_t rew_stride,
-                           double* p_out, hipStream_t st) {
+                           double* p_out, hipStream_t st, double* stats = nullptr) {
+  if (stats && !c->d_wstat) return fail(MDR_ESTATE, "window launch: no stats partial rows");
+  double* const wstat = stats ? c->d_wstat : nullptr;
   const int nw = (n + c->win - 1) / c->win;
   const int base = n / nw, rem = n % nw;
   const KParams kp = c->kp;
@@ -1261,18 +1289,23 @@ static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, doub
       HIP_TRY(hipEventCreate(&e1));
       c->step_events->push_back(e1);
     }
-#define MDR_CLOSED(C)                                                                                          \
-  do {                                                                                                         \
-    if (e0)                                                                                                    \
-      hipExtLaunchKernelGGL((k_step_closed<C, kWinHpt>), dim3(grid), dim3(256), 0, st, e0, e1, 0, kp, tk + t0, K, r, \
-                            rew_stride, slot);                                                                 \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_step_closed<C, kWinHpt>), dim3(grid), dim3(256), 0, st, kp, tk + t0, K, r, rew_stride, \
-                         slot);                                                                                \
-  } while (0)
-    if (mode == MDR_ACT_BANGBANG) MDR_CLOSED(kActBangBang);
-    else MDR_CLOSED(kActDeadband);
-#undef MDR_CLOSED
+    // (extra: nothing, or the STATS instantiations' partial rows)
+    auto closed = [&](auto kernel, auto... extra) {
+      if (e0)
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, e0, e1, 0, kp, tk + t0, K, r, rew_stride, slot,
+                              extra...);
+      else
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, kp, tk + t0, K, r, rew_stride, slot, extra...);
+    };
+    if (stats) {  // (the partial rows this launch's geometry writes)
+      if (int rc = mdr_window_stats_check(kp.n, c->wstat_bytes)) return rc;
+      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, true, double*>, wstat);
+      else closed(k_step_closed<kActDeadband, kWinHpt, true, double*>, wstat);
+    } else if (mode == MDR_ACT_BANGBANG) {
+      closed(k_step_closed<kActBangBang, kWinHpt, false>);
+    } else {
+      closed(k_step_closed<kActDeadband, kWinHpt, false>);
+    }
     LAUNCH_CHECK("k_step_closed");
     hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot, K, tk + t0,
                        w == nw - 1 ? p_out : nullptr);
@@ -1283,20 +1316,36 @@ static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, doub
                          rew_stride);
       LAUNCH_CHECK("k_closed_reward");
     }
+    if (stats) {
+      hipLaunchKernelGGL(k_closed_stats, dim3(K), dim3(kTickBlock), 0, st, kp, (const double*)wstat, (int)grid, slot,
+                         stats + (size_t)t0 * kTickRow);
+      LAUNCH_CHECK("k_closed_stats");
+    }
     t0 += K;
   }
   c->wslab_dirty = false;
   return MDR_OK;
 }
 
+// (per-tick stats rows, defined with mdr_tick_stats below)
+static int check_tick_stats_ctx(mdr_ctx* c, const char* who);
+static int tick_scratch(mdr_ctx* c);
+static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* row,
+                             hipStream_t st);
+
 // The launch sequence of a rollout with staged drivers (d_ticks), so a captured graph is reusable:
 // the window sequence (open-loop sources), the closed-loop window sequence (bang-bang sources under
 // individual_L2), or one step launch per tick (+ phase 1 where no lookahead counts ahead).
+// stats (mdr_rollout_stats; never on the open-loop window sequence): row t -> stats + t * kTickRow,
+// by the closed-loop windows themselves, or per tick by mdr_tick_stats' two kernels behind the
+// tick's step (and its finalise kernels in the common penalty modes), every tick's P on the device.
 static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t act_stride, int mode,
-                            double* reward, int64_t rew_stride, double* p_out, hipStream_t st) {
+                            double* reward, int64_t rew_stride, double* p_out, hipStream_t st,
+                            double* stats = nullptr) {
   if (window_ok(c, mode))
     return window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, false, st);
-  if (closed_ok(c, mode)) return closed_launches(c, n, c->d_ticks, mode, reward, rew_stride, p_out, st);
+  if (closed_ok(c, mode)) return closed_launches(c, n, c->d_ticks, mode, reward, rew_stride, p_out, st, stats);
+  double* const p_tick = p_out ? p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
   if (int rc = zero_slabs(c, st)) return rc;
   c->ring = 0;
   const bool la = lookahead_ok(mode);
@@ -1315,7 +1364,7 @@ static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t ac
       HIP_TRY(hipEventRecord(e0, st));
     }
     int rc = launch_step(c, a, mode, TickArgs{}, c->d_ticks + t, r, la ? mode : 0, MDR_CTRL_NONE,
-                         nullptr, t == n - 1 ? p_out : nullptr, st);
+                         nullptr, stats ? p_tick : t == n - 1 ? p_out : nullptr, st);
     if (rc) return rc;
     if (win_common(c)) {  // step_tensor's common-penalty tail, the tick's drivers read from d_ticks
       hipLaunchKernelGGL(k_pen_reduce, dim3(1), dim3(256), 0, st, c->d_pen_partial, c->pen_blocks, c->d_partial2);
@@ -1325,6 +1374,8 @@ static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t ac
                          (const double*)c->d_partial2, r);
       LAUNCH_CHECK("k_reward_finalize");
     }
+    if (stats)  // the post-step state, this tick's reward row and P: mdr_tick_stats' launches
+      if (int rc2 = launch_tick_stats(c, r, p_tick, 0.0, stats + (size_t)t * kTickRow, st)) return rc2;
     if (c->step_events) {
       HIP_TRY(hipEventCreate(&e1));
       c->step_events->push_back(e1);
@@ -1340,16 +1391,54 @@ static bool consecutive(const mdr_tick* ticks, int n) {
   return true;
 }
 
-int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
-                int mode, double* reward, int64_t rew_stride, double* p_out, int use_graph, void* stream) {
-  if (!c || !ticks || !reward || n < 1) return fail(MDR_EARG, "mdr_rollout: bad argument");
+// the buffers a rollout with stats rows needs, allocated outside any capture: the closed-loop
+// windows' block partials, or the per-tick form's k_tick_stats partials and a P scalar
+static int rollout_stats_scratch(mdr_ctx* c, int mode, bool need_p) {
+  if (closed_ok(c, mode)) {
+    if (c->d_wstat) return MDR_OK;
+    const size_t bytes = mdr_window_stats_bytes(c->kp.n);
+    HIP_TRY(hipMalloc(&c->d_wstat, bytes));
+    c->wstat_bytes = bytes;
+    return MDR_OK;
+  }
+  if (need_p && !c->d_stat_p) HIP_TRY(hipMalloc(&c->d_stat_p, sizeof(double)));
+  return tick_scratch(c);
+}
+
+// who writes the stats rows of a rollout from this action source, or why nobody does
+static int rollout_stats_path(mdr_ctx* c, int mode, const std::string& who) {
+  if (int rc = check_tick_stats_ctx(c, who.c_str())) return rc;
+  if (window_ok(c, mode))
+    return fail(MDR_EARG, who + ": no stats rows from the open-loop window rollout (k_step_window); use the "
+                                "bang-bang sources, or mdr_set_rollout_window(0) for one launch per tick");
+  return closed_ok(c, mode) ? MDR_STATS_CLOSED_WINDOWS : MDR_STATS_PER_TICK;
+}
+
+int mdr_rollout_stats_path(mdr_ctx* c, int mode) {
+  if (!c) return fail(MDR_EARG, "mdr_rollout_stats_path: null ctx");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_stats_path: context not bound");
+  if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_stats_path: bad action source");
+  return rollout_stats_path(c, mode, "mdr_rollout_stats");
+}
+
+// mdr_rollout (stats == nullptr: its launches and graph keys) / mdr_rollout_stats
+static int rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
+                        int mode, double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
+                        int use_graph, void* stream, const char* who_c) {
+  const std::string who(who_c);
+  if (!c || !ticks || !reward || n < 1) return fail(MDR_EARG, who + ": bad argument");
   c->gq_keys_ready = false;
   c->fz_ready = false;
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout: context not bound");
-  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, "mdr_rollout: bad action source");
+  if (!c->bound) return fail(MDR_ESTATE, who + ": context not bound");
+  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, who + ": bad action source");
+  if (stats) {
+    if (row0 < 0) return fail(MDR_EARG, who + ": row0 < 0");
+    if (int rc = rollout_stats_path(c, mode, who); rc < 0) return rc;
+  }
   if (win_common(c) && (has_comm(c) || c->world > 1))  // (their mean / max penalty would be shard-local)
-    return fail(MDR_EARG, "mdr_rollout: common penalty modes on a sharded context need the per-step API");
+    return fail(MDR_EARG, who + ": common penalty modes on a sharded context need the per-step API");
   hipStream_t st = S(stream);
+  double* const srow = stats ? stats + (size_t)row0 * kTickRow : nullptr;
   const bool win = window_ok(c, mode);
   const bool consec = consecutive(ticks, n);
   // the first window counted ahead by mdr_rollout_begin for exactly this call?  (Its count took
@@ -1375,18 +1464,19 @@ int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
   }
   rc = stage_ticks(c, n, ticks, st);
   if (!rc) rc = wslab_clean(c, st);
+  if (!rc && stats) rc = rollout_stats_scratch(c, mode, !p_out);
   if (rc) return rc;
   if (!use_graph) {
-    rc = rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, st);
+    rc = rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, st, srow);
     c->counts_ready = false;
     return rc;
   }
-  GraphKey key{n, mode, action, act_stride, reward, rew_stride, p_out};
+  GraphKey key{n, mode, action, act_stride, reward, rew_stride, p_out, stats, stats ? row0 : 0};
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
     hipGraphExec_t ex;
     rc = capture_graph(c, [&](hipStream_t cs) {
-      return rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, cs);
+      return rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, cs, srow);
     }, &ex);
     if (rc) {
       c->wslab_dirty = true;
@@ -1396,12 +1486,25 @@ int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
   }
   if (hipGraphLaunch(it->second.first, st) != hipSuccess) {
     c->wslab_dirty = true;
-    return fail(MDR_EHIP, "mdr_rollout: hipGraphLaunch");
+    return fail(MDR_EHIP, who + ": hipGraphLaunch");
   }
   ++c->graph_launches[0];
   c->ring = it->second.second;
   c->counts_ready = false;
   return MDR_OK;
+}
+
+int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
+                int mode, double* reward, int64_t rew_stride, double* p_out, int use_graph, void* stream) {
+  return rollout_impl(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, nullptr, 0, use_graph, stream,
+                      "mdr_rollout");
+}
+
+int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
+                      int mode, double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
+                      int use_graph, void* stream) {
+  return rollout_impl(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, stats, row0, use_graph, stream,
+                      stats ? "mdr_rollout_stats" : "mdr_rollout");
 }
 
 // The first window's FSM counts (and its cluster power P) of an mdr_rollout of n ticks from tick

@@ -184,9 +184,13 @@ __global__ void k_win_reward_common(KParams p, const double* res, const double* 
 // controller -> FSM -> thermal update in registers, the raw pen_i to reward row j, the ticks' ON
 // counts into `slot` (this window's); k_win_reduce and k_closed_reward follow it.  Always the
 // reference's thermal expression (MDR_OPT_WINDOW_THERMAL does not apply).
-template <int CTRL, int HPT>
+// STATS: every block also stores, per tick of the window, its partial of the twelve k_tick_stats
+// values over the post-step state (slot 4: the sum of the raw pen_i) to wstat[tick][block][12];
+// k_closed_stats finishes the rows.  W: <double*> (wstat) with STATS, empty without (the kernel
+// arguments of the STATS = false instantiations are unchanged).
+template <int CTRL, int HPT, bool STATS = false, class... W>
 __global__ void k_step_closed(KParams p, const TickArgs* tkp, int K, double* reward, int64_t rew_stride,
-                              unsigned long long* slot);
+                              unsigned long long* slot, W... wstat);
 // reward rows j0 + blockIdx.y of a closed-loop window from their raw pen_i and the tick records
 __global__ void k_closed_reward(KParams p, const double* rec, int j0, double* reward, int64_t rew_stride);
 // k_reward_finalize with the tick's drivers in device memory (rollouts with staged drivers)
@@ -220,6 +224,9 @@ constexpr int kTickBlocks = 1024; // grid cap (as kStatsBlocks caps k_cluster_st
 template <bool HAS_R, bool VS, bool VR>
 __global__ void k_tick_stats(KParams p, const double* reward, double* partial);
 __global__ void k_tick_stats_finish(const double* partial, int nblk, const double* p_dev, double p_host, double* row);
+// the stats rows of a closed-loop window (mdr_rollout_stats): one block of kTickBlock threads per
+// tick, from k_step_closed<..., true>'s block partials and the window slot's counts and records
+__global__ void k_closed_stats(KParams p, const double* wstat, int nblk, unsigned long long* slot, double* rows);
 __global__ void k_obs(KParams p, ObsArgs o, const double* p_dev, float* obs);
 __global__ void k_halo_pack(KParams p, ObsArgs o, int lo, int hi, float* out);
 __global__ void k_halo_step_pack(KParams p, ObsArgs o, const uint8_t* action, const TickArgs* tkp, int lo, int hi,

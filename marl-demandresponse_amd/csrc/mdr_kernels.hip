@@ -7,6 +7,7 @@
 // no contraction on this path.
 #include "mdr_kernels.h"
 
+#include <tuple>
 #include <type_traits>
 
 #include "mdr_device.h"
@@ -1699,10 +1700,106 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
 // that differs in the last bits (MDR_THERMAL_AFFINE) could flip an action and fork the trajectory.
 // Bit-identical to the k_step_t loop with lookahead = the source: same operations in the same order
 // per house, P a sum of exact integer counts.
-template <int CTRL, int HPT>
+//
+// STATS: the window also leaves what a stats row of every tick needs (mdr_rollout_stats; the row
+// is finished by k_closed_stats).  The post-step T, T_mass and FSM word of tick j exist only in this
+// kernel's registers, so the row's values are formed here, per house with tick_acc's expressions
+// (e = T - tg / N, d = T - tg) over the houses the tile holds; a house it does not hold adds nothing.
+//   * slots 0, 1, 3, 5-8 and slot 4 (the raw pen_i: the tick's reward is not known yet): a lane adds
+//     its houses in slot order h = 0 .. HPT-1 from 0, then the wave reduces the eight sums:
+//       1. wave-private LDS transpose: lane l stores its sum k to tr[wave][k][l] (row stride
+//          kClosedTr = 68 doubles: the loads below then touch every bank pair at most twice);
+//       2. lane 8 k + q (k, q < 8) adds tr[wave][k][q], [q + 8], ..., [q + 56] in that order from 0;
+//       3. the eight parts of a sum: ((q0 + q1) + (q2 + q3)) + ((q4 + q5) + (q6 + q7)), three DPP
+//          exchanges (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror);
+//   * slot 2 (the max, from 0): a ninth transposed row, fmax over the same columns and exchanges;
+//   * slots 10 / 11 (lockout / ON counts): popcounts of the wave's ballots, scalar work, exact;
+//   * slot 9 (sum of the targets, the same every tick): once per window after the tick loop, lanes in
+//     slot order, then an xor butterfly (32, 16, ..., 1);
+//   * the wave's values go to ws[wave][tick][slot]; after the barrier that precedes win_flush the
+//     block adds its 4 waves in index order and stores one partial of kStats doubles per (tick, block)
+//     to wstat[tick][block][slot].  Every block stores all K rows of its window, so wstat is never
+//     cleared.
+// The order is fixed, so a row has the same bits on every run: no atomics, no block barrier inside
+// the tick loop.  The two STATS = false instantiations hold no statement of this: their code is the
+// parent's.
+constexpr int kClosedSums = 8;  // the transposed sums, in row order slots 0, 1, 3, 4, 5, 6, 7, 8
+constexpr int kClosedTr = 68;   // doubles per transposed row (64 lanes + 4 of padding)
+struct ClosedLds {
+  double tr[4][kClosedSums + 1][kClosedTr];  // [wave][sum | max][lane]
+  double ws[4][kWinMax][kStats];             // [wave][tick][slot]
+};
+__device__ __forceinline__ ClosedLds& closed_lds() {
+  __shared__ ClosedLds s;
+  return s;
+}
+template <bool STATS> struct ClosedAcc {};
+template <> struct ClosedAcc<true> {
+  double a[kClosedSums], mx;
+  uint32_t n_lock, n_on;  // wave-uniform
+};
+
+// one valid house of the tile after its step (tick_acc's expressions; pen: its raw penalty)
+__device__ __forceinline__ void closed_acc(ClosedAcc<true>& c, double T, double Tm, double tg, double pen, double N) {
+  const double e = T - tg / N;
+  const double d = T - tg;
+  c.a[0] += e;
+  c.a[1] += fabs(e);
+  c.mx = fmax(c.mx, e);
+  c.a[2] += e * e;
+  c.a[3] += pen;
+  c.a[4] += T;
+  c.a[5] += d;
+  c.a[6] += fabs(d);
+  c.a[7] += Tm;
+}
+
+// x of the lane a DPP control selects (two 32-bit v_mov_dpp; every lane of the wave is active here)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double x) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// tick j of the wave: the lanes' sums and max -> ws[wv][j][slot] (every slot but 9)
+__device__ __forceinline__ void closed_stats_tick(const ClosedAcc<true>& c, int wv, int lane, int j) {
+  ClosedLds& s = closed_lds();
+#pragma unroll
+  for (int k = 0; k < kClosedSums; ++k) s.tr[wv][k][lane] = c.a[k];
+  s.tr[wv][kClosedSums][lane] = c.mx;
+  wave_lds_sync();
+  const int k = lane >> 3, q = lane & 7;
+  double v = 0.0, m = 0.0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v += s.tr[wv][k][8 * i + q];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) m = fmax(m, s.tr[wv][kClosedSums][8 * i + q]);
+  // the eight parts, by DPP moves (no LDS round trip): lanes 1 and 2 apart inside a quad, then the
+  // other quad of the group of eight (row_half_mirror pairs lane q with 7 - q, which by then holds
+  // its quad's sum) — both lanes of a pair add the same two values, so all eight agree
+  v += dpp_f64<0xB1>(v);   // quad_perm [1, 0, 3, 2]
+  m = fmax(m, dpp_f64<0xB1>(m));
+  v += dpp_f64<0x4E>(v);   // quad_perm [2, 3, 0, 1]
+  m = fmax(m, dpp_f64<0x4E>(m));
+  v += dpp_f64<0x141>(v);  // row_half_mirror
+  m = fmax(m, dpp_f64<0x141>(m));
+  if (q == 0) s.ws[wv][j][k < 2 ? k : k + 1] = v;  // rows 0 .. 7 are slots 0, 1, 3, 4, 5, 6, 7, 8
+  if (lane == 0) {
+    s.ws[wv][j][2] = m;
+    s.ws[wv][j][10] = (double)c.n_lock;
+    s.ws[wv][j][11] = (double)c.n_on;
+  }
+  wave_lds_sync();  // (the next tick's stores to tr follow this tick's loads)
+}
+
+// (W: empty, or the one double* of a STATS launch — the other instantiations keep the parent's
+// kernel arguments, and with them the offsets of the implicit ones)
+template <int CTRL, int HPT, bool STATS, class... W>
 __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* __restrict__ tkp, int K,
                                                      double* __restrict__ reward, int64_t rew_stride,
-                                                     unsigned long long* __restrict__ slot) {
+                                                     unsigned long long* __restrict__ slot, W... wstat_arg) {
+  static_assert(sizeof...(W) == (STATS ? 1 : 0), "wstat rides only on a STATS launch");
   static_assert(CTRL == kActBangBang || CTRL == kActDeadband, "a bang-bang action source");
   __shared__ unsigned s_cnt[4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1765,6 +1862,13 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
     const bool store = rew_stride != 0 || j == K - 1;
     char* rrow = reinterpret_cast<char*>(reward + (int64_t)j * rew_stride);
     uint64_t on_m[HPT];
+    ClosedAcc<STATS> acc;
+    if constexpr (STATS) {
+#pragma unroll
+      for (int k = 0; k < kClosedSums; ++k) acc.a[k] = 0.0;
+      acc.mx = 0.0;
+      acc.n_lock = acc.n_on = 0u;
+    }
     auto houses = [&](auto fast_c) {
       constexpr bool F = decltype(fast_c)::value;
 #pragma unroll
@@ -1781,6 +1885,12 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
         Tm[h] = Tmn;
         const double pen = deadband_l2(tg[h], p.deadband, Tn);
         if (store && t.v[h]) __builtin_nontemporal_store(pen, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+        if constexpr (STATS) {  // the post-step state of tick j
+          if (t.v[h]) closed_acc(acc, Tn, Tmn, tg[h], pen, (double)p.n_global);
+          const uint64_t vm = __builtin_amdgcn_ballot_w64(t.v[h]);
+          acc.n_lock += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(hv_lock(w[h])) & vm);
+          acc.n_on += (uint32_t)__popcll(on_m[h] & vm);
+        }
       }
     };
     if (fast) houses(std::true_type());
@@ -1792,6 +1902,7 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
       for (int h = 0; h < HPT; ++h) k += (uint32_t)__popcll(on_m[h] & clm[h][c]);
       cnt_v[c] = writelane_u32(cnt_v[c], k, j);
     }
+    if constexpr (STATS) closed_stats_tick(acc, wv, lane, j);
   }
 
   // ---- state back, once per window
@@ -1807,14 +1918,37 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
 #pragma unroll
     for (int c = 0; c < kWinCap; ++c) s_cnt[wv][lane * kWinCap + c] = cnt_v[c];
   }
+  if constexpr (STATS) {  // slot 9 of the window's ticks: the tile's targets do not change
+    double g = 0.0;
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) g += t.v[h] ? tg[h] : 0.0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) g += __shfl_xor(g, off);
+    if (lane < K) closed_lds().ws[wv][lane][9] = g;
+  }
   __syncthreads();
   win_flush(p, K, s_cnt, slot);
+  if constexpr (STATS) {  // the block's partial of every tick: its 4 waves in index order
+    const ClosedLds& s = closed_lds();
+    double* __restrict__ wstat = std::get<0>(std::tuple<W...>(wstat_arg...));
+    for (int e = threadIdx.x; e < K * kStats; e += blockDim.x) {
+      const int j = e / kStats, k = e - j * kStats;
+      double v = s.ws[0][j][k];
+#pragma unroll
+      for (int r = 1; r < 4; ++r) v = k == 2 ? fmax(v, s.ws[r][j][k]) : v + s.ws[r][j][k];
+      wstat[((size_t)j * gridDim.x + blockIdx.x) * kStats + k] = v;
+    }
+  }
 }
 
-template __global__ void k_step_closed<kActBangBang, kWinHpt>(KParams, const TickArgs*, int, double*, int64_t,
-                                                              unsigned long long*);
-template __global__ void k_step_closed<kActDeadband, kWinHpt>(KParams, const TickArgs*, int, double*, int64_t,
-                                                              unsigned long long*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, false>(KParams, const TickArgs*, int, double*, int64_t,
+                                                                     unsigned long long*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, false>(KParams, const TickArgs*, int, double*, int64_t,
+                                                                     unsigned long long*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, true, double*>(KParams, const TickArgs*, int, double*,
+                                                                             int64_t, unsigned long long*, double*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, true, double*>(KParams, const TickArgs*, int, double*,
+                                                                             int64_t, unsigned long long*, double*);
 
 
 #define MDR_INST_WIN_C(A, SI, KA_, FO, CO)                                                                     \
@@ -2259,6 +2393,49 @@ __global__ void __launch_bounds__(kTickBlock) k_tick_stats_finish(const double* 
   if (k < kStats) row[k] = v;
   else if (k == kStats) row[k] = p_dev ? *p_dev : p_host;
   else if (k < kTickRow) row[k] = 0.0;
+}
+
+// Finish of a STATS window (behind k_step_closed<..., true>, k_win_reduce and k_closed_reward): one
+// block per tick j of the window writes stats row j of kTickRow doubles.  Thread t adds the block
+// partials wstat[j][t], [t + 256], ... in index order, then tick_block_reduce (the butterfly and wave
+// order of k_tick_stats_finish).  row[12] = the tick's P by win_power over the slot's reduced counts,
+// the value k_win_reduce used (the next window's reduce overwrites them: stream order puts this
+// kernel first).  row[4] = sum_i reward_i / N with the common factors taken out of the sum:
+// reward_i = -(alpha_temp pen_i [/ norm_temp] + sig), so from S = sum_i pen_i it is
+// -((alpha_temp S [/ norm_temp] + n sig) / N), whether or not the reward rows were finalised (a 1-D
+// reward buffer finalises only the rollout's last tick).
+__global__ void __launch_bounds__(kTickBlock) k_closed_stats(KParams p, const double* __restrict__ wstat, int nblk,
+                                                             unsigned long long* __restrict__ slot,
+                                                             double* __restrict__ rows) {
+  __shared__ double sh[kStats][4];
+  const int j = blockIdx.x, ncap = p.n_cap;
+  double a[kStats];
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+  const double* part = wstat + (size_t)j * nblk * kStats;
+  for (int b = threadIdx.x; b < nblk; b += kTickBlock)
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) {
+      const double o = part[(size_t)b * kStats + k];
+      a[k] = k == 2 ? fmax(a[k], o) : a[k] + o;
+    }
+  const double v = tick_block_reduce(a, sh);
+  double* row = rows + (size_t)j * kTickRow;
+  const int k = threadIdx.x;
+  if (k == 4) {
+    const double sig = -win_rec(slot, ncap)[j * kWinRec + 2];
+    const double tp = p.alpha_temp * v;
+    row[k] = -(((p.norm_temp == 1.0 ? tp : tp / p.norm_temp) + (double)p.n * sig) / (double)p.n_global);
+  } else if (k < kStats) {
+    row[k] = v;
+  } else if (k == kStats) {
+    double p_on[kWinCap];
+#pragma unroll
+    for (int c = 0; c < kWinCap; ++c) p_on[c] = p.p_on[c < ncap ? c : 0];
+    row[k] = win_power(p, win_red(slot, ncap) + j * ncap, p_on);
+  } else if (k < kTickRow) {
+    row[k] = 0.0;
+  }
 }
 
 // --------------------------------------------------------------------------------------- population

@@ -146,6 +146,8 @@ SIGNATURES = {
     "mdr_window_geometry_check": (I, [I64, C.c_size_t, C.c_size_t]),
     "mdr_window_pen_bytes": (C.c_size_t, [I64]),
     "mdr_window_pen_check": (I, [I64, C.c_size_t]),
+    "mdr_window_stats_bytes": (C.c_size_t, [I64]),
+    "mdr_window_stats_check": (I, [I64, C.c_size_t]),
     "mdr_time_step_kernels": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, P(C.c_float), P(I)]),
     "mdr_rollout_begin": (I, [VP, I, U64, VP, I64, I, VP]),
     "mdr_populate": (I, [VP, P(mdr_pop_spec), VP]),
@@ -156,6 +158,8 @@ SIGNATURES = {
     "mdr_penalty_buffer": (I, [VP, P(VP)]),
     "mdr_reward_finalize": (I, [VP, P(mdr_tick), VP, VP]),
     "mdr_rollout": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, I, VP]),  # ticks: const mdr_tick*
+    "mdr_rollout_stats": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP, I, I, VP]),
+    "mdr_rollout_stats_path": (I, [VP, I]),
     "mdr_msg_width": (I, [P(mdr_obs_spec)]),
     "mdr_obs": (I, [VP, P(mdr_obs_spec), P(mdr_obs_scalars), VP, VP, VP]),
     "mdr_halo_pack": (I, [VP, P(mdr_obs_spec), VP, VP]),

@@ -586,7 +586,7 @@ class Environment:
         return float(out.item())
 
     def rollout(self, n_ticks: int, actions=None, action_mode: str = "random", rewards=None,
-                use_graph: bool = False):
+                use_graph: bool = False, stats=None):
         """n_ticks steps in one C call.  ``actions``: uint8 [n_ticks, N] (buffer mode) or None;
         ``rewards``: float64 [n_ticks, N] output (allocated if None), or a 1-D [N] buffer that every
         tick overwrites.  Default (direct launches): the first window's count and its cluster power
@@ -603,7 +603,15 @@ class Environment:
         update in registers for up to 32 ticks, two short kernels finish each window's rewards),
         otherwise one step launch per tick inside the call; either way bit for bit the
         ``step_tensor(None, action_mode=c, lookahead=c)`` loop.  The drivers are staged first
-        (there is no early count to launch: every tick's ON set depends on the thermal state)."""
+        (there is no early count to launch: every tick's ON set depends on the thermal state).
+
+        ``stats`` (mdr_amd.services.RolloutStats, the contract of ``DeviceActor.rollout``): each tick's
+        row — the cluster statistics of the post-step state, its rewards and the cluster power — is
+        written inside the launch sequence (mdr_rollout_stats): by the closed-loop windows themselves
+        (k_step_closed<..., STATS> + k_closed_stats), or by mdr_tick_stats' kernels behind every tick
+        where the call runs one launch per tick.  The open-loop window rollout (random / always_on /
+        buffer with the window on) writes no rows: ``NotImplementedError``.  ``ValueError``: rows of
+        another env, or more ticks than the rows left."""
         import torch
 
         sh = self._shard
@@ -614,13 +622,24 @@ class Environment:
         if mode in (L.ACT_BANGBANG, L.ACT_DEADBAND_BANGBANG) and self._comm is not None:
             # (the window's cluster power would need an allreduce inside the closed-loop kernel's launch sequence)
             raise NotImplementedError("sharded bang-bang rollouts: use step_tensor(action_mode=..., lookahead=...)")
+        srow0 = 0
+        if stats is not None:
+            if stats.env is not self:
+                raise ValueError("the stats rows belong to another environment")
+            srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
+            try:  # which launch sequence would write the rows; nothing is launched
+                sh.rollout_stats_path(mode)
+            except L.MdrError as e:
+                if "MDR_EARG" in str(e):
+                    raise NotImplementedError(str(e)) from None
+                raise
         if rewards is None:
             rewards = torch.empty((n_ticks, self._n_local), dtype=torch.float64, device=sh.device)
         rew_stride = 0 if rewards.dim() == 1 else self._n_local  # 1-D: every tick overwrites it
         drivers_whole = self.power_grid.interp is None and self._links is not None  # one driver window
         native = self._comm is not None and getattr(self._comm, "native", False)
-        if (drivers_whole and not use_graph and (self._comm is None or native) and actions is None and n_ticks >= 2
-                and self._vector_drivers_ok() and _host is not None and _host_gauss_ok(self.rng)
+        if (stats is None and drivers_whole and not use_graph and (self._comm is None or native) and actions is None
+                and n_ticks >= 2 and self._vector_drivers_ok() and _host is not None and _host_gauss_ok(self.rng)
                 and not self._grid_pending):
             # one C call: mdr_rollout_begin, the host drivers, mdr_rollout / mdr_rollout_sharded (no
             # Python between them: r06, the sharded call's Python driver loop cost ~50 us a call)
@@ -637,7 +656,8 @@ class Environment:
             self.finish_grid_step()
             self._counts_ready = 0
             return rewards
-        if drivers_whole and not use_graph and (self._comm is None or getattr(self._comm, "native", False)):
+        if (stats is None and drivers_whole and not use_graph
+                and (self._comm is None or getattr(self._comm, "native", False))):
             # the first window's count (sharded: + its allreduce) and P, before the drivers exist
             sh.rollout_begin(n_ticks, self._tick, actions, self._n_local if actions is not None else 0, mode)
         done = 0
@@ -652,9 +672,18 @@ class Environment:
             else:
                 # graphs are cached per (length, buffers): shorter windows only reuse them on 1-D rewards
                 g = use_graph and (k == n_ticks or (a is None and not rew_stride))
-                sh.rollout(ticks, a, self._n_local if a is not None else 0, mode, r, rew_stride, g)
+                if stats is not None:
+                    if done == 0:
+                        stats.record_power(srow0)
+                    sh.rollout_stats(ticks, a, self._n_local if a is not None else 0, mode, r, rew_stride,
+                                     stats.stats, srow0 + done, g)
+                else:
+                    sh.rollout(ticks, a, self._n_local if a is not None else 0, mode, r, rew_stride, g)
             self._P_dev_valid = True
             self.finish_grid_step()
+            if stats is not None:  # tick t's post-step signal is tick t + 1's s_prev; the last one's is the grid's
+                post = list(ticks.s_prev[1:]) + [self.power_grid.current_signal]
+                stats.commit_rows(ticks.s_prev, ticks.t_od_prev, post, first=(done == 0))
             done += k
         self._counts_ready = 0
         return rewards
@@ -962,7 +991,7 @@ class Environment:
         # global random
         memo[id(self.rng)] = self.rng
         for k, v in self.__dict__.items():
-            if k in ("_shard", "cluster", "rng", "_comm", "_shard_factory"):
+            if k in ("_shard", "cluster", "rng", "_comm", "_shard_factory", "_eval_kept"):
                 continue
             new.__dict__[k] = copy.deepcopy(v, memo)
         new.rng, new._comm, new._shard_factory = self.rng, self._comm, self._shard_factory

@@ -233,7 +233,7 @@ class DeviceMAPPO:
         ``return_actions``: also the ticks' actions, uint8 [n_ticks, n_local]."""
         import copy
 
-        from .services import S_ABS_DIFF, S_POWER, S_REW, RolloutStats
+        from .services import RolloutStats, evaluation_means
 
         torch = _torch()
         if n_ticks < 1:
@@ -260,15 +260,7 @@ class DeviceMAPPO:
                 acts = kept["actions"] = torch.empty((n_ticks, ev.n_local), dtype=torch.uint8, device=ev.shard.device)
         # (one reward row, overwritten every tick: tick t's stats nodes read it before tick t + 1's step)
         kept["actor"].rollout(n_ticks, rewards=kept["rewards"], actions=acts, stats=stats)
-        rows, post = stats.host(), stats.prev()["signal_post"]
-        n = ev.n
-        ret = temp = sig = 0.0
-        for t in range(n_ticks):
-            ret += rows[t, S_REW]
-            temp += rows[t, S_ABS_DIFF] / n
-            sig += n * (np.abs(post[t] - rows[t, S_POWER]) / n ** 2)
-        out = {"Mean test return": float(ret / n_ticks), "Test mean temperature error": float(temp / n_ticks),
-               "Test mean signal error": float(sig / n_ticks)}
+        out = evaluation_means(stats.host(), stats.prev()["signal_post"], ev.n, n_ticks)
         return (out, acts) if return_actions else out
 
     def __len__(self) -> int:

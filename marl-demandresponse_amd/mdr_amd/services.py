@@ -12,6 +12,7 @@ per-house UI list is materialised only when read.
                  tick written inside a rollout: ``mdr_tick_stats``)  training_manager.py:242-245,265-295
   UISummary      ClientManagerService  server/app/services/client_manager_service.py:12-245
   ServerLoop     ControllerManager     server/app/services/controller_manager.py:93-260
+  evaluate_controller  TrainingManager.test for the bang-bang baselines  training_manager.py:265-295
 
 Floating-point sums over houses are reduced in a fixed blocked order on the device, where the
 reference adds house by house; they agree to rounding (tests/test_services_gpu.py: rtol 1e-12).
@@ -250,6 +251,61 @@ class DeviceMetrics:
                 "RMS Max Error temperature": self.rms_max_error_temp}
 
 
+def evaluation_means(rows, signal_post, n: int, n_ticks: int) -> dict:
+    """The three means TrainingManager.test logs (training_manager.py:265-295, metrics_service.py:
+    259-282) from the first ``n_ticks`` post-step stats rows and post-step signals of a cluster of
+    ``n`` houses:
+
+      "Mean test return"             sum_t sum_i reward_i / N / T
+      "Test mean temperature error"  sum_t sum_i |T_i - target_i| / N / T
+      "Test mean signal error"       sum_t N |s_post - P_post| / N^2 / T
+    """
+    ret = temp = sig = 0.0
+    for t in range(n_ticks):
+        ret += rows[t, S_REW]
+        temp += rows[t, S_ABS_DIFF] / n
+        sig += n * (np.abs(signal_post[t] - rows[t, S_POWER]) / n ** 2)
+    return {"Mean test return": float(ret / n_ticks), "Test mean temperature error": float(temp / n_ticks),
+            "Test mean signal error": float(sig / n_ticks)}
+
+
+BANGBANG_CONTROLLERS = ("bangbang", "deadband_bangbang")
+
+
+def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
+    """TrainingManager.test (training_manager.py:265-295) for a baseline controller, 'bangbang' or
+    'deadband_bangbang' (bangbang_controllers.py:25-65): the controller run for ``n_ticks`` on a reset
+    copy of ``env`` as ONE ``rollout(n_ticks, action_mode=controller, stats=...)`` — closed-loop windows
+    writing their own stats rows where they apply — and ``evaluation_means`` of the rows, the values
+    ``DeviceMAPPO.evaluate`` reports for a policy.  ``twin`` None: ``copy.deepcopy(env)`` as the
+    reference does; a caller-kept twin may be passed instead, whose context, row and reward buffers
+    and rollout graph are then reused by later calls.  The copy is ``reset`` (which advances the
+    shared RNG, as in the reference); ``env``'s device state, tick, date and P are not touched."""
+    import copy
+
+    import torch
+
+    if controller not in BANGBANG_CONTROLLERS:
+        raise ValueError(f"evaluate_controller: controller must be one of {BANGBANG_CONTROLLERS}, not {controller!r}")
+    if n_ticks < 1:
+        raise ValueError("n_ticks must be at least 1")
+    ev = copy.deepcopy(env) if twin is None else twin
+    if ev is env:
+        raise ValueError("evaluate_controller() resets its env: pass a copy as twin, not the env itself")
+    ev.reset(return_obs=False)
+    kept = getattr(ev, "_eval_kept", None) if twin is not None else None
+    if kept is None or kept["stats"].capacity != n_ticks:  # (a graph is cached per rollout length anyway)
+        kept = {"stats": RolloutStats(ev, n_ticks),
+                "rewards": torch.empty(ev.n_local, dtype=torch.float64, device=ev.shard.device)}
+        if twin is not None:
+            ev._eval_kept = kept  # (Environment.__deepcopy__ leaves it behind)
+    stats = kept["stats"]
+    stats.clear()
+    # (one reward row: the windows finalise only the last tick's rewards, the rows need none of them)
+    ev.rollout(n_ticks, action_mode=controller, rewards=kept["rewards"], use_graph=twin is not None, stats=stats)
+    return evaluation_means(stats.host(), stats.prev()["signal_post"], ev.n, n_ticks)
+
+
 def observe(env) -> dict:
     """The per-tick scalars every house's obs dict carries (environment.py:110-130)."""
     return {"reg_signal": env.power_grid.current_signal, "OD_temp": env.current_od_temp,
@@ -382,11 +438,19 @@ class ServerLoop:
     UI summary of the current obs -> actions -> env.step -> Metrics.update -> episode reset ->
     periodic log.  ``controller``: 'deadband_bangbang' / 'bangbang' / 'always_on' / 'random' (fused
     in the step kernel), 'greedy' (device GreedyMyopic), or a callable env -> uint8 device actions.
-    Per-house Python objects are only built on access (UISummary.houses_data)."""
+    Per-house Python objects are only built on access (UISummary.houses_data).
+    ``rollout_ticks`` = K > 0 (the two bang-bang controllers): ``run`` advances in chunks of up to K
+    ticks, each one rollout whose stats rows feed the Metrics, with one UI update per chunk."""
 
     def __init__(self, env, controller="deadband_bangbang", start_stats_from: int = 0, nb_time_steps: int = 1000,
                  time_steps_per_episode: int = 10 ** 9, time_steps_train_log: int = 10 ** 9, interface: bool = False,
-                 metrics=None, ui=None):
+                 metrics=None, ui=None, rollout_ticks: int = 0):
+        if rollout_ticks < 0:
+            raise ValueError("rollout_ticks must be >= 0")
+        if rollout_ticks and controller not in BANGBANG_CONTROLLERS:
+            raise ValueError(f"rollout_ticks needs one of the controllers {BANGBANG_CONTROLLERS}")
+        self.rollout_ticks = int(rollout_ticks)
+        self._rows = None  # RolloutStats of rollout_ticks rows + the chunks' one reward row
         self.env = env
         self.controller = controller
         self.metrics = metrics or DeviceMetrics()
@@ -410,8 +474,39 @@ class ServerLoop:
             return env.step_tensor(None, action_mode=c, lookahead=c)
         raise ValueError(f"unknown controller {c!r}")
 
+    def _run_chunks(self, end: int) -> None:
+        """``run``'s loop for ``rollout_ticks`` = K > 0: chunks of up to K ticks as one
+        ``env.rollout(k, action_mode=controller, stats=...)`` each, cut at episode ends, log
+        boundaries and ``end``; ``ui.update_data`` once at each chunk's start; Metrics from the
+        chunk's rows (``DeviceMetrics.update_rollout``: the per-tick arithmetic in its order)."""
+        import torch
+
+        env = self.env
+        if self._rows is None:
+            self._rows = (RolloutStats(env, self.rollout_ticks),
+                          torch.empty(env.n_local, dtype=torch.float64, device=env.shard.device))
+        stats, rewards = self._rows
+        ep, lg = self.time_steps_per_episode, self.time_steps_train_log
+        while self.current_time_step < end:
+            step = self.current_time_step
+            k = min(self.rollout_ticks, end - step, ep - step % ep, lg - step % lg)
+            self.ui.update_data(env, step)
+            stats.clear()
+            env.rollout(k, action_mode=self.controller, rewards=rewards, stats=stats)
+            self.metrics.update_rollout(stats, step)
+            last = step + k - 1
+            if last % ep == ep - 1:
+                env.reset(return_obs=False)
+            if last % lg == lg - 1:
+                self.logs.append(self.metrics.log(last, lg, env.date_time))
+                self.metrics.reset()
+            self.current_time_step += k
+
     def run(self, n_steps=None):
         end = self.nb_time_steps if n_steps is None else min(self.nb_time_steps, self.current_time_step + n_steps)
+        if self.rollout_ticks:
+            self._run_chunks(end)
+            end = self.current_time_step  # (the per-tick loop below has nothing left)
         for step in range(self.current_time_step, end):
             self.ui.update_data(self.env, step)
             prev = observe(self.env)

@@ -201,6 +201,25 @@ class HipShard:
                                      L.ptr(reward), rew_stride, L.ptr(self.p_dev), int(use_graph), self.stream()),
                 "mdr_rollout")
 
+    def rollout_stats(self, ticks, action, act_stride, mode, reward, rew_stride, stats, row0: int, use_graph=False):
+        """``rollout`` that also writes tick t's stats row into ``stats[row0 + t]`` (device float64
+        [rows, 16]) inside the same launch sequence (mdr_rollout_stats): the closed-loop windows of the
+        bang-bang sources form the rows themselves, the per-tick form appends mdr_tick_stats' kernels;
+        the open-loop window rollout is refused (MdrError, MDR_EARG)."""
+        if row0 < 0 or row0 + len(ticks) > stats.shape[0]:
+            raise ValueError(f"stats rows {row0} .. {row0 + len(ticks)} outside [0, {stats.shape[0]})")
+        L.check(self.lib.mdr_rollout_stats(self.ctx, len(ticks), ticks.ptr(), L.ptr(action), act_stride, mode,
+                                           L.ptr(reward), rew_stride, L.ptr(self.p_dev), L.ptr(stats), int(row0),
+                                           int(use_graph), self.stream()), "mdr_rollout_stats")
+
+    def rollout_stats_path(self, mode) -> int:
+        """mdr_rollout_stats_path: 1 (the closed-loop windows write the rows) or 2 (mdr_tick_stats'
+        kernels per tick); MdrError where mdr_rollout_stats would refuse.  Nothing is launched."""
+        rc = self.lib.mdr_rollout_stats_path(self.ctx, mode)
+        if rc < 0:
+            L.check(rc, "mdr_rollout_stats")
+        return rc
+
     def rollout_begin(self, n, tick0, action, act_stride, mode):
         """mdr_rollout_begin: the first window's count, launched before the host computes the drivers."""
         L.check(self.lib.mdr_rollout_begin(self.ctx, n, tick0, L.ptr(action), act_stride, mode, self.stream()),
