@@ -54,19 +54,41 @@ int fail(int code, const std::string& msg) {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
-struct GraphKey {
-  int n_ticks, mode;
-  const void* act;
+// the wave tiles (64 x kWinHpt houses) of a shard, and tiles rounded up to whole blocks of `waves`
+// waves (a tile per wave): the window kernels' grids and every buffer sized by them
+inline size_t win_tiles(int64_t n) { return ((size_t)n + 64 * kWinHpt - 1) / (64 * kWinHpt); }
+inline size_t whole_blocks(size_t tiles, int waves) { return (tiles + waves - 1) / waves * waves; }
+
+// n ticks as ceil(n / win) windows of near-equal size, the larger ones first
+struct WinPlan {
+  int nw, base, rem;
+  WinPlan(int n, int win) : nw((n + win - 1) / win), base(n / nw), rem(n % nw) {}
+  int count() const { return nw; }
+  int size(int w) const { return base + (w < rem ? 1 : 0); }
+  int start(int w) const { return w * base + (w < rem ? w : rem); }
+};
+
+// what every rollout entry point hands to its launch sequence
+struct RolloutArgs {
+  int n;
+  const uint8_t* action;
   int64_t act_stride;
-  void* rew;
+  int mode;
+  double* reward;
   int64_t rew_stride;
-  void* p_out;
-  void* stats = nullptr;  // mdr_rollout_stats: the rows' buffer and the first row (baked into the launches)
-  int row0 = 0;
-  bool operator<(const GraphKey& o) const {
-    return std::tie(n_ticks, mode, act, act_stride, rew, rew_stride, p_out, stats, row0) <
-           std::tie(o.n_ticks, o.mode, o.act, o.act_stride, o.rew, o.rew_stride, o.p_out, o.stats, o.row0);
+  double* p_out;
+  const uint8_t* act_row(int t) const { return action ? action + (int64_t)t * act_stride : nullptr; }
+  double* rew_row(int t) const { return reward + (int64_t)t * rew_stride; }
+};
+
+struct GraphKey {
+  RolloutArgs a;
+  void* stats;  // mdr_rollout_stats: the rows' buffer and the first row (baked into the launches)
+  int row0;
+  auto fields() const {
+    return std::tie(a.n, a.mode, a.action, a.act_stride, a.reward, a.rew_stride, a.p_out, stats, row0);
   }
+  bool operator<(const GraphKey& o) const { return fields() < o.fields(); }
 };
 
 }  // namespace
@@ -111,7 +133,7 @@ struct mdr_ctx {
   bool wslab_dirty = true;               // the slots' shard part must be zero when a rollout starts
   uint64_t* d_onb = nullptr;             // per-tick ON lane masks of the next window [tiles][HPT][kWindowMax]
   uint32_t* d_wah = nullptr;             // FSM word at the end of the next window, per house
-  uint64_t* d_onb2 = nullptr;            // second set for the count-ahead pipeline (window_launches pipe)
+  uint64_t* d_onb2 = nullptr;            // second set for the count-ahead pipeline (window_pipeline)
   uint32_t* d_wah2 = nullptr;
   size_t onb_bytes = 0, wah_bytes = 0;
   bool coef_dirty = true;
@@ -285,13 +307,13 @@ TickArgs to_tick(const mdr_tick* t) { return TickArgs{t->t_od_prev, t->solar, t-
 // ~1.5M houses per shard, 4 above
 int default_tpw(int64_t n) { return n <= 1572864 ? 2 : 4; }
 
-// phase 1 into the current slab
+// phase 1 into `slab` (nullptr: the current slab)
 int launch_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, const TickArgs* tkp,
-                  hipStream_t st) {
+                  hipStream_t st, unsigned long long* slab = nullptr) {
   static_assert(MDR_ACT_BANGBANG == kActBangBang && MDR_ACT_DEADBAND_BANGBANG == kActDeadband,
                 "the kernels take the bang-bang sources by their public ids");
   hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, action, mode,
-                     tick, tkp, slab_at(c, c->ring));
+                     tick, tkp, slab ? slab : slab_at(c, c->ring));
   LAUNCH_CHECK("k_power_counts");
   return MDR_OK;
 }
@@ -588,8 +610,7 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     // 64-house lane groups of every wave tile a count / step-window grid launches: the grids round
     // the tiles up to whole blocks (up to kCountWaves tiles per block), and the waves of a ragged
     // last block store and load the mask rows of their (empty) tiles too
-    const size_t tiles = ((size_t)cfg->n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
-    const size_t tiles64 = (tiles + kCountWaves) / kCountWaves * kCountWaves * kWinHpt + 1;
+    const size_t tiles64 = whole_blocks(win_tiles(cfg->n_local) + 1, kCountWaves) * kWinHpt + 1;
     c->onb_bytes = tiles64 * kWindowMax * sizeof(uint64_t);
     c->wah_bytes = ((size_t)cfg->n_local + 1) * sizeof(uint32_t);
     if (hipMalloc(&c->d_wslab, 3 * sizeof(unsigned long long) * c->wslab_len) != hipSuccess ||
@@ -957,12 +978,13 @@ static int wslab_clean(mdr_ctx* c, hipStream_t st) {
   return MDR_OK;
 }
 
-static unsigned win_grid(const mdr_ctx* c, int waves = 4) { return blocks(blocks(c->kp.n, 64 * kWinHpt), waves); }  // a tile per wave
+static unsigned win_grid(const mdr_ctx* c, int waves = 4) {  // a tile per wave
+  return (unsigned)(whole_blocks(win_tiles(c->kp.n), waves) / waves);
+}
 
 extern "C" size_t mdr_window_onb_bytes(int64_t n_local, int waves) {
   if (n_local < 0 || waves < 1) return 0;
-  const size_t tiles = ((size_t)n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
-  return (tiles + waves - 1) / waves * waves * kWinHpt * kWindowMax * sizeof(uint64_t);
+  return whole_blocks(win_tiles(n_local), waves) * kWinHpt * kWindowMax * sizeof(uint64_t);
 }
 
 extern "C" int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size_t wah_bytes) {
@@ -978,8 +1000,7 @@ extern "C" int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size
 
 extern "C" size_t mdr_window_pen_bytes(int64_t n_local) {
   if (n_local < 0) return 0;
-  const size_t tiles = ((size_t)n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
-  return (tiles + 3) / 4 * 4 * kWindowMax * 2 * sizeof(double);  // (step-window blocks hold 4 waves)
+  return whole_blocks(win_tiles(n_local), 4) * kWindowMax * 2 * sizeof(double);  // (step-window blocks hold 4 waves)
 }
 
 extern "C" int mdr_window_pen_check(int64_t n_local, size_t pen_bytes) {
@@ -994,8 +1015,7 @@ extern "C" int mdr_window_pen_check(int64_t n_local, size_t pen_bytes) {
 // k_step_closed<..., STATS = true>: every block stores kStats doubles per tick of a window
 extern "C" size_t mdr_window_stats_bytes(int64_t n_local) {
   if (n_local < 0) return 0;
-  const size_t tiles = ((size_t)n_local + 64 * kWinHpt - 1) / (64 * kWinHpt);
-  return (tiles + 3) / 4 * kWindowMax * kStats * sizeof(double);  // (a block holds 4 waves, a tile each)
+  return whole_blocks(win_tiles(n_local), 4) / 4 * kWindowMax * kStats * sizeof(double);  // (a block holds 4 waves, a tile each)
 }
 
 extern "C" int mdr_window_stats_check(int64_t n_local, size_t bytes) {
@@ -1011,7 +1031,7 @@ extern "C" int mdr_window_stats_check(int64_t n_local, size_t bytes) {
 // kernel boundary publishes the step kernel's partials): per-tick {sum, max}, then the reward rows.
 // One shared row (rew_stride == 0): only the window's last tick is finalised.
 static int win_pen_finish(mdr_ctx* c, int K, double* reward, int64_t rew_stride, hipStream_t st) {
-  const int ntile = (int)win_grid(c) * 4;
+  const int ntile = (int)whole_blocks(win_tiles(c->kp.n), 4);
   double *res = c->d_wres, *sig = c->d_wres + 2 * kWindowMax;
   const int j0 = rew_stride ? 0 : K - 1;
   hipLaunchKernelGGL(k_win_pen_reduce, dim3(K - j0), dim3(256), 0, st,
@@ -1023,18 +1043,29 @@ static int win_pen_finish(mdr_ctx* c, int K, double* reward, int64_t rew_stride,
   return MDR_OK;
 }
 
-// the first window's FSM count: ticks from tk (staged) or tick0 + j (tk == nullptr), from the
-// state's FSM words (w_in == nullptr) or from the end words of the previous window
-// p_only: the count kernel's last block also does the window's P-only reduce (win_reduce_last),
-// for a first window whose drivers ride on the step launch and whose shards need no allreduce
 // the reduced per-tick class counts of a window slot (after its kWindowMax x 64 x n_cap shards)
 static unsigned long long* win_red_ptr(const mdr_ctx* c, unsigned long long* slot) {
   return slot + (size_t)kWindowMax * kCountShards * c->kp.n_cap;
 }
 
+// a new event pair for one step launch while mdr_time_step_kernels measures (else null events)
+static int step_event_pair(mdr_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
+  *e0 = *e1 = nullptr;
+  if (!c->step_events) return MDR_OK;
+  HIP_TRY(hipEventCreate(e0));
+  c->step_events->push_back(*e0);
+  HIP_TRY(hipEventCreate(e1));
+  c->step_events->push_back(*e1);
+  return MDR_OK;
+}
+
+// a window's FSM count: ticks from tk (staged) or tick0 + j (tk == nullptr), from the
+// state's FSM words (w_in == nullptr) or from the end words of the previous window
+// p_only: the count kernel's last block also does the window's P-only reduce (win_reduce_last),
+// for a first window whose drivers ride on the step launch and whose shards need no allreduce
 static int launch_count(mdr_ctx* c, int mode, const uint8_t* action, int64_t act_stride, const TickArgs* tk,
                         uint64_t tick0, int K, unsigned long long* slot, uint64_t* onb, uint32_t* wah,
-                        const uint32_t* w_in, hipStream_t st, bool p_only = false) {
+                        const uint32_t* w_in, hipStream_t st, bool p_only) {
   if (int rc = mdr_window_geometry_check(c->kp.n, c->onb_bytes, c->wah_bytes)) return rc;
   const unsigned grid = win_grid(c, kCountWaves);
   unsigned* ticket = p_only ? c->d_tickets : nullptr;
@@ -1057,13 +1088,8 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
                               const WinDrv& dv, hipStream_t st) {
   if (int rc = mdr_window_geometry_check(c->kp.n, c->onb_bytes, c->wah_bytes)) return rc;
   const unsigned grid = win_grid(c);
-  hipEvent_t t0 = nullptr, t1 = nullptr;
-  if (c->step_events) {
-    HIP_TRY(hipEventCreate(&t0));
-    c->step_events->push_back(t0);
-    HIP_TRY(hipEventCreate(&t1));
-    c->step_events->push_back(t1);
-  }
+  hipEvent_t t0, t1;
+  if (int rc = step_event_pair(c, &t0, &t1)) return rc;
   const KParams kp = c->kp;
   // the common penalty modes: the COMMON variant (SIMPLE = false), its partial rows checked first
   const bool common = win_common(c);
@@ -1109,134 +1135,140 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
   return MDR_OK;
 }
 
-// n ticks as ceil(n / win) windows of near-equal size: a k_count_window for the first window, then
-// per window k_win_reduce (shard sums -> counts + tick records; sharded: the shards are allreduced
-// first) and one k_step_window (counting the next window's ticks).  Tick drivers come from tk
-// (device, staged) for every window.
-//
-// host_ticks (direct launches, mdr_rollout without a graph; ids consecutive, checked by the caller):
-// the first window's count and a P-only reduce (already issued by mdr_rollout_begin when counted)
-// need only the tick ids; its step kernel then takes the drivers as kernel arguments
-// (k_step_window<..., KA>), and the later windows' drivers are staged into tk behind it (their
-// first reader is the first step kernel's lookahead... which reads tick ids only: tick0 + K + j).
-//
-// pipe (sharded, comm stream present): the count-ahead pipeline.  The FSM of an open-loop source
-// needs no thermal state, so window w's count (from the FSM words at the end of window w-1) and
-// the allreduce of its counts run on the comm stream, up to two windows ahead of the compute
-// stream's reduce + step (which then has no lookahead): the allreduce latency hides behind the
-// step kernels.  Two sets of ON-mask / end-word buffers alternate; events order the reuse.
-static int window_launches(mdr_ctx* c, int n, const TickArgs* tk, const uint8_t* action, int64_t act_stride,
-                           int mode, double* reward, int64_t rew_stride, double* p_out, bool shd,
-                           hipStream_t st, bool counted = false, bool pipe = false,
-                           const mdr_tick* host_ticks = nullptr, bool ka_red = false) {
-  const int nw = (n + c->win - 1) / c->win;
-  const int base = n / nw, rem = n % nw;
-  auto wsz = [&](int w) { return base + (w < rem ? 1 : 0); };
-  auto slot = [&](int w) { return c->d_wslab + (size_t)(w % 3) * c->wslab_len; };
-  const KParams kp = c->kp;
-  const int ncap = kp.n_cap;
-  auto rec = [&](int w) {  // the slot's tick records, after its shards and reduced counts
-    return reinterpret_cast<const double*>(slot(w) + (size_t)kWindowMax * kCountShards * ncap + (size_t)kWindowMax * ncap);
-  };
-  // the common penalty modes: the cluster's per-tick mean / max penalty would need an allreduce
-  // inside the sequence (sharded contexts keep the per-step API)
-  const bool common = win_common(c);
-  if (common && (shd || pipe || ka_red))
-    return fail(MDR_EARG, "window launches: common penalty modes on a sharded context need the per-step API");
-  // the rows a later window overwrites are not finalised (one shared row: the last window's only)
-  auto finish = [&](int w, int K, int t0) {
-    if (!common || (!rew_stride && w + 1 < nw)) return (int)MDR_OK;
-    return win_pen_finish(c, K, reward + (int64_t)t0 * rew_stride, rew_stride, st);
-  };
-  c->wslab_dirty = true;  // until the sequence is fully issued
-  if (pipe) {
-    hipStream_t cs = c->comm_stream;
-    uint64_t* onbs[2] = {c->d_onb, c->d_onb2};
-    uint32_t* wahs[2] = {c->d_wah, c->d_wah2};
-    HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state and staged ticks, before the first count
-    HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
-    int t0 = 0;
-    for (int w = 0; w < nw; ++w) {
-      const int K = wsz(w);
-      // comm stream: count(w) + allreduce; count(w) reuses the buffers step(w - 2) read
-      if (w >= 2) HIP_TRY(hipStreamWaitEvent(cs, c->ev_k1[(w - 2) % kSlabs], 0));
-      const uint8_t* a = action ? action + (int64_t)t0 * act_stride : nullptr;
-      // (the count kernel's last block sums its shards: one allreduce of K x n_cap totals, <= 1 KiB)
-      if (int rc = launch_count(c, mode, a, act_stride, tk + t0, 0, K, slot(w), onbs[w % 2], wahs[w % 2],
-                                w == 0 ? nullptr : wahs[(w - 1) % 2], cs, true))
-        return rc;
+// ---- the open-loop window sequencers (window_launches, window_launches_direct,
+// window_pipeline).  Window w of the WinPlan counts into slot w % 3 of d_wslab; each sequencer sets
+// wslab_dirty before its first launch and clears it only once the last one is issued.
+struct WinSeq {  // the per-window pieces the three share
+  mdr_ctx* c;
+  const RolloutArgs& a;
+  hipStream_t st;
+  WinPlan plan;
+  const TickArgs* tk(int w) const { return c->d_ticks + plan.start(w); }
+  unsigned long long* slot(int w) const { return c->d_wslab + (size_t)(w % 3) * c->wslab_len; }
+  const double* rec(int w) const {  // the slot's tick records, after its shards and reduced counts
+    return reinterpret_cast<const double*>(win_red_ptr(c, slot(w)) + (size_t)kWindowMax * c->kp.n_cap);
+  }
+  double* p_out(int w) const { return w == plan.count() - 1 ? a.p_out : nullptr; }  // the rollout's last P
+  // window w's k_step_window, counting la ticks ahead into `next`; ka: the drivers as its arguments
+  int step(int w, int la, uint64_t* onb, uint32_t* wah, unsigned long long* next, const WinDrv* ka = nullptr) const {
+    static const WinDrv none{};
+    const int t0 = plan.start(w);
+    return launch_step_window(c, a.mode, ka != nullptr, a.act_row(t0), a.act_stride, tk(w), plan.size(w), la, rec(w),
+                              a.rew_row(t0), a.rew_stride, onb, wah, next, ka ? *ka : none, st);
+  }
+  // the common penalty modes' finish, unless a later window overwrites the one shared row
+  int finish(int w) const {
+    if (!win_common(c) || (!a.rew_stride && w + 1 < plan.count())) return MDR_OK;
+    return win_pen_finish(c, plan.size(w), a.rew_row(plan.start(w)), a.rew_stride, st);
+  }
+  // windows w0.. with staged drivers, each counted by its predecessor: k_win_reduce (shard sums ->
+  // counts + tick records) -> k_step_window -> finish.  shd: the ranks' count shards (exact
+  // integers, K x 64 x n_cap) are allreduced first, so the one reduce kernel yields global counts
+  int staged_windows(int w0, bool shd) const {
+    const int nw = plan.count(), ncap = c->kp.n_cap;
+    for (int w = w0; w < nw; ++w) {
+      const int K = plan.size(w);
       if (shd)
-        if (int rc = comm_allreduce(c, win_red_ptr(c, slot(w)), (size_t)K * ncap, 0, cs)) return rc;
-      HIP_TRY(hipEventRecord(c->ev_ar[w % kSlabs], cs));
-      // compute stream: the tick records + step (no lookahead)
-      HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[w % kSlabs], 0));
-      hipLaunchKernelGGL(k_win_records, dim3(1), dim3(kWindowMax), 0, st, kp, slot(w), K, tk + t0,
-                         w == nw - 1 ? p_out : nullptr);
-      LAUNCH_CHECK("k_win_records");
-      if (int rc = launch_step_window(c, mode, false, a, act_stride, tk + t0, K, 0, rec(w),
-                                      reward + (int64_t)t0 * rew_stride, rew_stride, onbs[w % 2], wahs[w % 2],
-                                      slot(w), WinDrv{}, st))
-        return rc;
-      HIP_TRY(hipEventRecord(c->ev_k1[w % kSlabs], st));
-      t0 += K;
+        if (int rc = comm_allreduce(c, slot(w), (size_t)K * kCountShards * ncap, 0, st)) return rc;
+      hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, c->kp, slot(w), K, tk(w), p_out(w));
+      LAUNCH_CHECK("k_win_reduce");
+      if (int rc = step(w, w + 1 < nw ? plan.size(w + 1) : 0, c->d_onb, c->d_wah, slot(w + 1))) return rc;
+      if (int rc = finish(w)) return rc;
     }
-    c->wslab_dirty = false;
     return MDR_OK;
   }
-  if (!counted) {  // (counted: mdr_rollout_begin launched the count and its P-only reduce already)
-    // host_ticks: the P-only reduce of the first window (the drivers come with the step) — in the
-    // count kernel's last block on one GPU, after the shards' allreduce when sharded
-    if (int rc = launch_count(c, mode, action, act_stride, host_ticks ? nullptr : tk,
-                              host_ticks ? host_ticks[0].tick : 0, wsz(0), slot(0), c->d_onb, c->d_wah, nullptr, st,
-                              host_ticks && !shd))
+};
+
+// (a sharded sequence would have to allreduce the cluster's per-tick mean / max penalty)
+static int win_common_unsharded(const mdr_ctx* c, bool shd) {
+  if (!win_common(c) || !shd) return MDR_OK;
+  return fail(MDR_EARG, "window launches: common penalty modes on a sharded context need the per-step API");
+}
+
+// The staged sequence: k_count_window for the first window, then staged_windows.  Tick drivers come
+// from d_ticks for every window.  Kernels only (unsharded), so a graph may capture it.
+static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream_t st) {
+  if (int rc = win_common_unsharded(c, shd)) return rc;
+  const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  if (int rc = launch_count(c, a.mode, a.action, a.act_stride, c->d_ticks, 0, s.plan.size(0), s.slot(0), c->d_onb,
+                            c->d_wah, nullptr, st, false))
+    return rc;
+  if (int rc = s.staged_windows(0, shd)) return rc;
+  c->wslab_dirty = false;
+  return MDR_OK;
+}
+
+enum FirstCounts {  // where the first window's per-tick counts of a direct sequence come from
+  kCountNow,        // counted here; the count kernel's last block does the P-only reduce
+  kBegun,           // the same launch, already issued by mdr_rollout_begin
+  kBegunAllreduced  // ... on a sharded context: P from the allreduced class totals (WinDrv::red)
+};
+
+// The direct sequence (ids consecutive, checked by the caller): the first window's count and P-only
+// reduce need only the tick ids; its step kernel then takes the drivers as kernel arguments
+// (k_step_window<..., KA>), and the later windows' drivers are staged into d_ticks behind it (their
+// first reader is the first step kernel's lookahead... which reads tick ids only: tick0 + K + j).
+static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_tick* host_ticks, FirstCounts first,
+                                  hipStream_t st) {
+  if (int rc = win_common_unsharded(c, first == kBegunAllreduced)) return rc;
+  const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
+  const int K = s.plan.size(0), nw = s.plan.count();
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  if (first == kCountNow)
+    if (int rc = launch_count(c, a.mode, a.action, a.act_stride, nullptr, host_ticks[0].tick, K, s.slot(0), c->d_onb,
+                              c->d_wah, nullptr, st, true))
       return rc;
-    if (host_ticks && shd)
-      if (int rc = comm_allreduce(c, slot(0), (size_t)wsz(0) * kCountShards * ncap, 0, st)) return rc;
-    if (host_ticks && shd) {
-      hipLaunchKernelGGL(k_win_reduce, dim3(wsz(0)), dim3(64 * ncap), 0, st, kp, slot(0), wsz(0),
-                         (const TickArgs*)nullptr, (double*)nullptr);
-      LAUNCH_CHECK("k_win_reduce (P only)");
-    }
+  WinDrv dv{};
+  for (int j = 0; j < K; ++j) {
+    const mdr_tick& h = host_ticks[j];
+    dv.od_k[j] = h.t_od_prev + 273.0;  // (k_win_reduce's rec[0]: the same IEEE addition)
+    dv.solar[j] = h.solar;
+    dv.s_prev[j] = h.s_prev;
+    if (fabs(h.t_od_prev) < 1048576.0 && fabs(h.solar) < 1099511627776.0) dv.ok |= 1u << j;  // (win_tick_record)
   }
-  int t0 = 0;
+  dv.tick0 = host_ticks[0].tick;
+  if (nw == 1) dv.p_out = a.p_out;
+  if (first == kBegunAllreduced) dv.red = win_red_ptr(c, s.slot(0));
+  if (int rc = s.step(0, nw > 1 ? s.plan.size(1) : 0, c->d_onb, c->d_wah, s.slot(1), &dv)) return rc;
+  if (int rc = s.finish(0)) return rc;
+  if (a.n > K)
+    if (int rc = stage_recs(host_ticks + K, a.n - K, c->d_ticks + K, st)) return rc;
+  if (int rc = s.staged_windows(1, false)) return rc;
+  c->wslab_dirty = false;
+  return MDR_OK;
+}
+
+// The count-ahead pipeline (sharded, comm stream present, drivers staged).  An open-loop source's FSM
+// needs no thermal state, so window w's count (from the end words of window w-1) and its allreduce
+// run on the comm stream, up to two windows ahead of the compute stream's tick records + step (no
+// lookahead): the allreduce hides behind the step kernels.  Two buffer sets alternate; events order them.
+static int window_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  if (int rc = win_common_unsharded(c, true)) return rc;
+  const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
+  const int nw = s.plan.count();
+  hipStream_t cs = c->comm_stream;
+  uint64_t* onbs[2] = {c->d_onb, c->d_onb2};
+  uint32_t* wahs[2] = {c->d_wah, c->d_wah2};
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state and staged ticks, before the first count
+  HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
   for (int w = 0; w < nw; ++w) {
-    const int K = wsz(w), la = w + 1 < nw ? wsz(w + 1) : 0;
-    const uint8_t* a = action ? action + (int64_t)t0 * act_stride : nullptr;
-    if (host_ticks && w == 0) {
-      // KA: the drivers ride on the step launch; the later windows' drivers are staged behind it
-      WinDrv dv{};
-      for (int j = 0; j < K; ++j) {
-        const mdr_tick& h = host_ticks[j];
-        dv.od_k[j] = h.t_od_prev + 273.0;  // (k_win_reduce's rec[0]: the same IEEE addition)
-        dv.solar[j] = h.solar;
-        dv.s_prev[j] = h.s_prev;
-        if (fabs(h.t_od_prev) < 1048576.0 && fabs(h.solar) < 1099511627776.0) dv.ok |= 1u << j;  // (win_tick_record)
-      }
-      dv.tick0 = host_ticks[0].tick;
-      if (nw == 1) dv.p_out = p_out;
-      if (ka_red) dv.red = win_red_ptr(c, slot(0));  // (sharded, begun: P from the allreduced totals)
-      if (int rc = launch_step_window(c, mode, true, a, act_stride, tk, K, la, rec(0), reward, rew_stride, c->d_onb,
-                                      c->d_wah, slot(1), dv, st))
-        return rc;
-      if (int rc = finish(0, K, 0)) return rc;
-      if (n > K)
-        if (int rc = stage_recs(host_ticks + K, n - K, const_cast<TickArgs*>(tk) + K, st)) return rc;
-      t0 += K;
-      continue;
-    }
-    // sharded: every rank's sharded per-tick class counts are summed first (exact integers; the
-    // slot's shard part, K x 64 x n_cap values), so one reduce kernel yields the global counts
-    if (shd)
-      if (int rc = comm_allreduce(c, slot(w), (size_t)K * kCountShards * ncap, 0, st)) return rc;
-    hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot(w), K, tk + t0,
-                       w == nw - 1 ? p_out : nullptr);
-    LAUNCH_CHECK("k_win_reduce");
-    if (int rc = launch_step_window(c, mode, false, a, act_stride, tk + t0, K, la, rec(w),
-                                    reward + (int64_t)t0 * rew_stride, rew_stride, c->d_onb, c->d_wah, slot(w + 1),
-                                    WinDrv{}, st))
+    const int K = s.plan.size(w);
+    // comm stream: count(w) + allreduce; count(w) reuses the buffers step(w - 2) read
+    if (w >= 2) HIP_TRY(hipStreamWaitEvent(cs, c->ev_k1[(w - 2) % kSlabs], 0));
+    // (the count kernel's last block sums its shards: one allreduce of K x n_cap totals, <= 1 KiB)
+    if (int rc = launch_count(c, a.mode, a.act_row(s.plan.start(w)), a.act_stride, s.tk(w), 0, K, s.slot(w),
+                              onbs[w % 2], wahs[w % 2], w == 0 ? nullptr : wahs[(w - 1) % 2], cs, true))
       return rc;
-    if (int rc = finish(w, K, t0)) return rc;
-    t0 += K;
+    if (int rc = comm_allreduce(c, win_red_ptr(c, s.slot(w)), (size_t)K * c->kp.n_cap, 0, cs)) return rc;
+    HIP_TRY(hipEventRecord(c->ev_ar[w % kSlabs], cs));
+    // compute stream: the tick records + step (no lookahead)
+    HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[w % kSlabs], 0));
+    hipLaunchKernelGGL(k_win_records, dim3(1), dim3(kWindowMax), 0, st, c->kp, s.slot(w), K, s.tk(w), s.p_out(w));
+    LAUNCH_CHECK("k_win_records");
+    if (int rc = s.step(w, 0, onbs[w % 2], wahs[w % 2], s.slot(w))) return rc;
+    HIP_TRY(hipEventRecord(c->ev_k1[w % kSlabs], st));
   }
   c->wslab_dirty = false;
   return MDR_OK;
@@ -1257,7 +1289,7 @@ static bool pipe_buffers(mdr_ctx* c) {
 }
 
 // n ticks of a bang-bang source as ceil(n / win) closed-loop windows of near-equal size
-// (window_launches' split), the drivers staged in tk.  Per window: k_step_closed (state in registers
+// (WinPlan), the drivers staged in d_ticks.  Per window: k_step_closed (state in registers
 // for the K ticks, raw pen_i to the reward rows, the ticks' ON counts into the count slot),
 // k_win_reduce (P and the signal penalty into the tick records; it zeroes the shards it sums, so the
 // one slot serves every window: stream order puts the next window's adds behind it) and
@@ -1266,29 +1298,24 @@ static bool pipe_buffers(mdr_ctx* c) {
 // stats (mdr_rollout_stats): row t of the rollout goes to stats + t * kTickRow — the STATS
 // instantiation of k_step_closed (block partials per tick into d_wstat, checked against the launch
 // geometry first) and, last of the window, k_closed_stats over its K ticks.
-static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, double* reward, int64_t rew_stride,
-                           double* p_out, hipStream_t st, double* stats = nullptr) {
+static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr) {
   if (stats && !c->d_wstat) return fail(MDR_ESTATE, "window launch: no stats partial rows");
   double* const wstat = stats ? c->d_wstat : nullptr;
-  const int nw = (n + c->win - 1) / c->win;
-  const int base = n / nw, rem = n % nw;
+  const WinPlan plan(a.n, c->win);
+  const int nw = plan.count(), mode = a.mode;
+  const int64_t rew_stride = a.rew_stride;
   const KParams kp = c->kp;
   const int ncap = kp.n_cap;
+  const TickArgs* const tk = c->d_ticks;
   unsigned long long* slot = c->d_wslab;
   const double* rec = reinterpret_cast<const double*>(win_red_ptr(c, slot) + (size_t)kWindowMax * ncap);
   const unsigned grid = win_grid(c);
   c->wslab_dirty = true;  // until the sequence is fully issued
-  int t0 = 0;
   for (int w = 0; w < nw; ++w) {
-    const int K = base + (w < rem ? 1 : 0);
-    double* r = reward + (int64_t)t0 * rew_stride;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->step_events) {
-      HIP_TRY(hipEventCreate(&e0));
-      c->step_events->push_back(e0);
-      HIP_TRY(hipEventCreate(&e1));
-      c->step_events->push_back(e1);
-    }
+    const int K = plan.size(w), t0 = plan.start(w);
+    double* r = a.rew_row(t0);
+    hipEvent_t e0, e1;
+    if (int rc = step_event_pair(c, &e0, &e1)) return rc;
     // (extra: nothing, or the STATS instantiations' partial rows)
     auto closed = [&](auto kernel, auto... extra) {
       if (e0)
@@ -1308,7 +1335,7 @@ static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, doub
     }
     LAUNCH_CHECK("k_step_closed");
     hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot, K, tk + t0,
-                       w == nw - 1 ? p_out : nullptr);
+                       w == nw - 1 ? a.p_out : nullptr);
     LAUNCH_CHECK("k_win_reduce");
     if (rew_stride || w == nw - 1) {
       const int j0 = rew_stride ? 0 : K - 1;
@@ -1321,7 +1348,6 @@ static int closed_launches(mdr_ctx* c, int n, const TickArgs* tk, int mode, doub
                          stats + (size_t)t0 * kTickRow);
       LAUNCH_CHECK("k_closed_stats");
     }
-    t0 += K;
   }
   c->wslab_dirty = false;
   return MDR_OK;
@@ -1339,32 +1365,24 @@ static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_d
 // stats (mdr_rollout_stats; never on the open-loop window sequence): row t -> stats + t * kTickRow,
 // by the closed-loop windows themselves, or per tick by mdr_tick_stats' two kernels behind the
 // tick's step (and its finalise kernels in the common penalty modes), every tick's P on the device.
-static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t act_stride, int mode,
-                            double* reward, int64_t rew_stride, double* p_out, hipStream_t st,
-                            double* stats = nullptr) {
-  if (window_ok(c, mode))
-    return window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, false, st);
-  if (closed_ok(c, mode)) return closed_launches(c, n, c->d_ticks, mode, reward, rew_stride, p_out, st, stats);
-  double* const p_tick = p_out ? p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
+static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr) {
+  const int n = a.n, mode = a.mode;
+  if (window_ok(c, mode)) return window_launches(c, a, false, st);
+  if (closed_ok(c, mode)) return closed_launches(c, a, st, stats);
+  double* const p_tick = a.p_out ? a.p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
   if (int rc = zero_slabs(c, st)) return rc;
   c->ring = 0;
   const bool la = lookahead_ok(mode);
   for (int t = 0; t < n; ++t) {
-    const uint8_t* a = action ? action + (int64_t)t * act_stride : nullptr;
-    double* r = reward + (int64_t)t * rew_stride;
-    if (!la || t == 0) {
-      hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, a, mode,
-                         (uint64_t)0, c->d_ticks + t, slab_at(c, c->ring));
-      LAUNCH_CHECK("k_power_counts");
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->step_events) {
-      HIP_TRY(hipEventCreate(&e0));
-      c->step_events->push_back(e0);
-      HIP_TRY(hipEventRecord(e0, st));
-    }
-    int rc = launch_step(c, a, mode, TickArgs{}, c->d_ticks + t, r, la ? mode : 0, MDR_CTRL_NONE,
-                         nullptr, stats ? p_tick : t == n - 1 ? p_out : nullptr, st);
+    const uint8_t* act = a.act_row(t);
+    double* r = a.rew_row(t);
+    if (!la || t == 0)
+      if (int rc = launch_counts(c, act, mode, 0, c->d_ticks + t, st)) return rc;
+    hipEvent_t e0, e1;  // (around the tick's group of launches, recorded on the stream)
+    if (int rc = step_event_pair(c, &e0, &e1)) return rc;
+    if (e0) HIP_TRY(hipEventRecord(e0, st));
+    int rc = launch_step(c, act, mode, TickArgs{}, c->d_ticks + t, r, la ? mode : 0, MDR_CTRL_NONE,
+                         nullptr, stats ? p_tick : t == n - 1 ? a.p_out : nullptr, st);
     if (rc) return rc;
     if (win_common(c)) {  // step_tensor's common-penalty tail, the tick's drivers read from d_ticks
       hipLaunchKernelGGL(k_pen_reduce, dim3(1), dim3(256), 0, st, c->d_pen_partial, c->pen_blocks, c->d_partial2);
@@ -1376,11 +1394,7 @@ static int rollout_launches(mdr_ctx* c, int n, const uint8_t* action, int64_t ac
     }
     if (stats)  // the post-step state, this tick's reward row and P: mdr_tick_stats' launches
       if (int rc2 = launch_tick_stats(c, r, p_tick, 0.0, stats + (size_t)t * kTickRow, st)) return rc2;
-    if (c->step_events) {
-      HIP_TRY(hipEventCreate(&e1));
-      c->step_events->push_back(e1);
-      HIP_TRY(hipEventRecord(e1, st));
-    }
+    if (e1) HIP_TRY(hipEventRecord(e1, st));
   }
   return MDR_OK;
 }
@@ -1421,63 +1435,83 @@ int mdr_rollout_stats_path(mdr_ctx* c, int mode) {
   return rollout_stats_path(c, mode, "mdr_rollout_stats");
 }
 
-// mdr_rollout (stats == nullptr: its launches and graph keys) / mdr_rollout_stats
-static int rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
-                        int mode, double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
-                        int use_graph, void* stream, const char* who_c) {
-  const std::string who(who_c);
-  if (!c || !ticks || !reward || n < 1) return fail(MDR_EARG, who + ": bad argument");
+// a common penalty mode on a sharded context: its mean / max penalty would be shard-local
+static bool common_sharded(const mdr_ctx* c) { return win_common(c) && (has_comm(c) || c->world > 1); }
+
+// The argument checks the rollout entry points share, in the order a call with several faults
+// reports them.  ptrs: the entry point's own pointer arguments are there.
+enum {
+  kDropBegun = 1,    // discard an early count once the arguments are there (the others settle it themselves)
+  kShardedOnly = 2,  // mdr_rollout_sharded: a communicator, no bang-bang source
+  kNoCommon = 4      // no common penalty mode (mdr_rollout / mdr_rollout_begin decide behind the preamble)
+};
+static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const RolloutArgs& a, int flags) {
+  if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
+  if (flags & kDropBegun) drop_begun(c);
   c->gq_keys_ready = false;
   c->fz_ready = false;
-  if (!c->bound) return fail(MDR_ESTATE, who + ": context not bound");
-  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, who + ": bad action source");
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if ((flags & kShardedOnly) && !has_comm(c))
+    return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
+  if (!check_mode(a.mode) || (a.mode == MDR_ACT_BUFFER && !a.action))
+    return fail(MDR_EARG, std::string(who) + ": bad action source");
+  if ((flags & kShardedOnly) && (a.mode == MDR_ACT_BANGBANG || a.mode == MDR_ACT_DEADBAND_BANGBANG))
+    return fail(MDR_EARG, std::string(who) + ": bang-bang sources need the per-step API");
+  if ((flags & kNoCommon) && win_common(c)) return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
+  return MDR_OK;
+}
+
+// The first window counted ahead by mdr_rollout_begin for exactly this call?  (Its count took the
+// ids tick0 + j and its P-only reduce consumed the slot's shards: only the direct sequence can follow
+// it, whatever use_graph asks.)  sharded: a single window, its counts allreduced already.
+static bool begun_matches(const mdr_ctx* c, const RolloutArgs& a, const mdr_tick* ticks, bool sharded) {
+  const auto& b = c->begun;
+  return b.on && b.sharded == sharded && b.n == a.n && b.mode == a.mode && b.tick0 == ticks[0].tick &&
+         b.action == a.action && b.act_stride == a.act_stride && (!sharded || (has_comm(c) && a.n <= c->win)) &&
+         window_ok(c, a.mode) && consecutive(ticks, a.n);
+}
+
+// (stats == nullptr: mdr_rollout, its launches and graph keys)
+int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
+                      int mode, double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
+                      int use_graph, void* stream) {
+  const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, p_out};
+  const char* const who = stats ? "mdr_rollout_stats" : "mdr_rollout";
+  if (int rc = rollout_preamble(c, who, ticks && a.reward, a, 0)) return rc;
   if (stats) {
-    if (row0 < 0) return fail(MDR_EARG, who + ": row0 < 0");
-    if (int rc = rollout_stats_path(c, mode, who); rc < 0) return rc;
+    if (row0 < 0) return fail(MDR_EARG, std::string(who) + ": row0 < 0");
+    if (int rc = rollout_stats_path(c, a.mode, who); rc < 0) return rc;
   }
-  if (win_common(c) && (has_comm(c) || c->world > 1))  // (their mean / max penalty would be shard-local)
-    return fail(MDR_EARG, who + ": common penalty modes on a sharded context need the per-step API");
+  if (common_sharded(c))
+    return fail(MDR_EARG, std::string(who) + ": common penalty modes on a sharded context need the per-step API");
   hipStream_t st = S(stream);
   double* const srow = stats ? stats + (size_t)row0 * kTickRow : nullptr;
-  const bool win = window_ok(c, mode);
-  const bool consec = consecutive(ticks, n);
-  // the first window counted ahead by mdr_rollout_begin for exactly this call?  (Its count took
-  // the ids tick0 + j and its P-only reduce consumed the slot's shards: only the direct sequence
-  // with the drivers as kernel arguments can follow it, whatever use_graph asks.)
-  const bool counted = c->begun.on && !c->begun.sharded && c->begun.n == n && c->begun.mode == mode &&
-                       c->begun.tick0 == ticks[0].tick && c->begun.action == action &&
-                       c->begun.act_stride == act_stride && win && consec;
+  const bool counted = begun_matches(c, a, ticks, false);
   if (c->begun.on && !counted) c->wslab_dirty = true;  // an unmatched early count: clear its shards
   c->begun.on = false;
   int rc = refresh_if_dirty(c, st);
   if (rc) return rc;
-  if (counted || (win && !use_graph && consec)) {
-    // direct launches of the windowed path: the first window's drivers travel as kernel arguments
-    // of its step kernel (window_launches host_ticks)
-    rc = ensure_ticks(c, n);
+  if (counted || (!use_graph && window_ok(c, a.mode) && consecutive(ticks, a.n))) {
+    rc = ensure_ticks(c, a.n);
     if (!rc) rc = wslab_clean(c, st);
-    if (!rc)
-      rc = window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, false, st, counted,
-                           false, ticks);
+    if (!rc) rc = window_launches_direct(c, a, ticks, counted ? kBegun : kCountNow, st);
     c->counts_ready = false;
     return rc;
   }
-  rc = stage_ticks(c, n, ticks, st);
+  rc = stage_ticks(c, a.n, ticks, st);
   if (!rc) rc = wslab_clean(c, st);
-  if (!rc && stats) rc = rollout_stats_scratch(c, mode, !p_out);
+  if (!rc && stats) rc = rollout_stats_scratch(c, a.mode, !a.p_out);
   if (rc) return rc;
   if (!use_graph) {
-    rc = rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, st, srow);
+    rc = rollout_launches(c, a, st, srow);
     c->counts_ready = false;
     return rc;
   }
-  GraphKey key{n, mode, action, act_stride, reward, rew_stride, p_out, stats, stats ? row0 : 0};
+  const GraphKey key{a, stats, stats ? row0 : 0};
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
     hipGraphExec_t ex;
-    rc = capture_graph(c, [&](hipStream_t cs) {
-      return rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, p_out, cs, srow);
-    }, &ex);
+    rc = capture_graph(c, [&](hipStream_t cs) { return rollout_launches(c, a, cs, srow); }, &ex);
     if (rc) {
       c->wslab_dirty = true;
       return rc;
@@ -1486,7 +1520,7 @@ static int rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
   }
   if (hipGraphLaunch(it->second.first, st) != hipSuccess) {
     c->wslab_dirty = true;
-    return fail(MDR_EHIP, who + ": hipGraphLaunch");
+    return fail(MDR_EHIP, std::string(who) + ": hipGraphLaunch");
   }
   ++c->graph_launches[0];
   c->ring = it->second.second;
@@ -1496,15 +1530,7 @@ static int rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
 
 int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
                 int mode, double* reward, int64_t rew_stride, double* p_out, int use_graph, void* stream) {
-  return rollout_impl(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, nullptr, 0, use_graph, stream,
-                      "mdr_rollout");
-}
-
-int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
-                      int mode, double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
-                      int use_graph, void* stream) {
-  return rollout_impl(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, stats, row0, use_graph, stream,
-                      stats ? "mdr_rollout_stats" : "mdr_rollout");
+  return mdr_rollout_stats(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, nullptr, 0, use_graph, stream);
 }
 
 // The first window's FSM counts (and its cluster power P) of an mdr_rollout of n ticks from tick
@@ -1514,11 +1540,8 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
 // temporally blocked path.
 int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, int64_t act_stride, int mode,
                       void* stream) {
-  if (!c || n < 1) return fail(MDR_EARG, "mdr_rollout_begin: bad argument");
-  c->gq_keys_ready = false;
-  c->fz_ready = false;
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_begin: context not bound");
-  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, "mdr_rollout_begin: bad action source");
+  const RolloutArgs a{n, action, act_stride, mode, nullptr, 0, nullptr};
+  if (int rc = rollout_preamble(c, "mdr_rollout_begin", true, a, 0)) return rc;
   if (c->begun.on) c->wslab_dirty = true;  // a previous early count that no rollout consumed
   c->begun.on = false;
   if (!window_ok(c, mode)) return MDR_OK;
@@ -1526,13 +1549,12 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
   // the matching mdr_rollout_sharded launches just the KA step kernel
   const bool sharded = has_comm(c);
   if (sharded && n > c->win) return MDR_OK;
-  if (win_common(c) && (sharded || c->world > 1)) return MDR_OK;  // (mdr_rollout / _sharded refuse these)
+  if (common_sharded(c)) return MDR_OK;  // (mdr_rollout / _sharded refuse these)
   hipStream_t st = S(stream);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = wslab_clean(c, st);
   if (rc) return rc;
-  const int nw = (n + c->win - 1) / c->win;
-  const int k0 = n / nw + (n % nw ? 1 : 0);  // window_launches' first window
+  const int k0 = WinPlan(n, c->win).size(0);
   c->wslab_dirty = true;
   // the window's P (the counts need no drivers): the matching direct mdr_rollout then launches the
   // step kernel with the drivers as arguments (k_step_window<..., KA>), nothing in between — on one
@@ -1545,10 +1567,7 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
     if (int rc2 = comm_allreduce(c, win_red_ptr(c, c->d_wslab), (size_t)k0 * c->kp.n_cap, 0, st)) return rc2;
   }
   c->wslab_dirty = false;
-  c->begun.sharded = sharded;
-  c->begun.on = true;
-  c->begun.n = n; c->begun.mode = mode; c->begun.tick0 = tick0;
-  c->begun.action = action; c->begun.act_stride = act_stride;
+  c->begun = {true, n, mode, tick0, action, act_stride, sharded};
   return MDR_OK;
 }
 
@@ -1558,13 +1577,9 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
 // event.
 int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
                           int mode, double* reward, int64_t rew_stride, void* stream, float* ms, int* launches) {
-  drop_begun(c);
-  if (!c || !ticks || !reward || !ms || !launches || n < 1) return fail(MDR_EARG, "mdr_time_step_kernels: bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_time_step_kernels: context not bound");
-  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
-    return fail(MDR_EARG, "mdr_time_step_kernels: bad action source");
-  if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, "mdr_time_step_kernels: common penalty modes need the per-step API");
+  drop_begun(c);  // (a refused call discards an early count too)
+  const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, nullptr};
+  if (int rc = rollout_preamble(c, "mdr_time_step_kernels", ticks && reward && ms && launches, a, kNoCommon)) return rc;
   hipStream_t st = S(stream);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = stage_ticks(c, n, ticks, st);
@@ -1572,7 +1587,7 @@ int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_
   if (rc) return rc;
   std::vector<hipEvent_t> evs;
   c->step_events = &evs;
-  rc = rollout_launches(c, n, action, act_stride, mode, reward, rew_stride, nullptr, st);
+  rc = rollout_launches(c, a, st);
   c->step_events = nullptr;
   c->counts_ready = false;
   float total = 0.0f;
@@ -2273,14 +2288,13 @@ namespace {
 //                   slab (t-1)%4, lookahead counts of t+1 into slab (t+1)%4, zero slab (t+2)%4
 //   comm stream     allreduce(slab t%4) once K(t-1) has filled it — concurrent with K(t)
 // K(t+1) waits for allreduce(t); after the loop k_reward_state writes the last tick's reward.
-int rollout_sharded_overlap(mdr_ctx* c, const TickArgs* ticks, int n, int mode, double* reward,
-                            int64_t rew_stride, double* p_out, hipStream_t st) {
+int rollout_sharded_overlap(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  const TickArgs* ticks = c->d_ticks;
+  const int n = a.n, mode = a.mode;
   hipStream_t cs = c->comm_stream;
   auto slab = [&](int t) { return c->d_slab + (size_t)(t % kSlabs) * c->slab_len; };
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, nullptr,
-                     mode, (uint64_t)0, ticks, slab(0));
-  LAUNCH_CHECK("k_power_counts");
+  if (int rc = launch_counts(c, nullptr, mode, 0, ticks, st, slab(0))) return rc;
   HIP_TRY(hipEventRecord(c->ev_pc, st));
   for (int t = 0; t < n; ++t) {
     // comm stream: counts of tick t are complete once K(t-1) (or phase 1) has finished
@@ -2289,16 +2303,15 @@ int rollout_sharded_overlap(mdr_ctx* c, const TickArgs* ticks, int n, int mode, 
     HIP_TRY(hipEventRecord(c->ev_ar[t % kSlabs], cs));
     // compute stream: K(t) needs the allreduced counts of tick t-1 for that tick's reward
     if (t >= 1) HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(t - 1) % kSlabs], 0));
-    int rc = launch_step_on(c, nullptr, mode, TickArgs{}, ticks + t,
-                            t >= 1 ? reward + (int64_t)(t - 1) * rew_stride : reward, mode, MDR_CTRL_NONE,
-                            nullptr, nullptr, t >= 1 ? slab(t - 1) : nullptr, slab(t + 1), slab(t + 2),
-                            1, st);
+    int rc = launch_step_on(c, nullptr, mode, TickArgs{}, ticks + t, a.rew_row(t >= 1 ? t - 1 : 0), mode,
+                            MDR_CTRL_NONE, nullptr, nullptr, t >= 1 ? slab(t - 1) : nullptr, slab(t + 1),
+                            slab(t + 2), 1, st);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev_k1[t % kSlabs], st));
   }
   HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(n - 1) % kSlabs], 0));
   hipLaunchKernelGGL(k_reward_state, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp,
-                     ticks + (n - 1), slab(n - 1), reward + (int64_t)(n - 1) * rew_stride, p_out);
+                     ticks + (n - 1), slab(n - 1), a.rew_row(n - 1), a.p_out);
   LAUNCH_CHECK("k_reward_state");
   // leave the step path's invariant (slab ring+1 zero) behind
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
@@ -2308,22 +2321,18 @@ int rollout_sharded_overlap(mdr_ctx* c, const TickArgs* ticks, int n, int mode, 
 }
 
 // Serial sharded ticks on one stream: [phase 1 if needed] -> allreduce(counts) -> k_step.
-int rollout_sharded_serial(mdr_ctx* c, const TickArgs* ticks, int n, const uint8_t* action,
-                           int64_t act_stride, int mode, double* reward, int64_t rew_stride,
-                           double* p_out, hipStream_t st) {
+int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  const TickArgs* ticks = c->d_ticks;
+  const int n = a.n, mode = a.mode;
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
   c->ring = 0;
   const bool la = lookahead_ok(mode);
   for (int t = 0; t < n; ++t) {
-    const uint8_t* a = action ? action + (int64_t)t * act_stride : nullptr;
-    if (!la || t == 0) {
-      hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, a, mode,
-                         (uint64_t)0, ticks + t, slab_at(c, c->ring));
-      LAUNCH_CHECK("k_power_counts");
-    }
+    if (!la || t == 0)
+      if (int rc = launch_counts(c, a.act_row(t), mode, 0, ticks + t, st)) return rc;
     if (int rc = comm_allreduce(c, slab_at(c, c->ring), c->slab_len, 0, st)) return rc;
-    int rc = launch_step(c, a, mode, TickArgs{}, ticks + t, reward + (int64_t)t * rew_stride,
-                         la ? mode : 0, MDR_CTRL_NONE, nullptr, t == n - 1 ? p_out : nullptr, st);
+    int rc = launch_step(c, a.act_row(t), mode, TickArgs{}, ticks + t, a.rew_row(t), la ? mode : 0, MDR_CTRL_NONE,
+                         nullptr, t == n - 1 ? a.p_out : nullptr, st);
     if (rc) return rc;
   }
   c->counts_ready = false;
@@ -2337,30 +2346,22 @@ extern "C" {
 int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
                         int64_t act_stride, int mode, double* reward, int64_t rew_stride, double* p_out,
                         void* stream) {
-  if (!c || !ticks || !reward || n < 1) return fail(MDR_EARG, "mdr_rollout_sharded: bad argument");
+  const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, p_out};
   // a single window begun by mdr_rollout_begin on this sharded context (count, allreduce, P-only
-  // reduce already issued): only the KA step kernel is left, with these drivers as its arguments
-  if (c->begun.on && c->begun.sharded && has_comm(c) && c->begun.n == n && c->begun.mode == mode &&
-      c->begun.tick0 == ticks[0].tick && c->begun.action == action && c->begun.act_stride == act_stride &&
-      window_ok(c, mode) && n <= c->win && consecutive(ticks, n)) {
+  // reduce already issued): only the KA step kernel is left, with these drivers as its arguments.
+  // (Such a call passes every check of the preamble: mdr_rollout_begin made them.)
+  const bool begun = c && ticks && n >= 1 && begun_matches(c, a, ticks, true);
+  if (int rc = rollout_preamble(c, "mdr_rollout_sharded", ticks && reward, a,
+                                (begun ? 0 : kDropBegun) | kShardedOnly | kNoCommon))
+    return rc;
+  hipStream_t st = S(stream);
+  if (begun) {
     c->begun.on = false;
-    hipStream_t st = S(stream);
     int rc = ensure_ticks(c, n);
-    if (!rc)
-      rc = window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, false, st, true,
-                           false, ticks, true);
+    if (!rc) rc = window_launches_direct(c, a, ticks, kBegunAllreduced, st);
     c->counts_ready = false;
     return rc;
   }
-  drop_begun(c);
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_sharded: context not bound");
-  if (!has_comm(c)) return fail(MDR_ESTATE, "mdr_rollout_sharded: no communicator (mdr_rccl_init / mdr_comm_host)");
-  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action)) return fail(MDR_EARG, "mdr_rollout_sharded: bad action source");
-  if (mode == MDR_ACT_BANGBANG || mode == MDR_ACT_DEADBAND_BANGBANG)
-    return fail(MDR_EARG, "mdr_rollout_sharded: bang-bang sources need the per-step API");
-  if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, "mdr_rollout_sharded: common penalty modes need the per-step API");
-  hipStream_t st = S(stream);
   int rc = refresh_if_dirty(c, st);
   if (rc) return rc;
   rc = stage_ticks(c, n, ticks, st);
@@ -2369,15 +2370,13 @@ int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
     rc = wslab_clean(c, st);
     if (rc) return rc;
     const bool pipe = c->win_pipe && c->comm_stream && pipe_buffers(c);
-    rc = window_launches(c, n, c->d_ticks, action, act_stride, mode, reward, rew_stride, p_out, true, st, false,
-                         pipe);
+    rc = pipe ? window_pipeline(c, a, st) : window_launches(c, a, true, st);
     c->counts_ready = false;
     return rc;
   }
   const bool can_overlap = lookahead_ok(mode) && rew_stride != 0 && c->comm_stream;
-  if (can_overlap && c->tick_overlap)
-    return rollout_sharded_overlap(c, c->d_ticks, n, mode, reward, rew_stride, p_out, st);
-  return rollout_sharded_serial(c, c->d_ticks, n, action, act_stride, mode, reward, rew_stride, p_out, st);
+  if (can_overlap && c->tick_overlap) return rollout_sharded_overlap(c, a, st);
+  return rollout_sharded_serial(c, a, st);
 }
 
 int mdr_rollout_sharded_mode(mdr_ctx* c, int* window_pipeline, int* tick_overlap) {
