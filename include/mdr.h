@@ -313,7 +313,10 @@ int mdr_reward_finalize(mdr_ctx* ctx, const mdr_tick* tick, double* reward, void
  * on the temporally blocked path (below) each window's step kernel writes per-wave {sum pen/N,
  * max pen} partials every tick and two finish kernels (k_win_pen_reduce, k_win_reward_common)
  * follow it; on the one-tick path every step is followed by mdr_penalty_partials /
- * mdr_reward_finalize's kernels.  With rew_stride == 0 only the last tick's rewards are finalised
+ * mdr_reward_finalize's kernels.  The bang-bang sources' closed-loop windows (below) form the pair
+ * per tick and block in the one-tick kernels' summation order (k_step_closed<..., COMMON>), and
+ * k_win_pen_reduce + k_closed_reward_common finish each window behind k_win_reduce: bit for bit the
+ * one-tick path.  With rew_stride == 0 only the last tick's rewards are finalised
  * (the row every tick overwrites).  Fixed reduction order: bit-reproducible from run to run.  A
  * context with a communicator (or world > 1) returns MDR_EARG for these modes: per-step API. */
 int mdr_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
@@ -325,12 +328,15 @@ int mdr_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t*
  * Metrics.update (metrics_service.py:108-157) and TrainingManager.test means
  * (training_manager.py:265-295) at rollout speed.  stats == NULL is mdr_rollout, launch for launch.
  *   - closed-loop windows (MDR_ACT_BANGBANG / _DEADBAND_BANGBANG under individual_L2, <= 4 capacity
- *     classes, window > 0): the window kernel itself forms every tick's block partials
+ *     classes, window > 0; under a common penalty mode a call WITH stats rows stays on the one-tick
+ *     sequence below, though the same call without them runs windows): the window kernel itself
+ *     forms every tick's block partials
  *     (k_step_closed<..., STATS>) and one more kernel per window (k_closed_stats) writes its rows.
  *     Slots 2, 10, 11, 12 are mdr_tick_stats' bits; the sums are formed in another fixed order, and
  *     slot 4 from sum_i pen_i and the tick's signal term: -((alpha_temp sum pen [/ norm_temp] + n sig)
  *     / N), the same with rew_stride == 0;
- *   - one launch per tick (the bang-bang sources otherwise, any source with mdr_set_rollout_window(0)
+ *   - one launch per tick (the bang-bang sources otherwise — the common penalty modes among them —,
+ *     any source with mdr_set_rollout_window(0)
  *     or > 4 capacity classes): mdr_tick_stats' two kernels behind every tick's step and finalise
  *     kernels, bit for bit mdr_tick_stats after mdr_step;
  *   - the open-loop window rollout (k_step_window) writes no rows: MDR_EARG.
@@ -353,14 +359,17 @@ int mdr_rollout_stats_path(mdr_ctx* ctx, int action_mode);
  * cluster power from counts the previous launch ran ahead (the FSM of an open-loop source does
  * not depend on the thermal state).  Bit-identical to the one-tick path under MDR_THERMAL_EXACT.
  * The bang-bang sources (MDR_ACT_BANGBANG / _DEADBAND_BANGBANG) run blocked too in mdr_rollout,
- * under individual_L2 with <= 4 capacity classes: a closed-loop window (k_step_closed) keeps
+ * with <= 4 capacity classes: a closed-loop window (k_step_closed) keeps
  * controller, lockout FSM and thermal update in registers for its ticks, writes each tick's raw
  * temperature penalty to the reward row and counts its ON houses; k_win_reduce then forms every
  * tick's cluster power and a finish kernel (k_closed_reward) rewrites the rows in place (with
- * rew_stride == 0 only the last tick's).  Always the EXACT thermal form (MDR_OPT_WINDOW_THERMAL is
+ * rew_stride == 0 only the last tick's).  Under a common penalty mode (unsharded) the window also
+ * stores a {sum pen/N, max pen} pair per tick and block, added in the one-tick kernels' order, and
+ * k_win_pen_reduce + k_closed_reward_common finish the rows (the uniform modes write no raw
+ * penalties at all).  Always the EXACT thermal form (MDR_OPT_WINDOW_THERMAL is
  * ignored): bit-identical to the one-tick path.  What falls back to one launch per tick inside the
- * call: the bang-bang sources under the common penalty modes, any source with more than 4 capacity
- * classes, and ticks = 0.  mdr_rollout_sharded returns MDR_EARG for the bang-bang sources (the
+ * call: the bang-bang sources under a common penalty mode when stats rows are asked for
+ * (mdr_rollout_stats), any source with more than 4 capacity classes, and ticks = 0.  mdr_rollout_sharded returns MDR_EARG for the bang-bang sources (the
  * window's cluster power would need an allreduce inside the launch sequence): per-step API.
  * ticks in 1..32 (default 32), 0 = one launch per tick.  Applies to mdr_rollout and
  * mdr_rollout_sharded; drops cached rollout graphs. */
@@ -382,7 +391,8 @@ int mdr_rollout_begin(mdr_ctx* ctx, int n_ticks, uint64_t tick0, const uint8_t* 
  * with an event pair around every step-kernel launch; *ms = the summed step-kernel time,
  * *launches = step launches (windows — k_step_window or k_step_closed —, or ticks on the one-tick
  * path).  Advances the state like
- * mdr_rollout; synchronises the stream. */
+ * mdr_rollout; synchronises the stream.  Every penalty mode on an unsharded context (a common
+ * mode's finish kernels are outside the event pairs of a window, inside those of a one-tick group). */
 int mdr_time_step_kernels(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                           int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                           void* stream, float* ms, int* launches);

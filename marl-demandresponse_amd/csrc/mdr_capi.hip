@@ -963,10 +963,12 @@ static bool window_ok(const mdr_ctx* c, int mode) {
          (mode == MDR_ACT_RANDOM || mode == MDR_ACT_ALWAYS_ON || mode == MDR_ACT_BUFFER);
 }
 
-// the closed-loop window (k_step_closed): the bang-bang sources under individual_L2, the same
-// window, class and L / dt conditions; everything else of theirs runs one launch per tick
-static bool closed_ok(const mdr_ctx* c, int mode) {
-  return window_geom_ok(c) && !win_common(c) && (mode == MDR_ACT_BANGBANG || mode == MDR_ACT_DEADBAND_BANGBANG);
+// the closed-loop window (k_step_closed): the bang-bang sources, the same window, class and L / dt
+// conditions; a common penalty mode needs its partial rows (d_wpen / d_wres) and gives no stats rows
+// (no STATS x COMMON instantiation).  Everything else of theirs runs one launch per tick
+static bool closed_ok(const mdr_ctx* c, int mode, bool stats = false) {
+  return window_geom_ok(c) && (win_common(c) ? !stats && c->d_wpen && c->d_wres : true) &&
+         (mode == MDR_ACT_BANGBANG || mode == MDR_ACT_DEADBAND_BANGBANG);
 }
 
 // the window slots' shard part is zero between rollouts (k_win_reduce zeroes what it reads);
@@ -1298,7 +1300,15 @@ static bool pipe_buffers(mdr_ctx* c) {
 // stats (mdr_rollout_stats): row t of the rollout goes to stats + t * kTickRow — the STATS
 // instantiation of k_step_closed (block partials per tick into d_wstat, checked against the launch
 // geometry first) and, last of the window, k_closed_stats over its K ticks.
+// A common penalty mode (never with stats): the COMMON instantiation of k_step_closed (a {sum pen_i /
+// N, max pen_i} pair per tick and block into d_wpen, checked against the launch geometry first),
+// k_win_reduce, k_win_pen_reduce over the window's ticks (ntile = the grid: k_pen_reduce's order) and
+// k_closed_reward_common over its rows — 4 nw launches; one shared row: the last window's last tick
+// alone is reduced and finalised, 2 nw + 2.
 static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr) {
+  const bool common = win_common(c);
+  if (common && stats) return fail(MDR_ESTATE, "window launch: no stats rows from a common-penalty window");
+  if (common && (!c->d_wpen || !c->d_wres)) return fail(MDR_ESTATE, "window launch: no penalty partial rows");
   if (stats && !c->d_wstat) return fail(MDR_ESTATE, "window launch: no stats partial rows");
   double* const wstat = stats ? c->d_wstat : nullptr;
   const WinPlan plan(a.n, c->win);
@@ -1326,18 +1336,32 @@ static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, dou
     };
     if (stats) {  // (the partial rows this launch's geometry writes)
       if (int rc = mdr_window_stats_check(kp.n, c->wstat_bytes)) return rc;
-      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, true, double*>, wstat);
-      else closed(k_step_closed<kActDeadband, kWinHpt, true, double*>, wstat);
+      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, true, false, double*>, wstat);
+      else closed(k_step_closed<kActDeadband, kWinHpt, true, false, double*>, wstat);
+    } else if (common) {  // (grid x K pairs, a quarter of what the per-wave rows of k_step_window need)
+      if (int rc = mdr_window_pen_check(kp.n, c->wpen_bytes)) return rc;
+      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, false, true, double*>, c->d_wpen);
+      else closed(k_step_closed<kActDeadband, kWinHpt, false, true, double*>, c->d_wpen);
     } else if (mode == MDR_ACT_BANGBANG) {
-      closed(k_step_closed<kActBangBang, kWinHpt, false>);
+      closed(k_step_closed<kActBangBang, kWinHpt, false, false>);
     } else {
-      closed(k_step_closed<kActDeadband, kWinHpt, false>);
+      closed(k_step_closed<kActDeadband, kWinHpt, false, false>);
     }
     LAUNCH_CHECK("k_step_closed");
     hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot, K, tk + t0,
                        w == nw - 1 ? a.p_out : nullptr);
     LAUNCH_CHECK("k_win_reduce");
-    if (rew_stride || w == nw - 1) {
+    if (common) {
+      if (rew_stride || w == nw - 1) {
+        const int j0 = rew_stride ? 0 : K - 1;
+        hipLaunchKernelGGL(k_win_pen_reduce, dim3(K - j0), dim3(256), 0, st,
+                           (const double*)c->d_wpen + (size_t)j0 * grid * 2, (int)grid, c->d_wres + 2 * j0);
+        LAUNCH_CHECK("k_win_pen_reduce");
+        hipLaunchKernelGGL(k_closed_reward_common, dim3(blocks(kp.n, 256), K - j0), dim3(256), 0, st, kp,
+                           (const double*)c->d_wres, rec, j0, r, rew_stride);
+        LAUNCH_CHECK("k_closed_reward_common");
+      }
+    } else if (rew_stride || w == nw - 1) {
       const int j0 = rew_stride ? 0 : K - 1;
       hipLaunchKernelGGL(k_closed_reward, dim3(blocks(kp.n, 256), K - j0), dim3(256), 0, st, kp, rec, j0, r,
                          rew_stride);
@@ -1368,7 +1392,7 @@ static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_d
 static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr) {
   const int n = a.n, mode = a.mode;
   if (window_ok(c, mode)) return window_launches(c, a, false, st);
-  if (closed_ok(c, mode)) return closed_launches(c, a, st, stats);
+  if (closed_ok(c, mode, stats != nullptr)) return closed_launches(c, a, st, stats);
   double* const p_tick = a.p_out ? a.p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
   if (int rc = zero_slabs(c, st)) return rc;
   c->ring = 0;
@@ -1408,7 +1432,7 @@ static bool consecutive(const mdr_tick* ticks, int n) {
 // the buffers a rollout with stats rows needs, allocated outside any capture: the closed-loop
 // windows' block partials, or the per-tick form's k_tick_stats partials and a P scalar
 static int rollout_stats_scratch(mdr_ctx* c, int mode, bool need_p) {
-  if (closed_ok(c, mode)) {
+  if (closed_ok(c, mode, true)) {
     if (c->d_wstat) return MDR_OK;
     const size_t bytes = mdr_window_stats_bytes(c->kp.n);
     HIP_TRY(hipMalloc(&c->d_wstat, bytes));
@@ -1425,7 +1449,7 @@ static int rollout_stats_path(mdr_ctx* c, int mode, const std::string& who) {
   if (window_ok(c, mode))
     return fail(MDR_EARG, who + ": no stats rows from the open-loop window rollout (k_step_window); use the "
                                 "bang-bang sources, or mdr_set_rollout_window(0) for one launch per tick");
-  return closed_ok(c, mode) ? MDR_STATS_CLOSED_WINDOWS : MDR_STATS_PER_TICK;
+  return closed_ok(c, mode, true) ? MDR_STATS_CLOSED_WINDOWS : MDR_STATS_PER_TICK;
 }
 
 int mdr_rollout_stats_path(mdr_ctx* c, int mode) {
@@ -1579,7 +1603,9 @@ int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_
                           int mode, double* reward, int64_t rew_stride, void* stream, float* ms, int* launches) {
   drop_begun(c);  // (a refused call discards an early count too)
   const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, nullptr};
-  if (int rc = rollout_preamble(c, "mdr_time_step_kernels", ticks && reward && ms && launches, a, kNoCommon)) return rc;
+  if (int rc = rollout_preamble(c, "mdr_time_step_kernels", ticks && reward && ms && launches, a, 0)) return rc;
+  if (common_sharded(c))  // (mdr_rollout's refusal)
+    return fail(MDR_EARG, "mdr_time_step_kernels: common penalty modes on a sharded context need the per-step API");
   hipStream_t st = S(stream);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = stage_ticks(c, n, ticks, st);

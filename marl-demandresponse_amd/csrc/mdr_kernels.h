@@ -188,11 +188,18 @@ __global__ void k_win_reward_common(KParams p, const double* res, const double* 
 // values over the post-step state (slot 4: the sum of the raw pen_i) to wstat[tick][block][12];
 // k_closed_stats finishes the rows.  W: <double*> (wstat) with STATS, empty without (the kernel
 // arguments of the STATS = false instantiations are unchanged).
-template <int CTRL, int HPT, bool STATS = false, class... W>
+// COMMON (the common penalty modes, STATS = false only; W: <double*>, wpen): every block also stores,
+// per tick of the window, {sum pen_i / N, max pen_i} over its 512 houses to wpen[tick][block][2], the
+// sum in the order of k_step_t's block partial; the reward rows get the raw pen_i (mixture) or
+// nothing; k_win_reduce, k_win_pen_reduce (ntile = the grid) and k_closed_reward_common follow it.
+template <int CTRL, int HPT, bool STATS = false, bool COMMON = false, class... W>
 __global__ void k_step_closed(KParams p, const TickArgs* tkp, int K, double* reward, int64_t rew_stride,
                               unsigned long long* slot, W... wstat);
 // reward rows j0 + blockIdx.y of a closed-loop window from their raw pen_i and the tick records
 __global__ void k_closed_reward(KParams p, const double* rec, int j0, double* reward, int64_t rew_stride);
+// ... of a COMMON closed-loop window: k_win_reward_common, the signal term from the tick records
+__global__ void k_closed_reward_common(KParams p, const double* res, const double* rec, int j0, double* reward,
+                                       int64_t rew_stride);
 // k_reward_finalize with the tick's drivers in device memory (rollouts with staged drivers)
 __global__ void k_reward_finalize_dev(KParams p, const TickArgs* tkp, const unsigned long long* counts,
                                       const double* partial2, double* reward);

@@ -1793,13 +1793,39 @@ __device__ __forceinline__ void closed_stats_tick(const ClosedAcc<true>& c, int 
   wave_lds_sync();  // (the next tick's stores to tr follow this tick's loads)
 }
 
-// (W: empty, or the one double* of a STATS launch — the other instantiations keep the parent's
-// kernel arguments, and with them the offsets of the implicit ones)
-template <int CTRL, int HPT, bool STATS, class... W>
+// COMMON (common_L2 / common_max_error / mixture): the cluster's {sum pen_i / N, max pen_i} of every
+// tick enter the reward and nothing else, so the window's state trajectory is the individual_L2 one
+// and the pair is finished behind the window (k_win_pen_reduce, k_closed_reward_common).  Per tick
+// the wave adds its tile's terms a = pen_i / N IN THE ORDER OF k_step_t, whose lane L holds houses
+// 2L, 2L + 1 of the same 128-house tile where this layout holds house 64 h + l in slot h of lane l:
+//   * per slot h: u_h = a_h + (a_h of lane l ^ 1)                 (k_step_t's lane sum from 0.0)
+//   * in the lane: v = u_0 + u_1                                   (its __shfl_xor offset 32)
+//   * v += __shfl_xor(v, off), off = 32, 16, 8, 4, 2                (its offsets 16 .. 1)
+// A house the tile does not hold adds 0.0; finite penalties are >= +0, so 0.0 + a and a + 0.0 are a
+// bit for bit, and IEEE addition commutes, so lanes that get the operands swapped agree.  The max is
+// an fmax from 0.0 (any order).  Lane 0 stores the wave's pair to LDS; behind the barrier that
+// precedes win_flush thread j adds the block's 4 waves in index order from 0.0 (k_step_t's thread 0)
+// and stores one pair per (tick, block) to wpen[tick][block] — the grid is k_step_t's, so
+// k_win_pen_reduce over gridDim.x entries runs k_pen_reduce's order.  Every block stores all K pairs
+// of its window: wpen is never cleared.  Reward rows: mixture gets the raw pen_i (the `store` rule),
+// the two uniform modes nothing.
+struct ClosedPenLds {
+  double pw[4][kWinMax][2];  // [wave][tick]{sum, max}
+};
+__device__ __forceinline__ ClosedPenLds& closed_pen_lds() {
+  __shared__ ClosedPenLds s;
+  return s;
+}
+
+// (W: empty, or the one double* of a STATS (wstat) or COMMON (wpen) launch — the other
+// instantiations keep the parent's kernel arguments, and with them the offsets of the implicit ones)
+template <int CTRL, int HPT, bool STATS, bool COMMON, class... W>
 __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* __restrict__ tkp, int K,
                                                      double* __restrict__ reward, int64_t rew_stride,
                                                      unsigned long long* __restrict__ slot, W... wstat_arg) {
-  static_assert(sizeof...(W) == (STATS ? 1 : 0), "wstat rides only on a STATS launch");
+  static_assert(sizeof...(W) == (STATS || COMMON ? 1 : 0), "a partial buffer rides only on a STATS or COMMON launch");
+  static_assert(!(STATS && COMMON), "stats rows under a common penalty mode stay on the per-tick sequence");
+  static_assert(!COMMON || HPT == 2, "the COMMON order restates k_step_t's two houses per lane");
   static_assert(CTRL == kActBangBang || CTRL == kActDeadband, "a bang-bang action source");
   __shared__ unsigned s_cnt[4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1847,8 +1873,10 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
   // ---- the K ticks; the tick's drivers are wave-uniform (scalar loads), read one tick ahead
   uint32_t cnt_v[kWinCap] = {0u, 0u, 0u, 0u};  // lane j: tick j's ON houses of the tile per class
   const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
+  const bool mix = COMMON && p.penalty_mode == MDR_PEN_MIXTURE;  // COMMON: only mixture keeps the raw pen_i
   TickArgs nx = tkp[0];
   for (int j = 0; j < K; ++j) {
+    [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
     const TickArgs tk = nx;
     nx = tkp[j + 1 < K ? j + 1 : j];
     const double od_k = tk.t_od_prev + 273.0;  // rc_apply_t's od_k
@@ -1884,7 +1912,9 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
         T[h] = Tn;
         Tm[h] = Tmn;
         const double pen = deadband_l2(tg[h], p.deadband, Tn);
-        if (store && t.v[h]) __builtin_nontemporal_store(pen, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+        if constexpr (COMMON) pen_t[h] = pen;
+        if ((!COMMON || mix) && store && t.v[h])
+          __builtin_nontemporal_store(pen, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
         if constexpr (STATS) {  // the post-step state of tick j
           if (t.v[h]) closed_acc(acc, Tn, Tmn, tg[h], pen, (double)p.n_global);
           const uint64_t vm = __builtin_amdgcn_ballot_w64(t.v[h]);
@@ -1903,6 +1933,31 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
       cnt_v[c] = writelane_u32(cnt_v[c], k, j);
     }
     if constexpr (STATS) closed_stats_tick(acc, wv, lane, j);
+    if constexpr (COMMON) {  // the tile's {sum pen_i / N, max pen_i}, the sum in k_step_t's order
+      double u[HPT], m = 0.0;
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        const double a = t.v[h] ? pen_t[h] / (double)p.n_global : 0.0;
+        u[h] = a + dpp_f64<0xB1>(a);  // quad_perm [1, 0, 3, 2]: lane l ^ 1
+        m = fmax(m, t.v[h] ? pen_t[h] : 0.0);
+      }
+      double v = u[0] + u[1];
+#pragma unroll
+      for (int off = 32; off > 2; off >>= 1) v += __shfl_xor(v, off);
+      v += dpp_f64<0x4E>(v);  // quad_perm [2, 3, 0, 1]: lane l ^ 2
+      // the max of the row of 16 by DPP moves (any order), then the four rows
+      m = fmax(m, dpp_f64<0xB1>(m));
+      m = fmax(m, dpp_f64<0x4E>(m));
+      m = fmax(m, dpp_f64<0x141>(m));  // row_half_mirror
+      m = fmax(m, dpp_f64<0x140>(m));  // row_mirror
+      m = fmax(m, __shfl_xor(m, 16));
+      m = fmax(m, __shfl_xor(m, 32));
+      if (lane == 0) {
+        ClosedPenLds& s = closed_pen_lds();
+        s.pw[wv][j][0] = v;
+        s.pw[wv][j][1] = m;
+      }
+    }
   }
 
   // ---- state back, once per window
@@ -1939,16 +1994,35 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
       wstat[((size_t)j * gridDim.x + blockIdx.x) * kStats + k] = v;
     }
   }
+  if constexpr (COMMON) {  // the block's pair of every tick: its 4 waves in index order from 0.0
+    const ClosedPenLds& s = closed_pen_lds();
+    double* __restrict__ wpen = std::get<0>(std::tuple<W...>(wstat_arg...));
+    if ((int)threadIdx.x < K) {
+      const int j = threadIdx.x;
+      double bs = 0.0, bm = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { bs += s.pw[r][j][0]; bm = fmax(bm, s.pw[r][j][1]); }
+      *reinterpret_cast<double2*>(wpen + ((size_t)j * gridDim.x + blockIdx.x) * 2) = make_double2(bs, bm);
+    }
+  }
 }
 
-template __global__ void k_step_closed<kActBangBang, kWinHpt, false>(KParams, const TickArgs*, int, double*, int64_t,
-                                                                     unsigned long long*);
-template __global__ void k_step_closed<kActDeadband, kWinHpt, false>(KParams, const TickArgs*, int, double*, int64_t,
-                                                                     unsigned long long*);
-template __global__ void k_step_closed<kActBangBang, kWinHpt, true, double*>(KParams, const TickArgs*, int, double*,
-                                                                             int64_t, unsigned long long*, double*);
-template __global__ void k_step_closed<kActDeadband, kWinHpt, true, double*>(KParams, const TickArgs*, int, double*,
-                                                                             int64_t, unsigned long long*, double*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, false, false>(KParams, const TickArgs*, int, double*,
+                                                                            int64_t, unsigned long long*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, false, false>(KParams, const TickArgs*, int, double*,
+                                                                            int64_t, unsigned long long*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, true, false, double*>(KParams, const TickArgs*, int,
+                                                                                    double*, int64_t,
+                                                                                    unsigned long long*, double*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, true, false, double*>(KParams, const TickArgs*, int,
+                                                                                    double*, int64_t,
+                                                                                    unsigned long long*, double*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, false, true, double*>(KParams, const TickArgs*, int,
+                                                                                    double*, int64_t,
+                                                                                    unsigned long long*, double*);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, false, true, double*>(KParams, const TickArgs*, int,
+                                                                                    double*, int64_t,
+                                                                                    unsigned long long*, double*);
 
 
 #define MDR_INST_WIN_C(A, SI, KA_, FO, CO)                                                                     \
@@ -2166,6 +2240,21 @@ __global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* 
   double* r = reward + (int64_t)j * rew_stride + i;
   const double tpen = p.alpha_temp * *r;
   __builtin_nontemporal_store(-((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term), r);
+}
+
+// Finish of a COMMON closed-loop window (behind k_step_closed<..., COMMON>, k_win_reduce and
+// k_win_pen_reduce): k_win_reward_common with the signal term read from the tick records as
+// k_closed_reward reads it (the exact negation of rec[2]), so no launch publishes the signal terms.
+__global__ void __launch_bounds__(256) k_closed_reward_common(KParams p, const double* __restrict__ res,
+                                                              const double* __restrict__ rec, int j0,
+                                                              double* __restrict__ reward, int64_t rew_stride) {
+  const int j = j0 + (int)blockIdx.y;
+  const double common_l2 = res[2 * j], common_max = res[2 * j + 1], sig_term = -rec[j * kWinRec + 2];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  double* r = reward + (int64_t)j * rew_stride + i;
+  const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
+  __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
 }
 
 // Reward of the last tick of an overlapped multi-GPU rollout (the k_step launches there write

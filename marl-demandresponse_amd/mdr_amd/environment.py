@@ -598,18 +598,21 @@ class Environment:
         mixture) take the same path on an unsharded environment: each window's step kernel writes
         per-wave penalty partials every tick and two finish kernels form the rewards (a 1-D
         ``rewards`` holds the last tick's); sharded environments keep ``step_tensor`` for them.
-        ``action_mode='bangbang'`` / ``'deadband_bangbang'`` (unsharded): closed-loop windows under
-        individual_L2 with <= 4 capacity classes (k_step_closed: controller, lockout FSM and thermal
-        update in registers for up to 32 ticks, two short kernels finish each window's rewards),
-        otherwise one step launch per tick inside the call; either way bit for bit the
+        ``action_mode='bangbang'`` / ``'deadband_bangbang'`` (unsharded): closed-loop windows with
+        <= 4 capacity classes (k_step_closed: controller, lockout FSM and thermal update in
+        registers for up to 32 ticks, two short kernels finish each window's rewards; under the
+        common penalty modes the window also leaves each tick's {mean, max} penalty partials, added
+        in the one-tick kernels' order, and three short kernels finish it), otherwise — more
+        capacity classes, ``set_rollout_window(0)``, or ``stats`` under a common penalty mode — one
+        step launch per tick inside the call; either way bit for bit the
         ``step_tensor(None, action_mode=c, lookahead=c)`` loop.  The drivers are staged first
         (there is no early count to launch: every tick's ON set depends on the thermal state).
 
         ``stats`` (mdr_amd.services.RolloutStats, the contract of ``DeviceActor.rollout``): each tick's
         row — the cluster statistics of the post-step state, its rewards and the cluster power — is
         written inside the launch sequence (mdr_rollout_stats): by the closed-loop windows themselves
-        (k_step_closed<..., STATS> + k_closed_stats), or by mdr_tick_stats' kernels behind every tick
-        where the call runs one launch per tick.  The open-loop window rollout (random / always_on /
+        (k_step_closed<..., STATS> + k_closed_stats; individual_L2 only), or by mdr_tick_stats' kernels
+        behind every tick where the call runs one launch per tick.  The open-loop window rollout (random / always_on /
         buffer with the window on) writes no rows: ``NotImplementedError``.  ``ValueError``: rows of
         another env, or more ticks than the rows left."""
         import torch
