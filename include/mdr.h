@@ -369,8 +369,10 @@ int mdr_rollout_stats_path(mdr_ctx* ctx, int action_mode);
  * penalties at all).  Always the EXACT thermal form (MDR_OPT_WINDOW_THERMAL is
  * ignored): bit-identical to the one-tick path.  What falls back to one launch per tick inside the
  * call: the bang-bang sources under a common penalty mode when stats rows are asked for
- * (mdr_rollout_stats), any source with more than 4 capacity classes, and ticks = 0.  mdr_rollout_sharded returns MDR_EARG for the bang-bang sources (the
- * window's cluster power would need an allreduce inside the launch sequence): per-step API.
+ * (mdr_rollout_stats), any source with more than 4 capacity classes, and ticks = 0.
+ * mdr_rollout_sharded runs the same closed-loop windows on every rank under individual_L2 (the
+ * window's state never reads the cluster power: its class totals are allreduced behind it, see
+ * mdr_rollout_sharded).
  * ticks in 1..32 (default 32), 0 = one launch per tick.  Applies to mdr_rollout and
  * mdr_rollout_sharded; drops cached rollout graphs. */
 int mdr_set_rollout_window(mdr_ctx* ctx, int ticks);
@@ -727,7 +729,17 @@ int mdr_comm_host(mdr_ctx* ctx, int world, int rank, mdr_host_allreduce_fn allre
 /* all-gather of `bytes` per rank into recv (world x bytes, rank order) on `stream` */
 int mdr_rccl_allgather(mdr_ctx* ctx, const void* send, void* recv, int64_t bytes, void* stream);
 /* sharded multi-tick rollout, RCCL allreduce of the count slab inside the loop:
- * per tick  [phase 1 if BUFFER] -> allreduce(counts) -> phase 2 (with lookahead when possible) */
+ * per tick  [phase 1 if BUFFER] -> allreduce(counts) -> phase 2 (with lookahead when possible)
+ * The bang-bang sources (individual_L2, <= 4 capacity classes, the window on): per window
+ * k_step_closed on this rank's houses -> k_win_shard_sum (the rank's per-tick class totals) ->
+ * allreduce of the K x n_cap totals (<= 1 KiB) -> k_closed_reward_sharded (P and the signal term
+ * from the cluster's totals; the rows rewritten in place; the last P to p_out) — bit for bit the
+ * single-process mdr_rollout.  With a reward row per tick and MDR_OPT_WINDOW_PIPELINE (default) the
+ * allreduce and the finish run on the communicator's side stream beside the next window's step
+ * kernel; one shared row (rew_stride == 0) finishes the last window's last tick only, on one
+ * stream.  With mdr_set_rollout_window(0) or more classes they take the per-tick loops above.
+ * Refused (MDR_EARG): the common penalty modes.  No stats rows on a sharded context
+ * (mdr_rollout_stats: MDR_ESTATE). */
 int mdr_rollout_sharded(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                         int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                         double* p_out, void* stream);

@@ -1377,6 +1377,101 @@ static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, dou
   return MDR_OK;
 }
 
+// ---- the sharded closed-loop window sequencers: a bang-bang source under
+// individual_L2 on a context with a communicator, the drivers staged in d_ticks.  The window's state
+// trajectory never reads the cluster power, so each rank runs k_step_closed on its own houses; only
+// the reward's signal term needs the cluster's ON counts.  Window w of the WinPlan uses count slot
+// w % 3: step (raw pen_i to the rows, this rank's ON counts into the slot's shards) -> sum
+// (k_win_shard_sum: shards -> red, shards zeroed) -> allreduce of red's K x n_cap totals (<= 1 KiB)
+// -> finish (k_closed_reward_sharded: P and the signal term from the totals, rows rewritten in
+// place; the last window's last P to p_out).  One shared row (rew_stride == 0): only the last window
+// is allreduced and finished (its last tick); the earlier ones sum and zero.
+struct ClosedShardSeq {
+  mdr_ctx* c;
+  const RolloutArgs& a;
+  WinPlan plan;
+  unsigned long long* slot(int w) const { return c->d_wslab + (size_t)(w % 3) * c->wslab_len; }
+  bool finished(int w) const { return a.rew_stride || w == plan.count() - 1; }
+  int step(int w, hipStream_t st) const {
+    const int K = plan.size(w), t0 = plan.start(w);
+    const unsigned grid = win_grid(c);
+    if (a.mode == MDR_ACT_BANGBANG)
+      hipLaunchKernelGGL((k_step_closed<kActBangBang, kWinHpt, false, false>), dim3(grid), dim3(256), 0, st, c->kp,
+                         (const TickArgs*)(c->d_ticks + t0), K, a.rew_row(t0), a.rew_stride, slot(w));
+    else
+      hipLaunchKernelGGL((k_step_closed<kActDeadband, kWinHpt, false, false>), dim3(grid), dim3(256), 0, st, c->kp,
+                         (const TickArgs*)(c->d_ticks + t0), K, a.rew_row(t0), a.rew_stride, slot(w));
+    LAUNCH_CHECK("k_step_closed");
+    return MDR_OK;
+  }
+  int sum(int w, hipStream_t st) const {
+    hipLaunchKernelGGL(k_win_shard_sum, dim3(plan.size(w)), dim3(64 * c->kp.n_cap), 0, st, c->kp, slot(w));
+    LAUNCH_CHECK("k_win_shard_sum");
+    return MDR_OK;
+  }
+  // the window's allreduce and reward finish, both ordered on st
+  int reduce_finish(int w, hipStream_t st) const {
+    const int K = plan.size(w), t0 = plan.start(w), j0 = a.rew_stride ? 0 : K - 1;
+    unsigned long long* red = win_red_ptr(c, slot(w));
+    if (int rc = comm_allreduce(c, red, (size_t)K * c->kp.n_cap, 0, st)) return rc;
+    hipLaunchKernelGGL(k_closed_reward_sharded, dim3(blocks(c->kp.n, 256), K - j0), dim3(256), 0, st, c->kp,
+                       (const unsigned long long*)red, (const TickArgs*)(c->d_ticks + t0), j0, K, a.rew_row(t0),
+                       a.rew_stride, w == plan.count() - 1 ? a.p_out : nullptr);
+    LAUNCH_CHECK("k_closed_reward_sharded");
+    return MDR_OK;
+  }
+};
+
+// one stream: step -> sum -> allreduce -> finish per window
+static int closed_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  for (int w = 0; w < s.plan.count(); ++w) {
+    if (int rc = s.step(w, st)) return rc;
+    if (int rc = s.sum(w, st)) return rc;
+    if (s.finished(w))
+      if (int rc = s.reduce_finish(w, st)) return rc;
+  }
+  c->wslab_dirty = false;
+  return MDR_OK;
+}
+
+// two streams, a reward row per tick (rew_stride != 0: every window is finished): the compute stream
+// runs step(w) -> sum(w), the comm stream allreduce(w) -> finish(w) behind sum(w)'s event.
+// step(w + 1) and sum(w + 1) are issued BEFORE the host enters allreduce(w): a host-callback
+// communicator synchronises the comm stream and blocks in the collective, and the device then has
+// the next window to run.  Hazards: sum(w + 3) rewrites the red part of slot w % 3, which
+// allreduce(w) and finish(w) use — it waits for finish(w)'s event (the shards step(w + 3) adds to
+// were zeroed by sum(w), earlier on the compute stream); finish(w) and step(w + 1) write disjoint
+// rows.  The caller's stream is the compute stream and waits for the last finish.
+// (One shared row has a single allreduce and finish, behind the last step: nothing to run beside
+// them, and the two stream hand-offs measured 8 % of a 1M-house call — mdr_rollout_sharded sends it
+// to closed_sharded_serial.)
+static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
+  const int nw = s.plan.count();
+  hipStream_t cs = c->comm_stream;
+  c->wslab_dirty = true;  // until the sequence is fully issued
+  auto compute = [&](int w) -> int {
+    if (int rc = s.step(w, st)) return rc;
+    if (w >= 3) HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(w - 3) % kSlabs], 0));
+    if (int rc = s.sum(w, st)) return rc;
+    HIP_TRY(hipEventRecord(c->ev_k1[w % kSlabs], st));
+    return MDR_OK;
+  };
+  if (int rc = compute(0)) return rc;
+  for (int w = 0; w < nw; ++w) {
+    if (w + 1 < nw)
+      if (int rc = compute(w + 1)) return rc;
+    HIP_TRY(hipStreamWaitEvent(cs, c->ev_k1[w % kSlabs], 0));
+    if (int rc = s.reduce_finish(w, cs)) return rc;
+    HIP_TRY(hipEventRecord(c->ev_ar[w % kSlabs], cs));
+  }
+  HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(nw - 1) % kSlabs], 0));
+  c->wslab_dirty = false;
+  return MDR_OK;
+}
+
 // (per-tick stats rows, defined with mdr_tick_stats below)
 static int check_tick_stats_ctx(mdr_ctx* c, const char* who);
 static int tick_scratch(mdr_ctx* c);
@@ -1466,7 +1561,7 @@ static bool common_sharded(const mdr_ctx* c) { return win_common(c) && (has_comm
 // reports them.  ptrs: the entry point's own pointer arguments are there.
 enum {
   kDropBegun = 1,    // discard an early count once the arguments are there (the others settle it themselves)
-  kShardedOnly = 2,  // mdr_rollout_sharded: a communicator, no bang-bang source
+  kShardedOnly = 2,  // mdr_rollout_sharded: a communicator
   kNoCommon = 4      // no common penalty mode (mdr_rollout / mdr_rollout_begin decide behind the preamble)
 };
 static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const RolloutArgs& a, int flags) {
@@ -1479,8 +1574,6 @@ static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const Rollou
     return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
   if (!check_mode(a.mode) || (a.mode == MDR_ACT_BUFFER && !a.action))
     return fail(MDR_EARG, std::string(who) + ": bad action source");
-  if ((flags & kShardedOnly) && (a.mode == MDR_ACT_BANGBANG || a.mode == MDR_ACT_DEADBAND_BANGBANG))
-    return fail(MDR_EARG, std::string(who) + ": bang-bang sources need the per-step API");
   if ((flags & kNoCommon) && win_common(c)) return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
   return MDR_OK;
 }
@@ -2397,6 +2490,14 @@ int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
     if (rc) return rc;
     const bool pipe = c->win_pipe && c->comm_stream && pipe_buffers(c);
     rc = pipe ? window_pipeline(c, a, st) : window_launches(c, a, true, st);
+    c->counts_ready = false;
+    return rc;
+  }
+  if (closed_ok(c, mode)) {  // (individual_L2: the preamble refused the common penalty modes)
+    rc = wslab_clean(c, st);
+    if (rc) return rc;
+    const bool pipe = c->win_pipe && c->comm_stream && rew_stride != 0;  // (one shared row: one stream)
+    rc = pipe ? closed_sharded_pipeline(c, a, st) : closed_sharded_serial(c, a, st);
     c->counts_ready = false;
     return rc;
   }

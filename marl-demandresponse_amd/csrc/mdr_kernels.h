@@ -200,6 +200,14 @@ __global__ void k_closed_reward(KParams p, const double* rec, int j0, double* re
 // ... of a COMMON closed-loop window: k_win_reward_common, the signal term from the tick records
 __global__ void k_closed_reward_common(KParams p, const double* res, const double* rec, int j0, double* reward,
                                        int64_t rew_stride);
+// Sharded closed-loop windows (mdr_rollout_sharded, bang-bang sources): block j sums this rank's
+// shards of tick j into the slot's red part and zeroes them (grid K, 64 x n_cap threads) ...
+__global__ void k_win_shard_sum(KParams p, unsigned long long* slot);
+// ... and, once red holds the allreduced class totals, k_closed_reward with P (win_power) and the
+// signal term (win_nsig, the staged tick's s_prev) formed per block; nt: the window's ticks, whose
+// last P goes to p_out (null: none)
+__global__ void k_closed_reward_sharded(KParams p, const unsigned long long* red, const TickArgs* tkp, int j0, int nt,
+                                        double* reward, int64_t rew_stride, double* p_out);
 // k_reward_finalize with the tick's drivers in device memory (rollouts with staged drivers)
 __global__ void k_reward_finalize_dev(KParams p, const TickArgs* tkp, const unsigned long long* counts,
                                       const double* partial2, double* reward);

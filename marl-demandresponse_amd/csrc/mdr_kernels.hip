@@ -1077,6 +1077,23 @@ __global__ void __launch_bounds__(256) k_win_reduce(KParams p, unsigned long lon
   win_reduce_body(p, slot, nt, tkp ? tkp + blockIdx.x : nullptr, p_out);
 }
 
+// Sharded closed-loop windows: win_reduce_body's shard sum without the record (its own statements,
+// so k_win_reduce's code stays the parent's).  Block j sums this rank's 64 shards of tick j per class
+// into red and zeroes them; the K x n_cap totals in red are then allreduced (<= 1 KiB) and
+// k_closed_reward_sharded forms P and the signal term from the cluster's totals.
+__global__ void __launch_bounds__(256) k_win_shard_sum(KParams p, unsigned long long* __restrict__ slot) {
+  const int j = blockIdx.x, c = threadIdx.x >> 6, q = threadIdx.x & 63, ncap = p.n_cap;
+  unsigned long long v = 0;
+  if (c < ncap) {
+    unsigned long long* e = &slot[((size_t)j * kCountShards + q) * ncap + c];
+    v = *e;
+    *e = 0ull;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if (q == 0 && c < ncap) win_red(slot, ncap)[j * ncap + c] = v;
+}
+
 // Sharded windows: the tick records from the slot's reduced counts `red` once they hold the
 // cluster's totals (every rank's count kernel reduced its own shards in its last block, then one
 // sum-allreduce of the K x n_cap totals): thread j writes tick j's record (tkp: the full record;
@@ -2235,6 +2252,32 @@ __global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* 
                                                        double* __restrict__ reward, int64_t rew_stride) {
   const int j = j0 + (int)blockIdx.y;
   const double sig_term = -rec[j * kWinRec + 2];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  double* r = reward + (int64_t)j * rew_stride + i;
+  const double tpen = p.alpha_temp * *r;
+  __builtin_nontemporal_store(-((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term), r);
+}
+
+// Finish of a closed-loop window on a sharded context (behind k_step_closed, k_win_shard_sum and the
+// allreduce of the window's K x n_cap class totals): k_closed_reward with the signal term formed
+// here instead of read from a tick record.  `red` holds the CLUSTER's exact integer totals, so every
+// block derives tick j's P with win_power and its negated signal penalty with win_nsig from the
+// staged tick's s_prev — k_win_reduce's expressions on the single-process run's operands — and
+// -nsig has the bits of -rec[2].  The values are uniform in the block (scalar loads and arithmetic).
+// The block of house 0 at the window's last tick stores P to p_out (null: not the rollout's last
+// window).  rew_stride == 0: the caller launches the last tick alone.
+__global__ void __launch_bounds__(256) k_closed_reward_sharded(KParams p, const unsigned long long* __restrict__ red,
+                                                               const TickArgs* __restrict__ tkp, int j0, int nt,
+                                                               double* __restrict__ reward, int64_t rew_stride,
+                                                               double* p_out) {
+  const int j = j0 + (int)blockIdx.y, ncap = p.n_cap;
+  double p_on[kWinCap];
+#pragma unroll
+  for (int k = 0; k < kWinCap; ++k) p_on[k] = p.p_on[k < ncap ? k : 0];
+  const double P = win_power(p, red + j * ncap, p_on);
+  const double sig_term = -win_nsig(p, P, tkp[j].s_prev);
+  if (p_out && j == nt - 1 && blockIdx.x == 0 && threadIdx.x == 0) *p_out = P;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
   double* r = reward + (int64_t)j * rew_stride + i;

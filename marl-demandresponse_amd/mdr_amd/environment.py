@@ -598,7 +598,7 @@ class Environment:
         mixture) take the same path on an unsharded environment: each window's step kernel writes
         per-wave penalty partials every tick and two finish kernels form the rewards (a 1-D
         ``rewards`` holds the last tick's); sharded environments keep ``step_tensor`` for them.
-        ``action_mode='bangbang'`` / ``'deadband_bangbang'`` (unsharded): closed-loop windows with
+        ``action_mode='bangbang'`` / ``'deadband_bangbang'``: closed-loop windows with
         <= 4 capacity classes (k_step_closed: controller, lockout FSM and thermal update in
         registers for up to 32 ticks, two short kernels finish each window's rewards; under the
         common penalty modes the window also leaves each tick's {mean, max} penalty partials, added
@@ -607,6 +607,10 @@ class Environment:
         step launch per tick inside the call; either way bit for bit the
         ``step_tensor(None, action_mode=c, lookahead=c)`` loop.  The drivers are staged first
         (there is no early count to launch: every tick's ON set depends on the thermal state).
+        Sharded (individual_L2 only): the same closed-loop windows per rank; each window's per-tick
+        class totals (<= 1 KiB) are allreduced behind it, beside the next window's step kernel, and
+        a finish kernel forms the rewards from the cluster's totals (mdr_rollout_sharded) — bit for
+        bit the single-process rollout.  A ``TorchComm`` steps every tick from Python.
 
         ``stats`` (mdr_amd.services.RolloutStats, the contract of ``DeviceActor.rollout``): each tick's
         row — the cluster statistics of the post-step state, its rewards and the cluster power — is
@@ -622,9 +626,6 @@ class Environment:
             # (the cluster's per-tick mean / max penalty would need an allreduce inside the window sequence)
             raise NotImplementedError("sharded rollout supports individual_L2; use step_tensor for common penalties")
         mode = ACTION_MODES[action_mode]
-        if mode in (L.ACT_BANGBANG, L.ACT_DEADBAND_BANGBANG) and self._comm is not None:
-            # (the window's cluster power would need an allreduce inside the closed-loop kernel's launch sequence)
-            raise NotImplementedError("sharded bang-bang rollouts: use step_tensor(action_mode=..., lookahead=...)")
         srow0 = 0
         if stats is not None:
             if stats.env is not self:
