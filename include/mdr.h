@@ -480,6 +480,22 @@ int mdr_greedy_state(mdr_ctx* ctx, uint64_t* out);
  * (world > 1) returns MDR_ESTATE (its decision needs the caller's collectives: mdr_gq_shard_*). */
 int mdr_greedy_rollout(mdr_ctx* ctx, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
                        double* reward, int64_t rew_stride, double* p_out, void* stream);
+/* mdr_greedy_rollout that also writes tick t's stats row — mdr_tick_stats' 16 doubles of the state
+ * after its step, with its final rewards (under the common penalty modes: after
+ * mdr_reward_finalize) and its cluster power — into stats[row0 + t][16] (caller-owned device
+ * doubles; the caller answers for row0 + n rows): Metrics.update (metrics_service.py:108-157) and
+ * TrainingManager.test's means (training_manager.py:265-295) for GreedyMyopic at rollout speed.
+ * Both forms of the tick (MDR_OPT_GQ_FUSED 0 and 1).  Per tick one more launch (k_tick_stats into
+ * one of 32 slots of block partials in the context); one k_tick_rows_finish per 32 ticks and after
+ * the last tick writes the rows, a block each, and the last tick's P to p_out (may be NULL).  The
+ * rows have the bits of mdr_tick_stats called after every tick of the per-tick loop.
+ * MDR_EARG: row0 < 0, stats NULL with n > 0 (no rows: mdr_greedy_rollout).  MDR_ESTATE: a
+ * communicator or world > 1 (a row sums this shard's houses only).  A refused call launches
+ * nothing and leaves the context as it was; n == 0 runs the checks alone (the pointers may be
+ * NULL), so a caller can refuse before it advances its own drivers. */
+int mdr_greedy_rollout_stats(mdr_ctx* ctx, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
+                             double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
+                             void* stream);
 /* The predicted band (synchronises): out[4] = {mdr_ctrl_greedy calls that skipped the bins pass
  * (the step epilogue's band held the crossing, or no bins were needed), histogram-select calls,
  * the first superbin of the band the next GQ step counts, the band's width in superbins}.

@@ -218,6 +218,8 @@ struct mdr_ctx {
   float* d_halo = nullptr;     // sharded actor rollout: packed edge rows | received ring halo
   double* d_stats = nullptr;   // k_cluster_stats block partials
   double* d_tick_part = nullptr;  // k_tick_stats block partials (allocated zeroed, outside any capture)
+  double* d_rows_part = nullptr;  // mdr_greedy_rollout_stats: [kTickRowsBatch][kTickBlocks][kStats] block partials
+  double* d_rows_p = nullptr;     //   and the batch's [kTickRowsBatch] cluster powers (both allocated zeroed on first use)
   size_t halo_bytes = 0;
   std::map<std::vector<int64_t>, hipGraphExec_t> actor_graphs;
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
@@ -666,6 +668,8 @@ int mdr_destroy(mdr_ctx* c) {
   hipFree(c->d_halo);
   hipFree(c->d_stats);
   hipFree(c->d_tick_part);
+  hipFree(c->d_rows_part);
+  hipFree(c->d_rows_p);
   hipFree(c->d_obs_sc);
   hipFree(c->d_tables);
   hipFree(c->d_flags);
@@ -1477,6 +1481,8 @@ static int check_tick_stats_ctx(mdr_ctx* c, const char* who);
 static int tick_scratch(mdr_ctx* c);
 static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* row,
                              hipStream_t st);
+static int launch_tick_partials(mdr_ctx* c, const double* reward, double* partial, unsigned* nb_out, hipStream_t st);
+static int rows_scratch(mdr_ctx* c);
 
 // The launch sequence of a rollout with staged drivers (d_ticks), so a captured graph is reusable:
 // the window sequence (open-loop sources), the closed-loop window sequence (bang-bang sources under
@@ -2117,13 +2123,28 @@ int mdr_greedy_fused_diag(mdr_ctx* c, uint64_t* out) {
   return MDR_OK;
 }
 
-int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
-                       double* reward, int64_t rew_stride, double* p_out, void* stream) {
-  if (!c || (n > 0 && (!ticks || !action || !reward))) return fail(MDR_EARG, "mdr_greedy_rollout: null argument");
-  if (n < 0 || act_stride < 0 || rew_stride < 0) return fail(MDR_EARG, "mdr_greedy_rollout: negative size");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_rollout: context not bound");
-  if (c->world > 1)  // (a shard-local decision and step would use shard-local counts: per-tick loop)
-    return fail(MDR_ESTATE, "mdr_greedy_rollout: single-GPU only (sharded contexts: the per-tick greedy + step loop)");
+// The rows of a greedy rollout (stats != NULL): behind tick t's step (and finalise)
+// kernels, k_tick_stats into slot t mod kTickRowsBatch of the context's partial slab, that tick's P
+// into the same slot of the P slab, and k_tick_rows_finish after every kTickRowsBatch ticks and
+// after the last one, a block per tick.  A batch's slots are rewritten only by launches issued
+// behind its finish on the same stream.
+static int greedy_rows_tick(mdr_ctx* c, int t, int n, const double* r, double* stats, double* p_out, hipStream_t st) {
+  const int slot = t % kTickRowsBatch;
+  unsigned nb = 0;
+  if (int rc = launch_tick_partials(c, r, c->d_rows_part + (size_t)slot * kTickBlocks * kStats, &nb, st)) return rc;
+  if (slot == kTickRowsBatch - 1 || t == n - 1) {
+    hipLaunchKernelGGL(k_tick_rows_finish, dim3(slot + 1), dim3(kTickBlock), 0, st, (const double*)c->d_rows_part,
+                       (int)nb, (const double*)c->d_rows_p, stats + (size_t)(t - slot) * kTickRow,
+                       t == n - 1 ? p_out : nullptr);
+    LAUNCH_CHECK("k_tick_rows_finish");
+  }
+  return MDR_OK;
+}
+
+// mdr_greedy_rollout (stats == NULL) and mdr_greedy_rollout_stats (stats = the row of the call's
+// first tick): without rows, launch for launch the sequence as it was before there were any
+static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
+                              double* reward, int64_t rew_stride, double* p_out, double* stats, void* stream) {
   hipStream_t st = S(stream);
   // the fused tick (MDR_OPT_GQ_FUSED): individual_L2 on the software-pipelined step, <= 4 classes
   const bool fused = c->gq_fused && !c->greedy_sort && c->kp.n_cap <= 4 && c->tpw >= 1 && c->fastdiv &&
@@ -2163,10 +2184,13 @@ int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action
       hipLaunchKernelGGL(k_gq_decide2, dim3(kGqSelBlocks), dim3(1024), 0, st, c->kp, c->fz, par, ticks[t].s_prev, pmin,
                          slab_at(c, c->ring), c->g_tickets, (const double*)c->g_part, c->gq_nparts);
       LAUNCH_CHECK("k_gq_decide2");
-      if (int rc = launch_step_fused(c, to_tick(&ticks[t]), reward + (int64_t)t * rew_stride,
-                                     action ? action + (int64_t)t * act_stride : nullptr, p_out, par, st))
+      double* r = reward + (int64_t)t * rew_stride;
+      if (int rc = launch_step_fused(c, to_tick(&ticks[t]), r, action ? action + (int64_t)t * act_stride : nullptr,
+                                     stats ? c->d_rows_p + t % kTickRowsBatch : p_out, par, st))
         return rc;
       par = 1 - par;
+      if (stats)
+        if (int rc = greedy_rows_tick(c, t, n, r, stats, p_out, st)) return rc;
     }
     c->fz_par = par;
     c->fz_ready = true;
@@ -2193,14 +2217,43 @@ int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action
     c->gq_s2 = c->gq_s1;
     c->gq_s1 = sb;
     if (int rc = launch_step(c, a, MDR_ACT_BUFFER, to_tick(&ticks[t]), nullptr, r, 0, MDR_CTRL_GREEDY_KEYS, nullptr,
-                             p_out, st))
+                             stats ? c->d_rows_p + t % kTickRowsBatch : p_out, st))
       return rc;
     if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2) {  // (Environment.step_tensor's common-penalty tail)
       if (int rc = mdr_penalty_partials(c, stream)) return rc;
       if (int rc = mdr_reward_finalize(c, &ticks[t], r, stream)) return rc;
     }
+    if (stats)  // the post-step state with this tick's final rewards
+      if (int rc = greedy_rows_tick(c, t, n, r, stats, p_out, st)) return rc;
   }
   return MDR_OK;
+}
+
+int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
+                       double* reward, int64_t rew_stride, double* p_out, void* stream) {
+  if (!c || (n > 0 && (!ticks || !action || !reward))) return fail(MDR_EARG, "mdr_greedy_rollout: null argument");
+  if (n < 0 || act_stride < 0 || rew_stride < 0) return fail(MDR_EARG, "mdr_greedy_rollout: negative size");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_rollout: context not bound");
+  if (c->world > 1)  // (a shard-local decision and step would use shard-local counts: per-tick loop)
+    return fail(MDR_ESTATE, "mdr_greedy_rollout: single-GPU only (sharded contexts: the per-tick greedy + step loop)");
+  return greedy_rollout_seq(c, n, ticks, action, act_stride, reward, rew_stride, p_out, nullptr, stream);
+}
+
+int mdr_greedy_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
+                             double* reward, int64_t rew_stride, double* p_out, double* stats, int row0,
+                             void* stream) {
+  // (the checks of the plain arguments first: they need no context, so no device either)
+  if (n < 0 || act_stride < 0 || rew_stride < 0) return fail(MDR_EARG, "mdr_greedy_rollout_stats: negative size");
+  if (row0 < 0) return fail(MDR_EARG, "mdr_greedy_rollout_stats: negative row0");
+  if (n > 0 && !stats) return fail(MDR_EARG, "mdr_greedy_rollout_stats: null stats rows (mdr_greedy_rollout writes none)");
+  if (!c || (n > 0 && (!ticks || !action || !reward)))
+    return fail(MDR_EARG, "mdr_greedy_rollout_stats: null argument");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_rollout_stats: context not bound");
+  if (int rc = check_tick_stats_ctx(c, "mdr_greedy_rollout_stats")) return rc;
+  if (n == 0) return MDR_OK;
+  if (int rc = rows_scratch(c)) return rc;
+  return greedy_rollout_seq(c, n, ticks, action, act_stride, reward, rew_stride, p_out,
+                            stats + (size_t)row0 * kTickRow, stream);
 }
 
 int mdr_greedy_band(mdr_ctx* c, uint64_t* out) {
@@ -3042,25 +3095,49 @@ static int tick_scratch(mdr_ctx* c) {
   return MDR_OK;
 }
 
+// mdr_greedy_rollout_stats' slabs: a batch of kTickRowsBatch ticks' block partials and cluster powers
+static int rows_scratch(mdr_ctx* c) {
+  if (c->d_rows_part && c->d_rows_p) return MDR_OK;
+  const size_t bytes = sizeof(double) * kStats * kTickBlocks * kTickRowsBatch;
+  if (!c->d_rows_part) {
+    HIP_TRY(hipMalloc(&c->d_rows_part, bytes));
+    HIP_TRY(hipMemset(c->d_rows_part, 0, bytes));
+  }
+  if (!c->d_rows_p) {
+    HIP_TRY(hipMalloc(&c->d_rows_p, sizeof(double) * kTickRowsBatch));
+    HIP_TRY(hipMemset(c->d_rows_p, 0, sizeof(double) * kTickRowsBatch));
+  }
+  return MDR_OK;
+}
+
 static int check_tick_stats_ctx(mdr_ctx* c, const char* who) {
   if (has_comm(c) || c->world > 1)
     return fail(MDR_ESTATE, std::string(who) + ": stats rows are single-shard (a row sums this shard's houses only)");
   return MDR_OK;
 }
 
-static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* row,
-                             hipStream_t st) {
+// k_tick_stats over the bound state (+ reward) into partial[nb][kStats]; the instantiation follows
+// the pointers' alignment (mdr_kernels.hip)
+static int launch_tick_partials(mdr_ctx* c, const double* reward, double* partial, unsigned* nb_out, hipStream_t st) {
   const unsigned nb = std::max(1u, std::min(blocks(blocks(c->kp.n, kTickHpt), kTickBlock), (unsigned)kTickBlocks));
   const KParams& k = c->kp;
   const bool vs = (((uintptr_t)k.t_air | (uintptr_t)k.t_mass | (uintptr_t)k.target | (uintptr_t)k.hvac) & 15) == 0;
   const bool vr = reward && ((uintptr_t)reward & 15) == 0;
 #define MDR_LAUNCH_TICK(R, VS, VR) \
-  hipLaunchKernelGGL((k_tick_stats<R, VS, VR>), dim3(nb), dim3(kTickBlock), 0, st, c->kp, reward, c->d_tick_part)
+  hipLaunchKernelGGL((k_tick_stats<R, VS, VR>), dim3(nb), dim3(kTickBlock), 0, st, c->kp, reward, partial)
   if (!reward) { if (vs) MDR_LAUNCH_TICK(false, true, false); else MDR_LAUNCH_TICK(false, false, false); }
   else if (vs) { if (vr) MDR_LAUNCH_TICK(true, true, true); else MDR_LAUNCH_TICK(true, true, false); }
   else { if (vr) MDR_LAUNCH_TICK(true, false, true); else MDR_LAUNCH_TICK(true, false, false); }
 #undef MDR_LAUNCH_TICK
   LAUNCH_CHECK("k_tick_stats");
+  *nb_out = nb;
+  return MDR_OK;
+}
+
+static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, double* row,
+                             hipStream_t st) {
+  unsigned nb = 0;
+  if (int rc = launch_tick_partials(c, reward, c->d_tick_part, &nb, st)) return rc;
   hipLaunchKernelGGL(k_tick_stats_finish, dim3(1), dim3(kTickBlock), 0, st, c->d_tick_part, (int)nb, p_dev, p_host, row);
   LAUNCH_CHECK("k_tick_stats_finish");
   return MDR_OK;

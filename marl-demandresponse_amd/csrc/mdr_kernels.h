@@ -239,6 +239,11 @@ constexpr int kTickBlocks = 1024; // grid cap (as kStatsBlocks caps k_cluster_st
 template <bool HAS_R, bool VS, bool VR>
 __global__ void k_tick_stats(KParams p, const double* reward, double* partial);
 __global__ void k_tick_stats_finish(const double* partial, int nblk, const double* p_dev, double p_host, double* row);
+// the rows of a greedy rollout (mdr_greedy_rollout_stats): every tick's k_tick_stats writes slot
+// t mod kTickRowsBatch of [kTickRowsBatch][kTickBlocks][kStats] partials and its step one P of a
+// [kTickRowsBatch] slab; one launch per batch, a block per tick, writes the batch's rows
+constexpr int kTickRowsBatch = 32;
+__global__ void k_tick_rows_finish(const double* part, int nblk, const double* p_slab, double* rows, double* p_last);
 // the stats rows of a closed-loop window (mdr_rollout_stats): one block of kTickBlock threads per
 // tick, from k_step_closed<..., true>'s block partials and the window slot's counts and records
 __global__ void k_closed_stats(KParams p, const double* wstat, int nblk, unsigned long long* slot, double* rows);

@@ -2527,6 +2527,42 @@ __global__ void __launch_bounds__(kTickBlock) k_tick_stats_finish(const double* 
   else if (k < kTickRow) row[k] = 0.0;
 }
 
+// The batched finish of a greedy rollout's rows (mdr_greedy_rollout_stats): block j of the grid
+// writes the row of the batch's tick j from slot j of part[kTickRowsBatch][kTickBlocks][kStats],
+// where that tick's k_tick_stats left its nblk block partials, and row[12] from slot j of the P
+// slab its step wrote.  k_tick_stats_finish's order — thread i adds partials i, i + 256, ... in
+// index order (slot 2 by fmax from 0), then tick_block_reduce — so a row has the bits of
+// k_tick_stats_finish on that tick.  The last block also stores its P to p_last (null: the call
+// goes on).  Stream order is the only hand-off: the partial passes in front, the next batch's behind.
+__global__ void __launch_bounds__(kTickBlock) k_tick_rows_finish(const double* __restrict__ part, int nblk,
+                                                                 const double* __restrict__ p_slab,
+                                                                 double* __restrict__ rows, double* p_last) {
+  __shared__ double sh[kStats][4];
+  const int j = blockIdx.x;
+  double a[kStats];
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+  const double* slot = part + (size_t)j * kTickBlocks * kStats;
+  for (int b = threadIdx.x; b < nblk; b += kTickBlock)
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) {
+      const double o = slot[(size_t)b * kStats + k];
+      a[k] = k == 2 ? fmax(a[k], o) : a[k] + o;
+    }
+  const double v = tick_block_reduce(a, sh);
+  double* row = rows + (size_t)j * kTickRow;
+  const int k = threadIdx.x;
+  if (k < kStats) {
+    row[k] = v;
+  } else if (k == kStats) {
+    const double P = p_slab[j];
+    row[k] = P;
+    if (p_last && j == (int)gridDim.x - 1) *p_last = P;
+  } else if (k < kTickRow) {
+    row[k] = 0.0;
+  }
+}
+
 // Finish of a STATS window (behind k_step_closed<..., true>, k_win_reduce and k_closed_reward): one
 // block per tick j of the window writes stats row j of kTickRow doubles.  Thread t adds the block
 // partials wstat[j][t], [t + 256], ... in index order, then tick_block_reduce (the butterfly and wave

@@ -170,6 +170,7 @@ SIGNATURES = {
     "mdr_greedy_state": (I, [VP, VP]),
     "mdr_greedy_band": (I, [VP, VP]),
     "mdr_greedy_rollout": (I, [VP, I, VP, VP, I64, VP, I64, VP, VP]),
+    "mdr_greedy_rollout_stats": (I, [VP, I, VP, VP, I64, VP, I64, VP, VP, I, VP]),
     "mdr_build_id": (C.c_char_p, []),
     "mdr_greedy_inputs": (I, [VP, VP, VP, VP, VP]),
     "mdr_greedy_select": (I, [VP, I64, VP, VP, VP, D, VP, VP]),

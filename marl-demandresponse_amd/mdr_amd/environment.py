@@ -692,16 +692,30 @@ class Environment:
         self._counts_ready = 0
         return rewards
 
-    def greedy_rollout(self, n_ticks: int, actions=None, rewards=None):
+    def greedy_rollout(self, n_ticks: int, actions=None, rewards=None, stats=None):
         """Config C3's loop for n_ticks: ``greedy_actions`` then ``step_tensor(actions,
         ctrl='greedy_keys')`` every tick, as one C call per driver window (mdr_greedy_rollout: no
         Python between the ticks).  ``actions``: uint8 [n_ticks, N] (every tick's decisions) or a
         1-D [N] buffer every tick overwrites (allocated if None); ``rewards`` likewise (float64).
-        Sharded, or a comm mode that draws per tick: the per-tick loop.  Returns (actions, rewards)."""
+        Sharded, or a comm mode that draws per tick: the per-tick loop.  Returns (actions, rewards).
+
+        ``stats`` (mdr_amd.services.RolloutStats, the contract of ``rollout``): each tick's row — the
+        cluster statistics of the post-step state, its final rewards and the cluster power — is
+        written inside the launch sequence (mdr_greedy_rollout_stats: one partial pass per tick, one
+        finish launch per 32 ticks), bit for bit ``shard.tick_stats`` after every tick of the
+        per-tick loop, which is what the per-tick fallback here does.  ``ValueError``: rows of
+        another env, or more ticks than the rows left; a context with a communicator is refused
+        (MdrError) before the drivers advance."""
         import torch
 
         sh = self._shard
         n = self._n_local
+        srow0 = 0
+        if stats is not None:
+            if stats.env is not self:
+                raise ValueError("the stats rows belong to another environment")
+            srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
+            sh.greedy_rollout_stats_check()  # (MdrError: a communicator; nothing is launched)
         if actions is None:
             actions = torch.empty(n, dtype=torch.uint8, device=sh.device)
         if rewards is None:
@@ -716,17 +730,32 @@ class Environment:
                 or self._grid_pending):
             for t in range(n_ticks):
                 a = actions[t] if a_st else actions
+                if stats is not None:
+                    if t == 0:
+                        stats.record_power(srow0)
+                    s_prev, od = self.power_grid.current_signal, self.current_od_temp
                 self.greedy_actions(out=a)
-                self.step_tensor(a, rewards=rewards[t] if r_st else rewards, ctrl="greedy_keys")
+                r = self.step_tensor(a, rewards=rewards[t] if r_st else rewards, ctrl="greedy_keys")
+                if stats is not None:
+                    sh.tick_stats(r, stats.stats[srow0 + t])
+                    stats.commit_rows([s_prev], [od], [self.power_grid.current_signal], first=(t == 0))
             return actions, rewards
         done = 0
         while done < n_ticks:  # one window unless interpolation ends it early (driver_window)
             ticks = self.driver_window(n_ticks - done)
             k = len(ticks)
-            sh.greedy_rollout(ticks, actions[done:] if a_st else actions, a_st,
-                              rewards[done:] if r_st else rewards, r_st)
+            a, r = actions[done:] if a_st else actions, rewards[done:] if r_st else rewards
+            if stats is not None:
+                if done == 0:
+                    stats.record_power(srow0)
+                sh.greedy_rollout_stats(ticks, a, a_st, r, r_st, stats.stats, srow0 + done)
+            else:
+                sh.greedy_rollout(ticks, a, a_st, r, r_st)
             self._P_dev_valid = True
             self.finish_grid_step()
+            if stats is not None:  # tick t's post-step signal is tick t + 1's s_prev; the last one's is the grid's
+                post = list(ticks.s_prev[1:]) + [self.power_grid.current_signal]
+                stats.commit_rows(ticks.s_prev, ticks.t_od_prev, post, first=(done == 0))
             done += k
         self._counts_ready = 0
         return actions, rewards

@@ -12,7 +12,8 @@ per-house UI list is materialised only when read.
                  tick written inside a rollout: ``mdr_tick_stats``)  training_manager.py:242-245,265-295
   UISummary      ClientManagerService  server/app/services/client_manager_service.py:12-245
   ServerLoop     ControllerManager     server/app/services/controller_manager.py:93-260
-  evaluate_controller  TrainingManager.test for the bang-bang baselines  training_manager.py:265-295
+  evaluate_controller  TrainingManager.test for the bang-bang and greedy-myopic baselines
+                                                                 training_manager.py:265-295
 
 Floating-point sums over houses are reduced in a fixed blocked order on the device, where the
 reference adds house by house; they agree to rounding (tests/test_services_gpu.py: rtol 1e-12).
@@ -270,6 +271,9 @@ def evaluation_means(rows, signal_post, n: int, n_ticks: int) -> dict:
 
 
 BANGBANG_CONTROLLERS = ("bangbang", "deadband_bangbang")
+# the controllers whose rollouts write their own stats rows: ``rollout(action_mode=c, stats=...)`` for the
+# bang-bang pair, ``greedy_rollout(stats=...)`` for GreedyMyopic (config C3)
+ROLLOUT_CONTROLLERS = BANGBANG_CONTROLLERS + ("greedy",)
 
 
 def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
@@ -277,7 +281,9 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
     'deadband_bangbang' (bangbang_controllers.py:25-65): the controller run for ``n_ticks`` on a reset
     copy of ``env`` as ONE ``rollout(n_ticks, action_mode=controller, stats=...)`` — closed-loop windows
     writing their own stats rows where they apply — and ``evaluation_means`` of the rows, the values
-    ``DeviceMAPPO.evaluate`` reports for a policy.  ``twin`` None: ``copy.deepcopy(env)`` as the
+    ``DeviceMAPPO.evaluate`` reports for a policy.  'greedy' (GreedyMyopic,
+    greedy_myopic_controller.py:67-104): ONE ``greedy_rollout(n_ticks, stats=...)`` with one action
+    and one reward row every tick overwrites.  ``twin`` None: ``copy.deepcopy(env)`` as the
     reference does; a caller-kept twin may be passed instead, whose context, row and reward buffers
     and rollout graph are then reused by later calls.  The copy is ``reset`` (which advances the
     shared RNG, as in the reference); ``env``'s device state, tick, date and P are not touched."""
@@ -285,8 +291,8 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
 
     import torch
 
-    if controller not in BANGBANG_CONTROLLERS:
-        raise ValueError(f"evaluate_controller: controller must be one of {BANGBANG_CONTROLLERS}, not {controller!r}")
+    if controller not in ROLLOUT_CONTROLLERS:
+        raise ValueError(f"evaluate_controller: controller must be one of {ROLLOUT_CONTROLLERS}, not {controller!r}")
     if n_ticks < 1:
         raise ValueError("n_ticks must be at least 1")
     ev = copy.deepcopy(env) if twin is None else twin
@@ -302,7 +308,12 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
     stats = kept["stats"]
     stats.clear()
     # (one reward row: the windows finalise only the last tick's rewards, the rows need none of them)
-    ev.rollout(n_ticks, action_mode=controller, rewards=kept["rewards"], use_graph=twin is not None, stats=stats)
+    if controller == "greedy":
+        if "actions" not in kept:
+            kept["actions"] = torch.empty(ev.n_local, dtype=torch.uint8, device=ev.shard.device)
+        ev.greedy_rollout(n_ticks, actions=kept["actions"], rewards=kept["rewards"], stats=stats)
+    else:
+        ev.rollout(n_ticks, action_mode=controller, rewards=kept["rewards"], use_graph=twin is not None, stats=stats)
     return evaluation_means(stats.host(), stats.prev()["signal_post"], ev.n, n_ticks)
 
 
@@ -439,18 +450,18 @@ class ServerLoop:
     periodic log.  ``controller``: 'deadband_bangbang' / 'bangbang' / 'always_on' / 'random' (fused
     in the step kernel), 'greedy' (device GreedyMyopic), or a callable env -> uint8 device actions.
     Per-house Python objects are only built on access (UISummary.houses_data).
-    ``rollout_ticks`` = K > 0 (the two bang-bang controllers): ``run`` advances in chunks of up to K
-    ticks, each one rollout whose stats rows feed the Metrics, with one UI update per chunk."""
+    ``rollout_ticks`` = K > 0 (the two bang-bang controllers and 'greedy'): ``run`` advances in chunks
+    of up to K ticks, each one rollout whose stats rows feed the Metrics, with one UI update per chunk."""
 
     def __init__(self, env, controller="deadband_bangbang", start_stats_from: int = 0, nb_time_steps: int = 1000,
                  time_steps_per_episode: int = 10 ** 9, time_steps_train_log: int = 10 ** 9, interface: bool = False,
                  metrics=None, ui=None, rollout_ticks: int = 0):
         if rollout_ticks < 0:
             raise ValueError("rollout_ticks must be >= 0")
-        if rollout_ticks and controller not in BANGBANG_CONTROLLERS:
-            raise ValueError(f"rollout_ticks needs one of the controllers {BANGBANG_CONTROLLERS}")
+        if rollout_ticks and controller not in ROLLOUT_CONTROLLERS:
+            raise ValueError(f"rollout_ticks needs one of the controllers {ROLLOUT_CONTROLLERS}")
         self.rollout_ticks = int(rollout_ticks)
-        self._rows = None  # RolloutStats of rollout_ticks rows + the chunks' one reward row
+        self._rows = None  # RolloutStats of rollout_ticks rows + the chunks' one reward (greedy: and action) row
         self.env = env
         self.controller = controller
         self.metrics = metrics or DeviceMetrics()
@@ -476,7 +487,8 @@ class ServerLoop:
 
     def _run_chunks(self, end: int) -> None:
         """``run``'s loop for ``rollout_ticks`` = K > 0: chunks of up to K ticks as one
-        ``env.rollout(k, action_mode=controller, stats=...)`` each, cut at episode ends, log
+        ``env.rollout(k, action_mode=controller, stats=...)`` (``env.greedy_rollout(k, stats=...)``
+        for 'greedy') each, cut at episode ends, log
         boundaries and ``end``; ``ui.update_data`` once at each chunk's start; Metrics from the
         chunk's rows (``DeviceMetrics.update_rollout``: the per-tick arithmetic in its order)."""
         import torch
@@ -484,15 +496,20 @@ class ServerLoop:
         env = self.env
         if self._rows is None:
             self._rows = (RolloutStats(env, self.rollout_ticks),
-                          torch.empty(env.n_local, dtype=torch.float64, device=env.shard.device))
-        stats, rewards = self._rows
+                          torch.empty(env.n_local, dtype=torch.float64, device=env.shard.device),
+                          torch.empty(env.n_local, dtype=torch.uint8, device=env.shard.device)
+                          if self.controller == "greedy" else None)
+        stats, rewards, actions = self._rows
         ep, lg = self.time_steps_per_episode, self.time_steps_train_log
         while self.current_time_step < end:
             step = self.current_time_step
             k = min(self.rollout_ticks, end - step, ep - step % ep, lg - step % lg)
             self.ui.update_data(env, step)
             stats.clear()
-            env.rollout(k, action_mode=self.controller, rewards=rewards, stats=stats)
+            if self.controller == "greedy":
+                env.greedy_rollout(k, actions=actions, rewards=rewards, stats=stats)
+            else:
+                env.rollout(k, action_mode=self.controller, rewards=rewards, stats=stats)
             self.metrics.update_rollout(stats, step)
             last = step + k - 1
             if last % ep == ep - 1:

@@ -266,6 +266,22 @@ class HipShard:
                                             L.ptr(reward), rew_stride, L.ptr(self.p_dev), self.stream()),
                 "mdr_greedy_rollout")
 
+    def greedy_rollout_stats(self, ticks, action, act_stride, reward, rew_stride, stats, row0: int):
+        """``greedy_rollout`` that also writes tick t's stats row into ``stats[row0 + t]`` (device
+        float64 [rows, 16]) inside the same launch sequence (mdr_greedy_rollout_stats): one partial
+        pass per tick, one finish launch per 32 ticks; the rows of ``tick_stats`` after every tick."""
+        if row0 < 0 or row0 + len(ticks) > stats.shape[0]:
+            raise ValueError(f"stats rows {row0} .. {row0 + len(ticks)} outside [0, {stats.shape[0]})")
+        L.check(self.lib.mdr_greedy_rollout_stats(self.ctx, len(ticks), ticks.ptr(), L.ptr(action), act_stride,
+                                                  L.ptr(reward), rew_stride, L.ptr(self.p_dev), L.ptr(stats),
+                                                  int(row0), self.stream()), "mdr_greedy_rollout_stats")
+
+    def greedy_rollout_stats_check(self) -> None:
+        """MdrError where mdr_greedy_rollout_stats would refuse this context (a communicator, a
+        shard of several): its zero-tick call, which runs the checks and launches nothing."""
+        L.check(self.lib.mdr_greedy_rollout_stats(self.ctx, 0, None, None, 0, None, 0, None, None, 0, self.stream()),
+                "mdr_greedy_rollout_stats")
+
     # ---- sharded histogram select (mdr_gq_shard_*): the stages between the comm's collectives
     def gq_shard_begin(self) -> dict:
         """This shard's key codes, superbin histogram and key range; returns zero-copy views of the
