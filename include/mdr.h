@@ -642,8 +642,9 @@ int mdr_actor_rollout_sharded(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, 
  * its neighbours' t_air, t_mass and hvac word, the tick's four obs scalars and parameters that are
  * fixed between resets, so a snapshot keeps 8 + 8 + 4 B per house-tick and one scalar row per tick,
  * and mdr_obs_gather rebuilds any transition's row on demand, bit-identical to mdr_obs of that tick.
- * Single shard only (a neighbour's snapshot would live on another shard): a context with a
- * communicator or world > 1 gives MDR_ESTATE. */
+ * These entry points are single shard only (a neighbour's snapshot would live on another shard): a
+ * context with a communicator or world > 1 gives MDR_ESTATE.  A shard of a 'neighbours' ring cluster
+ * takes the sharded forms further down (mdr_snap_halo), which keep the tick's ring halo as well. */
 typedef struct mdr_snap {
   int32_t struct_bytes;   /* = sizeof(mdr_snap); anything else is MDR_EARG ("mdr_snap" in mdr_last_error) */
   int32_t cap_rows;       /* ticks the slabs hold */
@@ -694,6 +695,51 @@ int mdr_actor_rollout_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, co
  * m < 0, a spec with halo_msg or msg_all set, a NULL slab. */
 int mdr_obs_gather(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_snap* snap, int rows, const int64_t* idx,
                    int64_t m, float* obs, void* stream);
+
+/* ---- replay snapshots of a house-sharded ring cluster (MA-PPO training on config C5) ----------- */
+/* A 'neighbours' ring obs row of a shard reads at most lo = n_comm / 2 houses before the shard and
+ * hi = (n_comm + 1) / 2 after it, and only their message features: the ring halo that the sharded
+ * actor reads every tick.  Stored beside the snapshot row ((lo + hi) * msg_w floats per tick, at most
+ * 440 B), it makes every local obs row rebuildable on its own rank.  The entry points above keep
+ * their single-shard refusals; these are the sharded forms. */
+typedef struct mdr_snap_halo {
+  int32_t struct_bytes;   /* = sizeof(mdr_snap_halo); anything else is MDR_EARG ("mdr_snap_halo" in mdr_last_error) */
+  int32_t cap_rows;       /* ticks the slab holds, >= the mdr_snap rows used with it */
+  int64_t row_stride;     /* floats between rows, >= (lo + hi) * msg_w */
+  float* rows;            /* [cap_rows][row_stride], caller-owned device memory: row t = the halo of
+                           * tick t in the layout of mdr_obs_spec.halo_msg, [lo rows of the houses
+                           * before the shard | hi rows of the houses after it], msg_w floats each */
+} mdr_snap_halo;
+/* mdr_snapshot for per-tick loops on a shard: one launch writes snapshot row `row` and copies
+ * halo_src — device [lo + hi][msg_w] floats, the halo the caller's exchange produced for this tick's
+ * obs (what it passes as mdr_obs_spec.halo_msg) — into row `row` of halo.  Needs `spec` for lo, hi and
+ * msg_w.  halo and halo_src may both be NULL when the obs reads no halo (n_comm == 0).  MDR_ESTATE: a
+ * context that is neither sharded (n_local < n_global) nor has a communicator.  MDR_EARG: mdr_snapshot's,
+ * a TABLE comm mode, a row outside the halo slab, a short halo stride, a NULL slab or halo_src while
+ * n_comm > 0. */
+int mdr_snapshot_sharded(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_snap* snap, const mdr_snap_halo* halo,
+                         int row, const mdr_obs_scalars* sc, const double* p_dev, const float* halo_src,
+                         void* stream);
+/* mdr_actor_rollout_sharded that also records tick t's pre-step state, its obs scalars and the ring
+ * halo its actor reads into row row0 + t of snap / halo, in all three forms of the loop (one launch
+ * per tick, before the tick's step, after the halo's arrival and before the halo buffer's next reuse;
+ * tick 0's halo is that of the exchange before the loop).  snap == NULL is mdr_actor_rollout_sharded,
+ * launch for launch.  MDR_EARG, before anything is launched: rows outside [0, cap_rows) of either
+ * struct, a short stride, a NULL slab, halo == NULL while a halo is exchanged (world > 1 or
+ * MDR_OPT_FORCE_HALO, with n_comm > 0).  MDR_ESTATE: no communicator. */
+int mdr_actor_rollout_sharded_snap(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const mdr_obs_scalars* obs_sc,
+                                   const mdr_obs_spec* obs, uint8_t* action, int64_t act_stride, float* prob,
+                                   int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                                   const mdr_snap* snap, const mdr_snap_halo* halo, int row0, void* stream);
+/* mdr_obs_gather on a shard: idx are local (tick * n_local + local house); the sources of a ring obs
+ * outside the shard come from halo row `tick`, so the rows are bit-identical to mdr_obs /
+ * mdr_actor_act on this rank at that tick.  halo may be NULL only when no halo is read (n_comm == 0,
+ * or a communicator at world 1 without MDR_OPT_FORCE_HALO: the local wrap-around).  MDR_ESTATE: a
+ * context that is neither sharded nor has a communicator.  MDR_EARG: mdr_obs_gather's, a spec with
+ * halo_msg or msg_all set (the halo comes from the slab), a TABLE comm mode, rows > halo->cap_rows, a
+ * short halo stride, a NULL slab. */
+int mdr_obs_gather_sharded(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_snap* snap, const mdr_snap_halo* halo,
+                           int rows, const int64_t* idx, int64_t m, float* obs, void* stream);
 
 /* ---- interpolated base power ---------------------------------------- */
 /* Replaces PowerInterpolator (server/app/core/environment/power_grid/interpolation.py:24-264) as

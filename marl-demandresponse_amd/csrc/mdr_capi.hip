@@ -3160,10 +3160,16 @@ static int check_snap_struct(const mdr_snap* sn, const char* who) {
   return MDR_OK;
 }
 
+static int check_snap_slabs(mdr_ctx* c, const mdr_snap* sn, int row0, int nrows, const char* who);
+
 // rows [row0, row0 + nrows) of the caller's slabs can take this context's houses
 static int check_snap(mdr_ctx* c, const mdr_snap* sn, int row0, int nrows, const char* who) {
   if (has_comm(c) || c->world > 1)
     return fail(MDR_ESTATE, std::string(who) + ": snapshots are single-shard (a neighbour's rows live on another shard)");
+  return check_snap_slabs(c, sn, row0, nrows, who);
+}
+
+static int check_snap_slabs(mdr_ctx* c, const mdr_snap* sn, int row0, int nrows, const char* who) {
   if (!sn->t_air || !sn->t_mass || !sn->hvac || !sn->scalars) return fail(MDR_EARG, std::string(who) + ": null snapshot slab");
   if (sn->row_stride < c->kp.n) return fail(MDR_EARG, std::string(who) + ": mdr_snap.row_stride < n_local");
   if (sn->cap_rows < 0 || row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > sn->cap_rows)
@@ -3211,6 +3217,114 @@ int mdr_obs_gather(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, int r
   hipLaunchKernelGGL(k_obs_gather, dim3(blocks(m, kGatherRows)), dim3(kGatherRows * kGatherLanes), bytes, S(stream),
                      c->kp, o, sn->t_air, sn->t_mass, sn->hvac, sn->row_stride, sn->scalars, rows, idx, m, obs);
   LAUNCH_CHECK("k_obs_gather");
+  return MDR_OK;
+}
+
+// ---- the sharded forms (mdr.h mdr_snap_halo): the ring halo of the tick beside its snapshot row
+static int check_snap_halo_struct(const mdr_snap_halo* hl, const char* who) {
+  if (hl->struct_bytes != (int32_t)sizeof(mdr_snap_halo))
+    return fail(MDR_EARG, std::string(who) + ": mdr_snap_halo.struct_bytes is not sizeof(mdr_snap_halo)");
+  return MDR_OK;
+}
+
+// a shard of a larger cluster (its collectives may be the caller's: no communicator) or a context
+// with a communicator (world 1 included: the exchanges to self)
+static bool ctx_sharded(const mdr_ctx* c) { return has_comm(c) || c->world > 1 || c->kp.n < c->kp.n_global; }
+
+// rows [row0, row0 + nrows) of the halo slab can take `need` floats each
+static int check_snap_halo(const mdr_snap_halo* hl, int64_t need, int row0, int nrows, const char* who) {
+  if (!hl->rows) return fail(MDR_EARG, std::string(who) + ": null halo slab");
+  if (hl->row_stride < need) return fail(MDR_EARG, std::string(who) + ": mdr_snap_halo.row_stride < (lo + hi) * msg_w");
+  if (hl->cap_rows < 0 || row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > hl->cap_rows)
+    return fail(MDR_EARG, std::string(who) + ": halo rows outside [0, cap_rows)");
+  return MDR_OK;
+}
+
+// k_snap_halo: snapshot row `row` and nlo floats at halo_lo, nhi at halo_hi into halo row `row`
+static int launch_snap_halo(mdr_ctx* c, const mdr_snap* sn, const mdr_snap_halo* hl, int row, const double* sc_dev,
+                            const double* p_dev, const mdr_obs_scalars& sc, const float* halo_lo,
+                            const float* halo_hi, int nlo, int nhi, hipStream_t st) {
+  const int64_t off = (int64_t)row * sn->row_stride;
+  const unsigned grid = std::max(1u, std::min(blocks((c->kp.n + 1) / 2, kSnapBlock), (unsigned)kSnapGrid));
+  float* hrow = hl && hl->rows ? hl->rows + (int64_t)row * hl->row_stride : nullptr;
+  if (!hrow) nlo = nhi = 0;
+  hipLaunchKernelGGL(k_snap_halo, dim3(grid), dim3(kSnapBlock), 0, st, c->kp, sn->t_air + off, sn->t_mass + off,
+                     sn->hvac + off, sn->scalars + 4 * (int64_t)row, p_dev, sc_dev, sc.p, sc.s, sc.solar, sc.t_od,
+                     halo_lo, halo_hi, nlo, nhi, hrow);
+  LAUNCH_CHECK("k_snap_halo");
+  return MDR_OK;
+}
+
+int mdr_snapshot_sharded(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, const mdr_snap_halo* hl, int row,
+                         const mdr_obs_scalars* sc, const double* p_dev, const float* halo_src, void* stream) {
+  const char* who = "mdr_snapshot_sharded";
+  if (sn)
+    if (int rc = check_snap_struct(sn, who)) return rc;
+  if (hl)
+    if (int rc = check_snap_halo_struct(hl, who)) return rc;
+  if (!c || !sp || !sn || !sc) return fail(MDR_EARG, std::string(who) + ": null argument");
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (!ctx_sharded(c)) return fail(MDR_ESTATE, std::string(who) + ": not a shard and no communicator (mdr_snapshot)");
+  if (int rc = check_obs_spec(sp, who)) return rc;
+  const int K = sp->n_comm, M = mdr_msg_width(sp), lo = K / 2, hi = (K + 1) / 2;
+  if (K > 0 && sp->comm_mode != MDR_COMM_RING)
+    return fail(MDR_EARG, std::string(who) + ": across shards only the 'neighbours' ring obs is supported");
+  if (int rc = check_snap_slabs(c, sn, row, 1, who)) return rc;
+  if (K > 0) {
+    if (!hl || !halo_src) return fail(MDR_EARG, std::string(who) + ": the obs reads a ring halo: halo and halo_src must be given");
+    if (int rc = check_snap_halo(hl, (int64_t)(lo + hi) * M, row, 1, who)) return rc;
+  }
+  return launch_snap_halo(c, sn, K > 0 ? hl : nullptr, row, nullptr, p_dev, *sc, halo_src,
+                          halo_src ? halo_src + (size_t)lo * M : nullptr, lo * M, hi * M, S(stream));
+}
+
+// the obs of this context read a ring halo of other shards' (or, forced, its own) houses
+static bool reads_halo(const mdr_ctx* c, const mdr_obs_spec* sp) {
+  return sp->n_comm > 0 && sp->comm_mode == MDR_COMM_RING &&
+         (c->world > 1 || c->kp.n < c->kp.n_global || c->force_halo);
+}
+
+int mdr_obs_gather_sharded(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, const mdr_snap_halo* hl, int rows,
+                           const int64_t* idx, int64_t m, float* obs, void* stream) {
+  const char* who = "mdr_obs_gather_sharded";
+  if (sn)
+    if (int rc = check_snap_struct(sn, who)) return rc;
+  if (hl)
+    if (int rc = check_snap_halo_struct(hl, who)) return rc;
+  if (!c || !sp || !sn || m < 0 || (m > 0 && (!idx || !obs))) return fail(MDR_EARG, std::string(who) + ": bad argument");
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (!ctx_sharded(c)) return fail(MDR_ESTATE, std::string(who) + ": not a shard and no communicator (mdr_obs_gather)");
+  if (int rc = check_obs_spec(sp, who)) return rc;
+  if (sp->halo_msg || sp->msg_all)
+    return fail(MDR_EARG, std::string(who) + ": halo_msg / msg_all set (the halo comes from the slab)");
+  if (sp->n_comm > 0 && sp->comm_mode != MDR_COMM_RING)
+    return fail(MDR_EARG, std::string(who) + ": across shards only the 'neighbours' ring obs is supported");
+  if (int rc = check_snap_slabs(c, sn, 0, rows, who)) return rc;
+  const bool halo = reads_halo(c, sp);
+  const int K = sp->n_comm, lo = K / 2, hi = (K + 1) / 2;
+  if (halo) {
+    if (!hl) return fail(MDR_EARG, std::string(who) + ": the obs reads a ring halo: halo must be given");
+    if (int rc = check_snap_halo(hl, (int64_t)(lo + hi) * mdr_msg_width(sp), 0, rows, who)) return rc;
+    if (c->kp.n < (lo > hi ? lo : hi)) return fail(MDR_EARG, std::string(who) + ": shard smaller than the ring half-width");
+  }
+  if (m == 0) return MDR_OK;
+  ObsArgs o = obs_args(c, sp, nullptr);
+  const size_t tile = ((size_t)kGatherRows * sp->n_feat + 3) & ~(size_t)3;
+  const size_t nmsg = (size_t)(sp->comm_mode == MDR_COMM_RING ? sp->n_comm + 1 : 0) * o.msg_w;
+  const size_t bytes = (tile + kGatherRows * (nmsg + kObsConst)) * sizeof(float);
+  if (bytes > 64 * 1024) return fail(MDR_EARG, std::string(who) + ": obs row too wide for one LDS tile");
+  if ((m + kGatherRows - 1) / kGatherRows > 0x7fffffffLL)
+    return fail(MDR_EARG, std::string(who) + ": m too large for one launch");
+  if (halo) {
+    hipLaunchKernelGGL(k_obs_gather_halo, dim3(blocks(m, kGatherRows)), dim3(kGatherRows * kGatherLanes), bytes,
+                       S(stream), c->kp, o, sn->t_air, sn->t_mass, sn->hvac, sn->row_stride, sn->scalars, rows, idx, m,
+                       obs, (const float*)hl->rows, hl->row_stride);
+    LAUNCH_CHECK("k_obs_gather_halo");
+  } else {
+    hipLaunchKernelGGL(k_obs_gather, dim3(blocks(m, kGatherRows)), dim3(kGatherRows * kGatherLanes), bytes, S(stream),
+                       c->kp, o, sn->t_air, sn->t_mass, sn->hvac, sn->row_stride, sn->scalars, rows, idx, m, obs);
+    LAUNCH_CHECK("k_obs_gather");
+  }
   return MDR_OK;
 }
 
@@ -3335,15 +3449,29 @@ int mdr_actor_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_
 //   -> RCCL sum-allreduce of the count slab -> k_step (BUFFER actions, global P)
 // Actions are sampled from Philox keyed by (seed, GLOBAL house id, tick) and the counts are exact
 // integers, so the sharded run is bit-identical to the single-shard one.
-int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                              const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
-                              void* stream) {
-  drop_begun(c);
+// snap != NULL (mdr_actor_rollout_sharded_snap): one k_snap_halo per tick records the state, scalars
+// and halo the tick's actor reads; snap == NULL: mdr_actor_rollout_sharded's launches
+static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                                      const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                                      int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                                      const mdr_snap* snap, const mdr_snap_halo* shalo, int row0, void* stream,
+                                      const char* who) {
+  if (c) drop_begun(c);
+  if (snap)
+    if (int rc = check_snap_struct(snap, who)) return rc;
+  if (snap && shalo)
+    if (int rc = check_snap_halo_struct(shalo, who)) return rc;
   if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1)
     return fail(MDR_EARG, "mdr_actor_rollout_sharded: bad argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_rollout_sharded: context not bound");
   if (!has_comm(c)) return fail(MDR_ESTATE, "mdr_actor_rollout_sharded: no communicator (mdr_rccl_init / mdr_comm_host)");
+  if (snap) {  // (before anything is launched or staged)
+    if (int rc = check_snap_slabs(c, snap, row0, n, who)) return rc;
+    if ((c->world > 1 || c->force_halo) && sp->n_comm > 0) {
+      if (!shalo) return fail(MDR_EARG, std::string(who) + ": a ring halo is exchanged: halo must be given");
+      if (int rc = check_snap_halo(shalo, (int64_t)sp->n_comm * mdr_msg_width(sp), row0, n, who)) return rc;
+    }
+  }
   if (int rc = check_actor_obs(c, sp, "mdr_actor_rollout_sharded", S(stream))) return rc;
   if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
     return fail(MDR_EARG, "mdr_actor_rollout_sharded: common penalty modes need the per-step API");
@@ -3405,6 +3533,13 @@ int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const md
       }
       ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act,
                    prob ? prob + (int64_t)t * prob_stride : nullptr, nullptr, nullptr, buf(t), nullptr};
+      // the halo this tick's actor reads: tick 0's from the exchange above, later ticks' the two parts
+      // of tick t - 1's allreduced rows (stream-ordered after that allreduce, and before this tick's
+      // step and the pack of tick t + 2 that next write buf((t - 1) % 3))
+      if (snap)
+        if (int rc = launch_snap_halo(c, snap, shalo, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{}, ot.halo_msg,
+                                      t > 0 ? ot.halo_next : ot.halo_msg + (size_t)lo * M, lo * M, hi * M, st))
+          return rc;
       if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, out, st)) return rc;
       hipLaunchKernelGGL(k_halo_step_pack, dim3(1), dim3(256), 0, st, c->kp, ot, (const uint8_t*)out.action,
                          (const TickArgs*)(c->d_ticks + t), lo, hi, c->rank, c->world, rows(t));
@@ -3448,12 +3583,19 @@ int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const md
       HIP_TRY(hipEventRecord(c->ev_ar[0], cs));
       HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[0], 0));
       out.tiles = 2;
+      // (recv has landed for the compute stream; the next tick's exchange waits on ev_pc, recorded
+      // after the snapshot launch below)
     } else if (halo) {
       hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, st, c->kp, o, lo, hi, mine);
       LAUNCH_CHECK("k_halo_pack");
       // the previous rank's last lo houses come first in the halo, the next rank's first hi after
       if (int rc = comm_halo(c, mine, recv, lo, hi, M, st)) return rc;
     }
+    // the pre-step state and the halo in recv (none: an empty halo row), before this tick's step
+    if (snap)
+      if (int rc = launch_snap_halo(c, snap, halo ? shalo : nullptr, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{},
+                                    recv, recv ? recv + (size_t)lo * M : nullptr, lo * M, hi * M, st))
+        return rc;
     if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, out, st)) return rc;
     if (int rc = comm_allreduce(c, slab_at(c, c->ring), c->slab_len, 0, st)) return rc;
     if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
@@ -3462,6 +3604,23 @@ int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const md
   }
   c->counts_ready = false;
   return MDR_OK;
+}
+
+int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                              const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                              void* stream) {
+  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
+                                    p_dev, nullptr, nullptr, 0, stream, "mdr_actor_rollout_sharded");
+}
+
+int mdr_actor_rollout_sharded_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                                   const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                                   int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                                   const mdr_snap* snap, const mdr_snap_halo* halo, int row0, void* stream) {
+  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
+                                    p_dev, snap, halo, row0, stream,
+                                    snap ? "mdr_actor_rollout_sharded_snap" : "mdr_actor_rollout_sharded");
 }
 
 }  // extern "C"

@@ -262,6 +262,15 @@ __global__ void k_snap(KParams p, double* t_air, double* t_mass, uint32_t* hvac,
 __global__ void k_obs_gather(KParams p, ObsArgs o, const double* s_air, const double* s_mass, const uint32_t* s_hvac,
                              int64_t row_stride, const double* scalars, int rows, const int64_t* idx, int64_t m,
                              float* obs);
+// the same two on a shard of a ring cluster (mdr_snapshot_sharded / mdr_actor_rollout_sharded_snap /
+// mdr_obs_gather_sharded): the tick's halo rows [lo before | hi after][msg_w] beside the snapshot row
+__global__ void k_snap_halo(KParams p, double* t_air, double* t_mass, uint32_t* hvac, double* sc_row,
+                            const double* p_dev, const double* sc_dev, double P, double s, double solar, double t_od,
+                            const float* halo_lo, const float* halo_hi, int nlo, int nhi, float* halo_row);
+__global__ void k_obs_gather_halo(KParams p, ObsArgs o, const double* s_air, const double* s_mass,
+                                  const uint32_t* s_hvac, int64_t row_stride, const double* scalars, int rows,
+                                  const int64_t* idx, int64_t m, float* obs, const float* halo_rows,
+                                  int64_t halo_stride);
 __global__ void k_greedy_keys(KParams p, double* key, int* idx);
 __global__ void k_greedy_gather(KParams p, const int* perm, double* psorted, uint8_t* lsorted);
 __global__ void k_greedy_walk(int64_t n, const double* incl, const double* psorted,

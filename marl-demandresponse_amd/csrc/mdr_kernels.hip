@@ -2777,16 +2777,45 @@ __global__ void __launch_bounds__(kSnapBlock) k_snap(KParams p, double* __restri
   }
 }
 
+// k_snap on a shard of a ring cluster: the same row, and the ring halo the tick's actor reads —
+// nlo floats at halo_lo (the lo houses before the shard) then nhi floats at halo_hi (the hi houses
+// after it; the one-collective loop keeps the two apart, the other forms pass halo_lo + nlo) — into
+// halo_row, the canonical [lo | hi][msg_w] layout of mdr_obs_spec.halo_msg.  At most 10 x 11 floats.
+__global__ void __launch_bounds__(kSnapBlock)
+    k_snap_halo(KParams p, double* __restrict__ t_air, double* __restrict__ t_mass, uint32_t* __restrict__ hvac,
+                double* __restrict__ sc_row, const double* __restrict__ p_dev, const double* __restrict__ sc_dev,
+                double P, double s, double solar, double t_od, const float* __restrict__ halo_lo,
+                const float* __restrict__ halo_hi, int nlo, int nhi, float* __restrict__ halo_row) {
+  const int64_t gtid = (int64_t)blockIdx.x * kSnapBlock + threadIdx.x;
+  const int64_t gthr = (int64_t)gridDim.x * kSnapBlock;
+  snap_copy<double>(p.t_air, t_air, p.n, gtid, gthr);
+  snap_copy<double>(p.t_mass, t_mass, p.n, gtid, gthr);
+  snap_copy<uint32_t>(p.hvac, hvac, p.n, gtid, gthr);
+  for (int64_t e = gtid; e < nlo + nhi; e += gthr) halo_row[e] = e < nlo ? halo_lo[e] : halo_hi[e - nlo];
+  if (gtid == 0) {
+    sc_row[0] = p_dev ? *p_dev : P;
+    sc_row[1] = sc_dev ? sc_dev[1] : s;
+    sc_row[2] = sc_dev ? sc_dev[2] : solar;
+    sc_row[3] = sc_dev ? sc_dev[3] : t_od;
+  }
+}
+
 // obs[q][0 .. F) = the row k_obs wrote for house idx[q] % p.n at the tick of snapshot row
 // idx[q] / p.n.  kGatherRows transitions per block, kGatherLanes lanes each: the lanes stage the
 // row's obs_consts and (ring) its K + 1 message sources from the snapshot row into the row's own
 // LDS areas, lane 0 assembles the row (mdr_obs_dev.h: the arithmetic of k_obs, so the same bits),
 // then the block flushes its contiguous output rows with 16-B stores.  An index outside
-// [0, rows * p.n) is not dereferenced: its row is NaN.  Single shard (o.halo_msg, o.msg_all null).
-__global__ void __launch_bounds__(kGatherRows* kGatherLanes)
-    k_obs_gather(KParams p, ObsArgs o, const double* __restrict__ s_air, const double* __restrict__ s_mass,
-                 const uint32_t* __restrict__ s_hvac, int64_t row_stride, const double* __restrict__ scalars,
-                 int rows, const int64_t* __restrict__ idx, int64_t m, float* __restrict__ obs) {
+// [0, rows * p.n) is not dereferenced: its row is NaN.  o.halo_msg and o.msg_all are null; a shard's rows: HALO below.
+// HALO (k_obs_gather_halo, a shard of a ring cluster): the row's o.halo_msg is row t of halo_rows, the
+// [lo | hi][msg_w] rows k_snap_halo stored at that tick, so obs_stage_ring takes the sources outside
+// the shard from them exactly as k_obs does on that rank.
+template <bool HALO>
+__device__ __forceinline__ void obs_gather_body(const KParams& p, const ObsArgs& o, const double* __restrict__ s_air,
+                                                const double* __restrict__ s_mass,
+                                                const uint32_t* __restrict__ s_hvac, int64_t row_stride,
+                                                const double* __restrict__ scalars, int rows,
+                                                const int64_t* __restrict__ idx, int64_t m, float* __restrict__ obs,
+                                                const float* __restrict__ halo_rows, int64_t halo_stride) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int F = o.n_feat;
   const int nmsg = (o.comm_mode == MDR_COMM_RING ? o.n_comm + 1 : 0) * o.msg_w;
@@ -2808,6 +2837,10 @@ __global__ void __launch_bounds__(kGatherRows* kGatherLanes)
   pr.hvac = const_cast<uint32_t*>(s_hvac) + t * row_stride;
   ObsArgs orow = o;
   orow.sc_dev = nullptr;
+  if constexpr (HALO) {
+    orow.halo_msg = halo_rows + t * halo_stride;
+    orow.halo_next = nullptr;
+  }
   double P = 0.0;
   if (ok) {
     const double* sc = scalars + 4 * t;
@@ -2838,6 +2871,21 @@ __global__ void __launch_bounds__(kGatherRows* kGatherLanes)
   } else {
     for (int64_t q = threadIdx.x; q < nflt; q += blockDim.x) dst[q] = tile[q];
   }
+}
+
+__global__ void __launch_bounds__(kGatherRows* kGatherLanes)
+    k_obs_gather(KParams p, ObsArgs o, const double* __restrict__ s_air, const double* __restrict__ s_mass,
+                 const uint32_t* __restrict__ s_hvac, int64_t row_stride, const double* __restrict__ scalars,
+                 int rows, const int64_t* __restrict__ idx, int64_t m, float* __restrict__ obs) {
+  obs_gather_body<false>(p, o, s_air, s_mass, s_hvac, row_stride, scalars, rows, idx, m, obs, nullptr, 0);
+}
+
+__global__ void __launch_bounds__(kGatherRows* kGatherLanes)
+    k_obs_gather_halo(KParams p, ObsArgs o, const double* __restrict__ s_air, const double* __restrict__ s_mass,
+                      const uint32_t* __restrict__ s_hvac, int64_t row_stride, const double* __restrict__ scalars,
+                      int rows, const int64_t* __restrict__ idx, int64_t m, float* __restrict__ obs,
+                      const float* __restrict__ halo_rows, int64_t halo_stride) {
+  obs_gather_body<true>(p, o, s_air, s_mass, s_hvac, row_stride, scalars, rows, idx, m, obs, halo_rows, halo_stride);
 }
 
 // --------------------------------------------------------------------------------------- greedy

@@ -91,6 +91,13 @@ class mdr_snap(C.Structure):
                 ("t_air", C.c_void_p), ("t_mass", C.c_void_p), ("hvac", C.c_void_p), ("scalars", C.c_void_p)]
 
 
+class mdr_snap_halo(C.Structure):
+    """Ring-halo slab beside the snapshot rows of a shard (mdr.h mdr_snap_halo); like ``mdr_snap``,
+    ``struct_bytes`` is its own size check."""
+    _fields_ = [("struct_bytes", C.c_int32), ("cap_rows", C.c_int32), ("row_stride", C.c_int64),
+                ("rows", C.c_void_p)]
+
+
 class mdr_actor_spec(C.Structure):
     _fields_ = [("n_in", C.c_int32), ("h1", C.c_int32), ("h2", C.c_int32), ("n_act", C.c_int32),
                 ("precision", C.c_int32)]
@@ -195,6 +202,11 @@ SIGNATURES = {
     "mdr_actor_rollout_stats": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64,
                                     VP, I64, VP, I, P(mdr_snap), I, VP, I64, I64, VP]),
     "mdr_obs_gather": (I, [VP, P(mdr_obs_spec), P(mdr_snap), I, VP, I64, VP, VP]),
+    "mdr_snapshot_sharded": (I, [VP, P(mdr_obs_spec), P(mdr_snap), P(mdr_snap_halo), I, P(mdr_obs_scalars), VP, VP,
+                                 VP]),
+    "mdr_actor_rollout_sharded_snap": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64, VP, I64, VP,
+                                           P(mdr_snap), P(mdr_snap_halo), I, VP]),
+    "mdr_obs_gather_sharded": (I, [VP, P(mdr_obs_spec), P(mdr_snap), P(mdr_snap_halo), I, VP, I64, VP, VP]),
     "mdr_actor_profile": (I, [VP, P(mdr_obs_spec), P(mdr_obs_scalars), VP, P(D), VP]),
     "mdr_interp_load": (I, [VP, P(mdr_interp_spec)]),
     "mdr_interp_values": (I, [VP, VP, I, D, D, D, VP, VP]),

@@ -207,7 +207,11 @@ class DeviceActor:
         ``store`` (mdr_amd.replay.RolloutStore): the ticks are appended to it as training
         transitions — each tick's pre-step state snapshot is recorded inside the same graph
         (mdr_actor_rollout_snap) and the store's next ``actions`` / ``probs`` / ``rewards`` rows are
-        the outputs (``rewards`` / ``actions`` / ``probs`` must then be None).
+        the outputs (``rewards`` / ``actions`` / ``probs`` must then be None).  On a sharded
+        environment the store also keeps each tick's ring halo: a native comm (RcclComm, HostComm)
+        records both inside the C loop (mdr_actor_rollout_sharded_snap), TorchComm and the common
+        penalty modes per tick (``Environment.snapshot``, sharing the tick's one halo exchange with
+        ``select_actions``).
 
         ``stats`` (mdr_amd.services.RolloutStats; combinable with ``store``): each tick's cluster
         statistics of the post-step state, its rewards and the cluster power are appended to it as one
@@ -233,7 +237,10 @@ class DeviceActor:
                                        for x in (store.rewards, store.actions, store.probs))
         if sh.penalty_mode != 0 or (env.world > 1 and not getattr(env._comm, "native", False)):
             return self._rollout_stepwise(n_ticks, rewards, actions, probs, store, stats)
-        sharded = env.world > 1
+        # (a sharded store at world 1, RCCL to self: the C loop records its halo rows)
+        sharded = env.world > 1 or (store is not None and getattr(store, "sharded", False))
+        if sharded and stats is not None:
+            raise ValueError("stats rows are single-shard: a sharded environment has no stats= rollouts")
         spec, _sc, keep = env.bound_obs_spec() if not sharded else (env.obs_spec(), None, [])
         self._check_obs(spec)
         n = env.n_local
@@ -257,7 +264,11 @@ class DeviceActor:
             osc[1:, 2] = ticks.solar[:-1]
             osc[:, 3] = ticks.t_od_prev
             sl = (lambda x, st: None if x is None else (x[done:done + k] if st else x))
-            if sharded:  # C loop: ring halo + actor + count allreduce + step per tick (RCCL)
+            if sharded and store is not None:  # ... and the tick's state, scalars and halo rows
+                sh.actor_rollout_sharded_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
+                                              sl(rewards, rs), rs, store.snap, store.halo, row0 + done)
+                store.commit_rows(k)
+            elif sharded:  # C loop: ring halo + actor + count allreduce + step per tick (RCCL)
                 sh.actor_rollout_sharded(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
                                          sl(rewards, rs), rs)
             else:

@@ -873,7 +873,12 @@ class Environment:
             keep.append(tab)
             spec.comm_table = L.ptr(tab)
         if spec.comm_mode == L.COMM_RING and self.world > 1 and spec.n_comm > 0:
-            halo = self._comm.ring_halo(sh, spec)
+            # (a sharded snapshot of this tick has exchanged it already: one exchange serves both)
+            kept, self._halo_kept = getattr(self, "_halo_kept", None), None
+            if kept is not None and kept[:2] == (self._tick, self._pop_epoch):
+                halo = kept[2]
+            else:
+                halo = self._comm.ring_halo(sh, spec)
             keep.append(halo)
             spec.halo_msg = L.ptr(halo)
         sc = L.mdr_obs_scalars(float(self._P_host), float(self.power_grid.current_signal),
@@ -896,10 +901,24 @@ class Environment:
     def snapshot(self, store):
         """Append the current pre-step state (t_air, t_mass, hvac) and obs scalars as one row of
         ``store`` (mdr_amd.replay.RolloutStore): what ``obs_tensor()`` would be built from now.  The
-        per-tick API, for loops that do not use the fused rollout.  Returns the row index."""
+        per-tick API, for loops that do not use the fused rollout.  Returns the row index.
+
+        A sharded store also records the tick's ring halo (``ring_halo``, one exchange): the next
+        ``bound_obs_spec`` of this tick — ``select_actions``, ``obs_tensor`` — reads the same tensor
+        instead of exchanging it again."""
         row = store.begin_rows(1)
         sc = L.mdr_obs_scalars(float(self._P_host), float(self.power_grid.current_signal),
                                float(self._solar), float(self.current_od_temp))
+        if getattr(store, "sharded", False):
+            spec = self.obs_spec()
+            halo = None
+            if spec.comm_mode == L.COMM_RING and spec.n_comm > 0:
+                halo = self._comm.ring_halo(self._shard, spec)
+                if self.world > 1:
+                    self._halo_kept = (self._tick, self._pop_epoch, halo)
+            self._shard.snapshot_sharded(spec, store.snap, store.halo, row, sc, halo, use_p_dev=self._P_dev_valid)
+            store.commit_rows(1)
+            return row
         self._shard.snapshot(store.snap, row, sc, use_p_dev=self._P_dev_valid)
         store.commit_rows(1)
         return row

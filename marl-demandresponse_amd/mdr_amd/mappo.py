@@ -22,6 +22,12 @@ What is changed, deliberately:
     update against the reference MAPPO at N = 2).
 Actions are sampled by the fused device actor (mdr_amd.actor.DeviceActor, Philox), not by torch's
 Categorical RNG.
+
+On a house-sharded ``neighbours`` environment ``collect`` / ``update`` train one policy from the
+cluster's buffer: every rank builds the agent with the same seed, stores its own houses' transitions
+and ring halos, and per minibatch contributes the rows it owns to one integer allreduce, after which
+every rank takes the identical optimiser step (``DeviceMAPPO.update``; ``evaluate`` and
+``collect(metrics=...)`` stay single-shard).
 """
 from __future__ import annotations
 
@@ -112,6 +118,62 @@ def discounted_returns(reward, done, gamma: float):
     if reward.numel() == 0:
         return reward.double().clone()
     return _suffix_affine(reward.double(), gamma * (1.0 - done.double()))
+
+
+def shard_owner(idx, n: int, world: int):
+    """(rank, local index) of the global transition indices ``idx`` (tick * n + global house, the
+    reference's buffer order) of a cluster of ``n`` houses sharded over ``world`` ranks as
+    ``environment.shard_range`` cuts it: rank r owns houses [r * n // world, (r + 1) * n // world),
+    so a house's rank is the largest r with r * n // world <= house, and its local index is
+    tick * n_local(rank) + house - offset(rank).  ``idx``: an integer torch tensor or numpy array."""
+    tick, house = idx // n, idx % n
+    rank = ((house + 1) * world - 1) // n
+    off = rank * n // world
+    nl = (rank + 1) * n // world - off
+    return rank, tick * nl + (house - off)
+
+
+def sharded_reference_returns(reward, done, gamma: float, rank: int, world: int, all_gather):
+    """``discounted_returns`` over the cluster's buffer (tick-major, house-minor over global house
+    ids) from one rank's part of it: ``reward`` [T, n_local] (this rank's houses, a contiguous range
+    of every tick), ``done`` [T].  The recurrence G_i = r_i + c_i G_{i+1} (c = gamma * (1 - done) of the
+    element's tick) runs across the houses of a tick, hence across ranks: each rank's part of a tick
+    is one block of the buffer, an affine map of the return entering it, G_first = C + A G_in with
+    A = c_t ** n_local and C the block's return for G_in = 0.  ``all_gather`` takes this rank's
+    [T, 2] float64 (A, C) rows and returns every rank's, [world, T, 2] in rank order — the only
+    exchange; then every rank solves the T x world block recurrence and fixes its elements up:
+    G[t, j] = G0[t, j] + c_t ** (n_local - j) * G_in[t].  Shards may be uneven.  float64 [T, n_local]."""
+    torch = _torch()
+    r = reward.double()
+    T, nl = r.shape
+    c = (gamma * (1.0 - done.double())).reshape(T)
+    # G0: the suffix recurrence inside every (tick, rank) block, the chain cut after its last element
+    cc = c[:, None].expand(T, nl).clone()
+    cc[:, nl - 1] = 0.0
+    g0 = _suffix_affine(r.reshape(-1).contiguous(), cc.reshape(-1)).view(T, nl)
+    # suf[t, j] = c_t ** (n_local - j): the weight of the entering return at element j
+    expo = torch.arange(nl, 0, -1, device=r.device, dtype=torch.float64)
+    suf = torch.pow(c[:, None], expo[None, :])
+    mine = torch.stack([suf[:, 0], g0[:, 0]], 1).contiguous()
+    blocks = all_gather(mine).double().cpu()  # [world, T, 2]
+    g_in = torch.zeros(T, dtype=torch.float64)
+    nxt = 0.0  # the return entering the buffer's last block
+    A, Cc = blocks[:, :, 0].tolist(), blocks[:, :, 1].tolist()
+    for t in range(T - 1, -1, -1):
+        for w in range(world - 1, -1, -1):
+            if w == rank:
+                g_in[t] = nxt
+            nxt = Cc[w][t] + A[w][t] * nxt
+    return g0 + suf * g_in.to(r.device)[:, None]
+
+
+def _checksum53(t):
+    """A 53-bit position-weighted checksum of an integer tensor's values (exact in a double, so a
+    min- and a max-allreduce of it compare the ranks' tensors): device int64 scalar."""
+    torch = _torch()
+    v = t.reshape(-1).to(torch.int64)
+    w = torch.arange(v.numel(), device=v.device, dtype=torch.int64) % 1021 + 1
+    return (v * w).sum() & ((1 << 53) - 1)
 
 
 class DeviceMAPPO:
@@ -282,12 +344,59 @@ class DeviceMAPPO:
             g[t] = nxt
         return g.reshape(-1)
 
+    # ---------------------------------------------------------------- sharded update
+    def _allgather_rows(self, mine):
+        """Every rank's equal-shape device tensor, [world, ...] in rank order (one byte all-gather)."""
+        torch = _torch()
+        env = self.env
+        raw = env._comm.allgather_bytes(env.shard, mine.contiguous().view(torch.uint8).reshape(-1))
+        return raw.view(mine.dtype).view(env.world, *mine.shape)
+
+    def _same_on_all_ranks(self, value, what: str) -> None:
+        """RuntimeError on every rank unless every rank holds the same 53-bit ``value`` (a device
+        int64 scalar): a min- and a max-allreduce of it as a double.  Synchronises."""
+        torch = _torch()
+        env = self.env
+        lo = value.double().reshape(1).clone()
+        hi = lo.clone()
+        env._comm.allreduce_min(env.shard, lo)
+        env._comm.allreduce_max(env.shard, hi)
+        if float(lo.item()) != float(hi.item()):
+            raise RuntimeError(f"DeviceMAPPO.update: the ranks' {what} differ (checksums {int(lo.item())} .. "
+                               f"{int(hi.item())}): the replicas would drift apart")
+
+    def _minibatch_sharded(self, st, idx, cols):
+        """The minibatch of global transition indices ``idx`` on every rank, bit for bit: float32
+        [B, F + 4] = the obs row, action, stored probability, return and the critic's others column.
+        Each rank fills the rows of the transitions it owns (``shard_owner``; the obs rows rebuilt
+        from its snapshot and halo rows) into a zeroed buffer at their positions, and one
+        sum-allreduce of the buffer as 32-bit integer bit patterns (x + 0 is exact, as in
+        k_halo_step_pack's rows) gives every rank every row."""
+        torch = _torch()
+        env = self.env
+        rank, loc = shard_owner(idx, env.n, env.world)
+        own = rank == env.rank
+        loc = torch.where(own, loc, torch.full_like(loc, -1))
+        rows = torch.cat([st.states(loc), cols[loc.clamp(min=0)]], 1)  # (not owned: a NaN row, masked below)
+        buf = torch.where(own[:, None], rows, torch.zeros_like(rows)).contiguous()
+        env._comm.allreduce_count32(env.shard, buf.view(torch.int32))
+        return buf
+
     def update(self, t=None) -> bool:
         """mappo.py:128-217: returns, then ppo_update_time epochs of minibatch PPO steps.  Returns
-        False (and keeps the buffer) while it holds fewer than batch_size transitions."""
+        False (and keeps the buffer) while it holds fewer than batch_size transitions.
+
+        After ``collect`` on a sharded environment the buffer is the cluster's T x N transitions in
+        the reference's order (tick-major, house-minor over global house ids): every rank draws the
+        same permutation of it (the ranks share the constructor's seed; a checksum guard per epoch),
+        holds every minibatch after one integer allreduce (``_minibatch_sharded``) and runs the
+        identical forward, backward, clip and Adam step — no gradient is exchanged — so the ranks
+        keep one set of weights (a checksum guard at the end)."""
         torch = _torch()
         F = torch.nn.functional
         L = len(self)
+        if self.store is not None and self.store.rows and self.store.sharded:
+            L = self.store.rows * self.env.n  # the cluster's buffer
         if L < self.cfg.batch_size:
             return False
         cfg = self.cfg
@@ -309,29 +418,48 @@ class DeviceMAPPO:
             dev = state.device
         n_glob = self.env.n
         tot = acts.sum(1, keepdim=True)
-        if self.env.world > 1:
+        sharded = st is not None and st.sharded  # one policy from the cluster's buffer (see _minibatch_sharded)
+        if self.env.world > 1 or sharded:
             self.env._comm.allreduce_sum(self.env.shard, tot)
         others = ((tot - acts) / max(n_glob - 1, 1)).float().reshape(-1, 1)  # mean of the other houses' actions
         reward = st.rewards[:T] if st is not None else torch.stack([b[3] for b in self.buffer])  # [T, N]
         done = torch.tensor(st.done if st is not None else [b[4] for b in self.buffer], dtype=torch.float64,
                             device=reward.device)
         done_rows = done[:, None].expand(-1, n)
-        Gt = self._returns(reward, done_rows, n).float()
+        if sharded and self.returns == "reference":
+            Gt = sharded_reference_returns(reward, done, cfg.gamma, self.env.rank, self.env.world,
+                                           self._allgather_rows).reshape(-1).float()
+        else:
+            Gt = self._returns(reward, done_rows, n).float()
         critic_in = torch.cat([state, others], 1) if st is None else None
+        if sharded:  # the local columns a minibatch row carries beside its obs row
+            cols = torch.cat([act.float(), old_prob, Gt.view(-1, 1), others], 1).contiguous()
         on_device = self.sampler == "device" or (self.sampler == "auto" and L > (1 << 20))
         self.last_sampler = "device" if on_device else "reference"
         for _ in range(cfg.ppo_update_time):
             # SubsetRandomSampler + BatchSampler(drop_last=False): a permutation (the global CPU
             # generator's, or the device generator's — see sampler), cut in order into batch_size chunks
             perm = torch.randperm(L, device=dev) if on_device else torch.randperm(L).to(dev)
+            if sharded:
+                self._same_on_all_ranks(_checksum53(perm), "minibatch permutations")
             for k in range(0, L, cfg.batch_size):
                 idx = perm[k:k + cfg.batch_size]
-                Gt_index = Gt[idx].view(-1, 1)
-                state_idx = state[idx] if st is None else st.states(idx)
-                V = self.critic_net(critic_in[idx] if st is None else torch.cat([state_idx, others[idx]], 1))
+                if sharded:
+                    mb = self._minibatch_sharded(st, idx, cols)
+                    nf = self.num_state
+                    state_idx = mb[:, :nf].contiguous()
+                    act_idx, old_idx = mb[:, nf].long().view(-1, 1), mb[:, nf + 1].reshape(-1, 1).contiguous()
+                    Gt_index = mb[:, nf + 2].reshape(-1, 1).contiguous()
+                    critic_idx = torch.cat([state_idx, mb[:, nf + 3:nf + 4]], 1)
+                else:
+                    Gt_index = Gt[idx].view(-1, 1)
+                    state_idx = state[idx] if st is None else st.states(idx)
+                    critic_idx = critic_in[idx] if st is None else torch.cat([state_idx, others[idx]], 1)
+                    act_idx, old_idx = act[idx], old_prob[idx]
+                V = self.critic_net(critic_idx)
                 advantage = (Gt_index - V).detach()
-                action_prob = self.actor_net(state_idx).gather(1, act[idx])
-                ratio = action_prob / old_prob[idx]
+                action_prob = self.actor_net(state_idx).gather(1, act_idx)
+                ratio = action_prob / old_idx
                 clipped_ratio = torch.clamp(ratio, 1 - cfg.clip_param, 1 + cfg.clip_param)
                 action_loss = -torch.min(ratio * advantage, clipped_ratio * advantage).mean()
                 self.actor_optimizer.zero_grad()
@@ -347,6 +475,10 @@ class DeviceMAPPO:
         del self.buffer[:]
         if st is not None:
             st.clear()
+        if sharded:
+            bits = torch.cat([p.detach().reshape(-1).view(torch.int32) for net in (self.actor_net, self.critic_net)
+                              for p in net.parameters()])
+            self._same_on_all_ranks(_checksum53(bits), "actor and critic weights after the update")
         self.device_actor.load_weights()  # the fused kernel's packed weights follow the update
         return True
 

@@ -13,8 +13,17 @@ assembles them with the device functions ``k_obs`` and ``k_actor`` use, so they 
 ``obs_tensor()`` of their tick.  With the action, its probability and the reward a stored
 transition is 33 B.
 
-Limits: one shard (a neighbour's snapshot would live on another shard) and fixed links (the
-``random_sample`` comm mode re-draws them every tick).  ``Environment.reset()`` re-draws targets,
+A house-sharded environment: with the ``neighbours`` ring a shard's rows read at most ``lo = K // 2``
+houses before the shard and ``hi = (K + 1) // 2`` after it, and only their message features — the ring
+halo the sharded actor reads every tick.  ``RolloutStore`` keeps that row beside the snapshot
+(``k_snap_halo``: ``halo_bytes_per_tick`` <= 440 B), so ``states(idx)`` of local indices rebuilds every
+local row on its own rank (``k_obs_gather_halo``), bit-identical to the single-process rows.
+
+Limits: fixed links (the ``random_sample`` comm mode re-draws them every tick); on a sharded
+environment the ``neighbours`` ring only (a table mode's neighbours live anywhere in the cluster)
+and shards no smaller than the ring half-width; ``ReplayStore`` (DQN) is single-shard (its next
+state is the ring-next slot's row, whose halo a trailing snapshot does not have).
+``Environment.reset()`` re-draws targets,
 parameters and links, so rows stored before it can no longer be rebuilt: a non-empty store then
 refuses appends and gathers until ``clear()``.
 """
@@ -39,6 +48,9 @@ class RolloutStore:
         if capacity_ticks < 1:
             raise ValueError("capacity_ticks must be at least 1")
         self.env = env
+        # a shard of a larger cluster, or a context with the library's own communicator (world 1
+        # included): the sharded entry points and a ring-halo row per tick
+        self.sharded = env.world > 1 or bool(getattr(env._comm, "native", False))
         self._check_supported()
         sh = env.shard
         dev = sh.device
@@ -53,6 +65,14 @@ class RolloutStore:
         self.rewards = torch.empty((cap, n), dtype=torch.float64, device=dev)
         self.snap = L.mdr_snap(C.sizeof(L.mdr_snap), cap, n, L.ptr(self.t_air), L.ptr(self.t_mass),
                                L.ptr(self.hvac), L.ptr(self.scalars))
+        self.halo_rows, self.halo, self.halo_bytes_per_tick = None, None, 0
+        if self.sharded:
+            spec = env.obs_spec()
+            w = spec.n_comm * sh.lib.mdr_msg_width(C.byref(spec))  # (lo + hi) rows of msg_w floats
+            if w:
+                self.halo_rows = torch.zeros((cap, w), dtype=torch.float32, device=dev)
+                self.halo = L.mdr_snap_halo(C.sizeof(L.mdr_snap_halo), cap, w, L.ptr(self.halo_rows))
+                self.halo_bytes_per_tick = 4 * w
         self.rows = 0
         self.done = []  # host: per stored tick
         self._epoch = None
@@ -62,12 +82,17 @@ class RolloutStore:
     # ---------------------------------------------------------------- validity
     def _check_supported(self):
         env = self.env
-        if env.world > 1:
-            raise ValueError("RolloutStore: sharded environments are not supported (a neighbour's "
-                             "snapshot lives on another shard)")
         if env._links is None:
             raise ValueError("RolloutStore: the random_sample comm mode re-draws its links every tick; "
                              "a state snapshot cannot reproduce its observations")
+        if self.sharded:
+            mode = env.init_props.cluster_prop.agents_comm_prop.mode
+            spec = env.obs_spec()
+            if spec.comm_mode != L.COMM_RING and spec.n_comm > 0:
+                raise ValueError(f"RolloutStore: on a sharded environment only the 'neighbours' ring is supported, "
+                                 f"not the {mode!r} comm mode (its neighbours live anywhere in the cluster)")
+            if env.n_local < (spec.n_comm + 1) // 2:
+                raise ValueError("RolloutStore: a shard smaller than the ring half-width")
 
     def _bind(self):
         """Remember the env's population epoch and links table (an empty store follows a reset)."""
@@ -126,7 +151,10 @@ class RolloutStore:
         idx = torch.as_tensor(idx, device=sh.device).to(torch.int64).reshape(-1).contiguous()
         out = torch.empty((idx.numel(), self._spec.n_feat), dtype=torch.float32, device=sh.device)
         if idx.numel():
-            sh.obs_gather(self._spec, self.snap, self.rows, idx, out)
+            if self.sharded:  # local indices; the ring sources outside the shard from the halo rows
+                sh.obs_gather_sharded(self._spec, self.snap, self.halo, self.rows, idx, out)
+            else:
+                sh.obs_gather(self._spec, self.snap, self.rows, idx, out)
         return out
 
 
@@ -193,7 +221,7 @@ class ReplayStore:
 
         self.ring = TickRing(capacity_ticks)
         self.env = env
-        RolloutStore._check_supported(self)
+        self._check_supported()
         dev = env.shard.device
         S, n = self.ring.slots, env.n_local
         self.capacity, self.n_local = self.ring.capacity, n
@@ -217,7 +245,17 @@ class ReplayStore:
     def rows(self) -> int:
         return self.ring.count
 
-    _check_supported = RolloutStore._check_supported
+    sharded = False  # (RolloutStore's attribute: this store never takes the sharded entry points)
+
+    def _check_supported(self):
+        env = self.env
+        if env.world > 1:
+            raise ValueError("ReplayStore: sharded environments are not supported (a transition's next state "
+                             "is the ring-next slot's row, and a neighbour's snapshot lives on another shard)")
+        if env._links is None:
+            raise ValueError("ReplayStore: the random_sample comm mode re-draws its links every tick; "
+                             "a state snapshot cannot reproduce its observations")
+
     _bind = RolloutStore._bind
     _check_epoch = RolloutStore._check_epoch
 

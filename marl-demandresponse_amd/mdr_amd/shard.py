@@ -474,6 +474,36 @@ class HipShard:
         L.check(self.lib.mdr_obs_gather(self.ctx, C.byref(spec), C.byref(snap), int(rows), L.ptr(idx),
                                         int(idx.numel()), L.ptr(out), self.stream()), "mdr_obs_gather")
 
+    # ------------------------------------------------------------------ replay snapshots of a shard
+    def snapshot_sharded(self, spec, snap, halo, row: int, scalars, halo_src, use_p_dev=True):
+        """mdr_snapshot_sharded: ``snapshot`` on a shard, and ``halo_src`` (device float32
+        [lo + hi, msg_w], the tick's ring halo, or None when the obs reads none) into row ``row`` of
+        ``halo`` (an ``mdr_snap_halo``)."""
+        L.check(self.lib.mdr_snapshot_sharded(self.ctx, C.byref(spec), C.byref(snap),
+                                              C.byref(halo) if halo is not None else None, int(row),
+                                              C.byref(scalars), L.ptr(self.p_dev) if use_p_dev else 0,
+                                              L.ptr(halo_src), self.stream()), "mdr_snapshot_sharded")
+
+    def actor_rollout_sharded_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
+                                   rew_stride, snap, halo, row0: int):
+        """``actor_rollout_sharded`` that also records tick t's pre-step state, obs scalars and ring
+        halo into row ``row0 + t`` of ``snap`` / ``halo`` (mdr_actor_rollout_sharded_snap; ``snap`` None:
+        ``actor_rollout_sharded``)."""
+        n = len(ticks)
+        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
+        assert obs_sc.shape == (n, 4)
+        L.check(self.lib.mdr_actor_rollout_sharded_snap(
+            self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec), L.ptr(action), act_stride, L.ptr(prob),
+            prob_stride, L.ptr(reward), rew_stride, L.ptr(self.p_dev), C.byref(snap) if snap is not None else None,
+            C.byref(halo) if halo is not None else None, int(row0), self.stream()), "mdr_actor_rollout_sharded_snap")
+
+    def obs_gather_sharded(self, spec, snap, halo, rows: int, idx, out):
+        """``obs_gather`` on a shard: ``idx`` local (tick * n_local + local house), the ring sources
+        outside the shard from the halo rows (mdr_obs_gather_sharded)."""
+        L.check(self.lib.mdr_obs_gather_sharded(self.ctx, C.byref(spec), C.byref(snap),
+                                                C.byref(halo) if halo is not None else None, int(rows), L.ptr(idx),
+                                                int(idx.numel()), L.ptr(out), self.stream()), "mdr_obs_gather_sharded")
+
     def interp_load(self, grids, values, cfg):
         """Monte-Carlo table + axes to the device (mdr_interp_load, synchronous)."""
         grid = np.ascontiguousarray(np.concatenate([np.asarray(g, np.float64) for g in grids]))
