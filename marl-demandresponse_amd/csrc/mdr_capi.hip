@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "mdr_actor.h"
+#include "mdr_devbuf.h"
 #include "mdr_interp.h"
 #include "mdr_obs_dev.h"
 #include "mdr_kernels.h"
@@ -50,6 +51,30 @@ int fail(int code, const std::string& msg) {
     hipError_t e_ = hipGetLastError();                                                     \
     if (e_ != hipSuccess) return fail(MDR_EHIP, std::string(what) + ": " + hipGetErrorString(e_)); \
   } while (0)
+
+// Device memory has one owner type (mdr_devbuf.h) and this one allocator: every buffer of a context
+// is a Dev<T> member and goes with the context's destructor.  A site that grows a
+// buffer queued work may still use: synchronise, drop the cached graphs that hold its address, then
+// reserve, which frees before it allocates and is empty in between.  What a captured launch sequence
+// uses is reserved, and zero-filled by hipMemset (never a memset node: zero_slabs), before the capture.
+struct HipAlloc {
+  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void release(void* p) { (void)hipFree(p); }
+};
+template <class T>
+using Dev = DevBuf<T, HipAlloc>;
+
+// room for n elements, zero-filled if asked and newly allocated; a failure is MDR_EHIP with the buffer's
+// name (mdr_create and mdr_interp_load report MDR_ENOMEM in words of their own: they call reserve)
+template <class T>
+int dev_reserve(Dev<T>& b, size_t n, const char* name, bool zero = false) {
+  if (n <= b.capacity()) return MDR_OK;
+  hipError_t e = (hipError_t)b.reserve(n);
+  if (e == hipSuccess && zero && (e = hipMemset(b, 0, n * sizeof(T))) != hipSuccess) b.reset();
+  return e == hipSuccess ? MDR_OK : fail(MDR_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+}
+template <class T>
+size_t dev_bytes(const Dev<T>& b) { return b.capacity() * sizeof(T); }
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -97,20 +122,18 @@ struct mdr_ctx {
   mdr_config cfg{};
   KParams kp{};
   bool bound = false;
-  double* d_tables = nullptr;           // q_on[MDR_MAX_CAP] | p_on[MDR_MAX_CAP]
-  unsigned long long* d_slab = nullptr;  // kSlabs x kCountShards x n_cap count slabs (ring of 3 on
+  Dev<double> d_tables;                 // q_on[MDR_MAX_CAP] | p_on[MDR_MAX_CAP]
+  Dev<unsigned long long> d_slab;        // kSlabs x kCountShards x n_cap count slabs (ring of 3 on
                                          // the step path, 4 in the overlapped sharded pipeline)
   int slab_len = 0;
   int ring = 0;                          // slab of the current tick
   bool counts_ready = false;             // current slab filled (phase 1 or previous lookahead)
-  double* d_pen_partial = nullptr;       // 2 per block of k_step_t
-  double* d_partial2 = nullptr;
-  double* d_wpen = nullptr;              // common-penalty windows: {sum pen/N, max pen} [kWindowMax][tiles_padded][2]
-  size_t wpen_bytes = 0;
-  double* d_wres = nullptr;              // their per-tick {sum, max} [kWindowMax][2], then signal terms [kWindowMax]
-  double* d_wstat = nullptr;             // closed-loop windows with stats rows: block partials [kWindowMax][grid][kStats]
-  size_t wstat_bytes = 0;                //   (allocated by the first mdr_rollout_stats, outside any capture)
-  double* d_stat_p = nullptr;            // mdr_rollout_stats per tick without a caller's p_out: the tick's P
+  Dev<double> d_pen_partial;             // 2 per block of k_step_t
+  Dev<double> d_partial2;
+  Dev<double> d_wpen;                    // common-penalty windows: {sum pen/N, max pen} [kWindowMax][tiles_padded][2]
+  Dev<double> d_wres;                    // their per-tick {sum, max} [kWindowMax][2], then signal terms [kWindowMax]
+  Dev<double> d_wstat;                   // closed-loop windows with stats rows: block partials [kWindowMax][grid][kStats]
+  Dev<double> d_stat_p;                  // mdr_rollout_stats per tick without a caller's p_out: the tick's P
   int pen_blocks = 0;
   // ---- options (mdr_set_option; defaults are the measured-fastest exact configuration)
   int tpw = 0;                           // MDR_OPT_STEP_TPW: k_step_pipe tiles per wave (0: k_step_t)
@@ -124,43 +147,39 @@ struct mdr_ctx {
   bool actor_fp32_bf16 = false;          // MDR_OPT_ACTOR_FP32_FORM: the three-way bf16 fp32 form (kernel PREC 6)
   bool halo_overlap = true;              // MDR_OPT_HALO_OVERLAP: sharded actor tick, halo beside the interior tiles
   bool halo_in_counts = true;            // MDR_OPT_HALO_IN_COUNTS: the next tick's ring halo rides in the count allreduce
-  unsigned long long* d_c5 = nullptr;    // that path's ring of 3 x [count slab | world x halo rows]
-  size_t c5_bytes = 0;
+  Dev<unsigned long long> d_c5;          // that path's ring of 3 x [count slab | world x halo rows]
   int thermal = MDR_THERMAL_AFFINE;      // MDR_OPT_WINDOW_THERMAL: k_step_window's per-tick update
   int win = kWindowMax;                  // ticks per k_step_window launch (0: one-tick path)
-  unsigned long long* d_wslab = nullptr; // 3 window count slots (mdr_kernels.hip K1W: slab | red | rec)
+  Dev<unsigned long long> d_wslab;       // 3 window count slots (mdr_kernels.hip K1W: slab | red | rec)
   int wslab_len = 0;
   bool wslab_dirty = true;               // the slots' shard part must be zero when a rollout starts
-  uint64_t* d_onb = nullptr;             // per-tick ON lane masks of the next window [tiles][HPT][kWindowMax]
-  uint32_t* d_wah = nullptr;             // FSM word at the end of the next window, per house
-  uint64_t* d_onb2 = nullptr;            // second set for the count-ahead pipeline (window_pipeline)
-  uint32_t* d_wah2 = nullptr;
-  size_t onb_bytes = 0, wah_bytes = 0;
+  Dev<uint64_t> d_onb;                   // per-tick ON lane masks of the next window [tiles][HPT][kWindowMax]
+  Dev<uint32_t> d_wah;                   // FSM word at the end of the next window, per house
+  Dev<uint64_t> d_onb2;                  // second set for the count-ahead pipeline (pipe_buffers: a unit)
+  Dev<uint32_t> d_wah2;
   bool coef_dirty = true;
-  int* d_flags = nullptr;                // [0] params_bad
-  unsigned* d_tickets = nullptr;         // k_count_window's grid_last_block counters (zero between uses)
-  // rollout tick drivers
-  TickArgs* d_ticks = nullptr;
-  int ticks_cap = 0;
+  Dev<int> d_flags;                      // [0] params_bad
+  Dev<unsigned> d_tickets;               // k_count_window's grid_last_block counters (zero between uses)
+  // rollout tick drivers (a unit with d_obs_sc: ensure_ticks)
+  Dev<TickArgs> d_ticks;
   std::map<GraphKey, std::pair<hipGraphExec_t, int>> graphs;  // exec, ring phase at end
-  // greedy scratch
+  // greedy scratch: one unit (greedy_scratch / greedy_clear), sized for g_cap houses
   int64_t g_cap = 0;
-  double *g_key = nullptr, *g_key2 = nullptr, *g_ps = nullptr, *g_incl = nullptr;
-  int *g_idx = nullptr, *g_idx2 = nullptr;
-  uint8_t* g_ls = nullptr;
-  void* g_tmp = nullptr;
-  size_t g_tmp_bytes = 0;
-  int64_t* g_kpos = nullptr;
-  int64_t* g_extra = nullptr;
+  Dev<double> g_key, g_key2, g_ps, g_incl;
+  Dev<int> g_idx, g_idx2;
+  Dev<uint8_t> g_ls;
+  Dev<unsigned char> g_tmp;              // hipCUB's temporary storage (capacity in bytes)
+  Dev<int64_t> g_kpos, g_extra;
   // histogram-select greedy (k_gq_*): partial min/max, bin histogram, selection, staged window
-  double* g_part = nullptr;
-  unsigned* g_hist = nullptr;
-  GqSel* g_sel = nullptr;
-  uint4* g_win = nullptr;                // the candidate window, unordered (k_gq_compact)
-  uint32_t* g_map = nullptr;             // the key -> bin map's cells (gq_bin; k_gq_bins writes the next)
-  unsigned* g_tickets = nullptr;         // k_gq_select's grid_last_block counters
-  double* g_range = nullptr;             // sharded select: this shard's (min, -max) key range (k_gq_range)
-  uint4* g_sorted = nullptr;             // the window in (key, house) order (k_gq_select)
+  Dev<double> g_part;
+  Dev<unsigned> g_hist;
+  Dev<unsigned char> g_sel_rec;          // the GqSel record's kGqSelBytes (the type is the kernels' own)
+  GqSel* g_sel = nullptr;                //   and the kernels' view of it
+  Dev<uint4> g_win;                      // the candidate window, unordered (k_gq_compact)
+  Dev<uint32_t> g_map;                   // the key -> bin map's cells (gq_bin; k_gq_bins writes the next)
+  Dev<unsigned> g_tickets;               // k_gq_select's grid_last_block counters
+  Dev<double> g_range;                   // sharded select: this shard's (min, -max) key range (k_gq_range)
+  Dev<uint4> g_sorted;                   // the window in (key, house) order (k_gq_select)
   int gq_parts_cap = 0;                  // g_part capacity in (min, max) pairs
   bool gq_keys_ready = false;            // keys + superbin histogram of the current state are in place
   bool gq_hist_dirty = false;            // a producer added counts to g_hist that no select has consumed
@@ -173,8 +192,14 @@ struct mdr_ctx {
   double gq_s1 = NAN, gq_s2 = NAN;       // the last two budgets mdr_greedy_rollout decided for
   bool gq_map_stale = true;              // the state was written since the key maps were last built (k_gq_remap)
   bool gq_fused = false;                 // MDR_OPT_GQ_FUSED (r06: slower than the band form)
-  GqfBufs fz{};
-  int64_t fz_cap_n = 0;                  // the cluster size fz is allocated for
+  GqfBufs fz{};                          // views of the blocks below, as the kernels take them
+  Dev<unsigned> fz_regions;              // par[0] | par[1] | miss
+  Dev<uint4> fz_bkt, fz_mbkt;            // bkt[0] | bkt[1]; mbkt
+  Dev<uint32_t> fz_maps;                 // map[0] | map[1]
+  Dev<unsigned char> fz_sel;             // sel (kGqSelBytes)
+  Dev<uint8_t> fz_dec;
+  Dev<unsigned long long> fz_stamps;     // stamps: not of the unit (it survives a regrow)
+  int64_t fz_cap_n = 0;                  // the cluster size the unit is allocated for (gqf_scratch / gqf_clear)
   int fz_par = 0;                        // the parity the last producer wrote
   bool fz_ready = false;                 // ... for the current state (the last step's GQ = 2 epilogue)
   int gq_nparts = 0;                     //   (from the last step's epilogue: its grid's partials)
@@ -200,34 +225,29 @@ struct mdr_ctx {
     bool sharded = false;                // counts allreduced over the ranks (for mdr_rollout_sharded)
   } begun;
   // MA-PPO actor (row P): packed weight image, per-tick obs scalars of actor rollouts
-  unsigned char* d_actor = nullptr;
-  size_t actor_cap = 0;
-  float* d_actor_raw = nullptr;  // the loaded fp32 weights (w1 b1 w2 b2 w3 b3), packed per obs layout
-  size_t actor_raw_cap = 0;
+  Dev<unsigned char> d_actor;
+  Dev<float> d_actor_raw;        // the loaded fp32 weights (w1 b1 w2 b2 w3 b3), packed per obs layout
   std::vector<int> actor_key;    // the slot layout + precision d_actor is packed for (empty: stale)
   mdr_actor_spec actor{};                // (the two-hidden-layer view the fused kernel packs from)
   mdr_actor_net net{};                   // the loaded actor: layers, widths, precision
   bool actor_ready = false;
   int actor_head = MDR_HEAD_SOFTMAX;     // mdr_actor_set_head: the output layer's head (in the actor graph keys)
-  float* d_eps = nullptr;                // ... and the Q head's epsilon, read by every launch (never in a key)
-  float* d_chain = nullptr;              // the chain's rows: obs [n][F] | hidden ping-pong 2 x [n][wmax4]
-  size_t chain_cap = 0;
+  Dev<float> d_eps;                      // ... and the Q head's epsilon, read by every launch (never in a key)
+  Dev<float> d_chain;                    // the chain's rows: obs [n][F] | hidden ping-pong 2 x [n][wmax4]
   int n_cu = 0;
-  double* d_obs_sc = nullptr;  // [ticks_cap][4]
-  uint8_t* d_act = nullptr;    // [n_local] actor actions when the caller keeps none
-  float* d_halo = nullptr;     // sharded actor rollout: packed edge rows | received ring halo
-  double* d_stats = nullptr;   // k_cluster_stats block partials
-  double* d_tick_part = nullptr;  // k_tick_stats block partials (allocated zeroed, outside any capture)
-  double* d_rows_part = nullptr;  // mdr_greedy_rollout_stats: [kTickRowsBatch][kTickBlocks][kStats] block partials
-  double* d_rows_p = nullptr;     //   and the batch's [kTickRowsBatch] cluster powers (both allocated zeroed on first use)
-  size_t halo_bytes = 0;
+  Dev<double> d_obs_sc;        // [d_ticks.capacity()][4]
+  Dev<uint8_t> d_act;          // [n_local] actor actions when the caller keeps none
+  Dev<float> d_halo;           // sharded actor rollout: packed edge rows | received ring halo
+  Dev<double> d_stats;         // k_cluster_stats block partials
+  Dev<double> d_tick_part;     // k_tick_stats block partials
+  Dev<double> d_rows_part;     // mdr_greedy_rollout_stats: [kTickRowsBatch][kTickBlocks][kStats] block partials
+  Dev<double> d_rows_p;        //   and the batch's [kTickRowsBatch] cluster powers
   std::map<std::vector<int64_t>, hipGraphExec_t> actor_graphs;
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
   int64_t graphs_guarded = 0;            // captured graphs the memset guard walked (graph_memset_guard)
   int64_t graph_nodes_checked = 0;       //   and their nodes
   // interpolated base power (row a10): grid | table | capacities
-  double* d_interp = nullptr;
-  size_t interp_bytes = 0;
+  Dev<double> d_interp;
   InterpArgs interp{};
   bool interp_ready = false;
 };
@@ -335,7 +355,7 @@ int greedy_scratch(mdr_ctx* c, int64_t n);
 int launch_gq_keys(mdr_ctx* c, hipStream_t st, unsigned long long* slab, bool local_map = true);
 int gq_hist_produce(mdr_ctx* c, hipStream_t st);
 // the histogram select's per-house codes (gq_code, 4 B) live in the sort form's key buffer
-uint32_t* gq_codes(mdr_ctx* c) { return reinterpret_cast<uint32_t*>(c->g_key); }
+uint32_t* gq_codes(mdr_ctx* c) { return reinterpret_cast<uint32_t*>(c->g_key.get()); }
 
 // k_step launch with explicit count slabs; reward_lag: the launch writes the previous tick's
 // reward from `cur` (nullptr: none), see k_step_t
@@ -581,17 +601,17 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     tab[MDR_MAX_CAP + i] = cfg->cap_table[i] / cfg->cop;
   }
   auto cleanup = [&](int rc) { mdr_destroy(c); return rc; };
-  if (hipMalloc(&c->d_tables, sizeof(tab)) != hipSuccess) return cleanup(fail(MDR_ENOMEM, "tables"));
+  if (c->d_tables.reserve(2 * MDR_MAX_CAP)) return cleanup(fail(MDR_ENOMEM, "tables"));
   if (hipMemcpy(c->d_tables, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess)
     return cleanup(fail(MDR_EHIP, "tables copy"));
   k.q_on = c->d_tables;
   k.p_on = c->d_tables + MDR_MAX_CAP;
-  if (hipMalloc(&c->d_flags, 16) != hipSuccess || hipMemset(c->d_flags, 0, 16) != hipSuccess)
+  if (c->d_flags.reserve(4) || hipMemset(c->d_flags, 0, 16) != hipSuccess)
     return cleanup(fail(MDR_ENOMEM, "flags"));  // [0] params_bad, [1..2] the actor's fp16-range counts
-  if (hipMalloc(&c->d_tickets, kTicketWords * sizeof(unsigned)) != hipSuccess ||
+  if (c->d_tickets.reserve(kTicketWords) ||
       hipMemset(c->d_tickets, 0, kTicketWords * sizeof(unsigned)) != hipSuccess)
     return cleanup(fail(MDR_ENOMEM, "tickets"));
-  if (hipMalloc(&c->d_eps, sizeof(float)) != hipSuccess || hipMemset(c->d_eps, 0, sizeof(float)) != hipSuccess)
+  if (c->d_eps.reserve(1) || hipMemset(c->d_eps, 0, sizeof(float)) != hipSuccess)
     return cleanup(fail(MDR_ENOMEM, "epsilon"));
   k.params_bad = c->d_flags;
   {
@@ -601,7 +621,7 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     k.fast_tick_ok = ok ? 1 : 0;
   }
   c->slab_len = kCountShards * cfg->n_cap;
-  if (hipMalloc(&c->d_slab, kSlabs * c->slab_len * sizeof(unsigned long long)) != hipSuccess)
+  if (c->d_slab.reserve((size_t)kSlabs * c->slab_len))
     return cleanup(fail(MDR_ENOMEM, "count slabs"));
   if (hipMemset(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long)) != hipSuccess)
     return cleanup(fail(MDR_EHIP, "count slabs memset"));
@@ -613,24 +633,19 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     // the tiles up to whole blocks (up to kCountWaves tiles per block), and the waves of a ragged
     // last block store and load the mask rows of their (empty) tiles too
     const size_t tiles64 = whole_blocks(win_tiles(cfg->n_local) + 1, kCountWaves) * kWinHpt + 1;
-    c->onb_bytes = tiles64 * kWindowMax * sizeof(uint64_t);
-    c->wah_bytes = ((size_t)cfg->n_local + 1) * sizeof(uint32_t);
-    if (hipMalloc(&c->d_wslab, 3 * sizeof(unsigned long long) * c->wslab_len) != hipSuccess ||
-        hipMalloc(&c->d_onb, c->onb_bytes) != hipSuccess || hipMalloc(&c->d_wah, c->wah_bytes) != hipSuccess)
+    if (c->d_wslab.reserve((size_t)3 * c->wslab_len) || c->d_onb.reserve(tiles64 * kWindowMax) ||
+        c->d_wah.reserve((size_t)cfg->n_local + 1))
       return cleanup(fail(MDR_ENOMEM, "window count slabs"));
   } else {
     c->win = 0;
   }
   c->pen_blocks = (int)blocks(cfg->n_local, 512);  // = k_step_t grid
-  if (hipMalloc(&c->d_pen_partial, 2 * sizeof(double) * c->pen_blocks) != hipSuccess ||
-      hipMalloc(&c->d_partial2, 2 * sizeof(double)) != hipSuccess)
+  if (c->d_pen_partial.reserve((size_t)2 * c->pen_blocks) || c->d_partial2.reserve(2))
     return cleanup(fail(MDR_ENOMEM, "penalty partials"));
   if (cfg->penalty_mode != MDR_PEN_INDIVIDUAL_L2 && c->d_wslab) {
     // windowed rollouts under a common penalty: the per-tick, per-wave partials (every wave of the
     // grid writes its rows each launch: never cleared) and the per-tick {sum, max} + signal term
-    c->wpen_bytes = mdr_window_pen_bytes(cfg->n_local);
-    if (hipMalloc(&c->d_wpen, c->wpen_bytes) != hipSuccess ||
-        hipMalloc(&c->d_wres, 3 * kWindowMax * sizeof(double)) != hipSuccess)
+    if (c->d_wpen.reserve(mdr_window_pen_bytes(cfg->n_local) / sizeof(double)) || c->d_wres.reserve(3 * kWindowMax))
       return cleanup(fail(MDR_ENOMEM, "window penalty partials"));
   }
   for (auto& e : c->ev)
@@ -648,45 +663,29 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
   return MDR_OK;
 }
 
-static void destroy_graphs(mdr_ctx* c) {
+// Cached graphs hold the addresses of the buffers their launches were captured with: a site that
+// frees such a buffer (d_ticks / d_obs_sc; d_actor, d_actor_raw, d_chain) drops them BEFORE it frees
+static void drop_rollout_graphs(mdr_ctx* c) {
   for (auto& g : c->graphs) hipGraphExecDestroy(g.second.first);
   c->graphs.clear();
+}
+
+static void drop_actor_graphs(mdr_ctx* c) {
   for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second);
   c->actor_graphs.clear();
 }
 
+static void destroy_graphs(mdr_ctx* c) {
+  drop_rollout_graphs(c);
+  drop_actor_graphs(c);
+}
+
+// (the device buffers go with the context's destructor; mdr_create's cleanup comes here half-built)
 int mdr_destroy(mdr_ctx* c) {
   if (!c) return MDR_OK;
   hipSetDevice(c->cfg.device);
   hipDeviceSynchronize();
   destroy_graphs(c);
-  hipFree(c->d_actor);
-  hipFree(c->d_actor_raw);
-  hipFree(c->d_chain);
-  hipFree(c->d_interp);
-  hipFree(c->d_act);
-  hipFree(c->d_halo);
-  hipFree(c->d_stats);
-  hipFree(c->d_tick_part);
-  hipFree(c->d_rows_part);
-  hipFree(c->d_rows_p);
-  hipFree(c->d_obs_sc);
-  hipFree(c->d_tables);
-  hipFree(c->d_flags);
-  hipFree(c->d_eps);
-  hipFree(c->d_slab);
-  hipFree(c->d_wslab);
-  hipFree(c->d_onb);
-  hipFree(c->d_wah);
-  hipFree(c->d_onb2);
-  hipFree(c->d_wah2);
-  hipFree(c->d_pen_partial);
-  hipFree(c->d_partial2);
-  hipFree(c->d_wpen);
-  hipFree(c->d_wres);
-  hipFree(c->d_wstat);
-  hipFree(c->d_stat_p);
-  hipFree(c->d_ticks);
   for (auto& e : c->ev)
     if (e) hipEventDestroy(e);
   for (int i = 0; i < kSlabs; ++i) {
@@ -696,16 +695,6 @@ int mdr_destroy(mdr_ctx* c) {
   if (c->ev_pc) hipEventDestroy(c->ev_pc);
   if (c->comm_stream) hipStreamDestroy(c->comm_stream);
   if (c->cap_stream) hipStreamDestroy(c->cap_stream);
-  hipFree(c->g_key); hipFree(c->g_key2); hipFree(c->g_ps); hipFree(c->g_incl);
-  hipFree(c->g_idx); hipFree(c->g_idx2); hipFree(c->g_ls); hipFree(c->g_tmp);
-  hipFree(c->g_kpos); hipFree(c->g_extra);
-  hipFree(c->g_part); hipFree(c->g_hist); hipFree(c->g_sel); hipFree(c->g_win);
-  hipFree(c->g_sorted); hipFree(c->g_map); hipFree(c->g_range); hipFree(c->g_tickets);
-  hipFree(c->d_tickets);
-  hipFree(c->fz.par[0]); hipFree(c->fz.bkt[0]); hipFree(c->fz.mbkt); hipFree(c->fz.map[0]); hipFree(c->fz.sel);
-  hipFree(c->fz.dec);
-  hipFree(c->fz.stamps);
-  hipFree(c->d_c5);
   if (c->comm) ncclCommDestroy(c->comm);
   delete c;
   return MDR_OK;
@@ -776,8 +765,7 @@ int mdr_bind(mdr_ctx* c, const mdr_soa* s) {
   c->coef_dirty = true;
   c->gq_map_stale = true;
   c->gq_s1 = c->gq_s2 = NAN;
-  for (auto& g : c->graphs) hipGraphExecDestroy(g.second.first);
-  c->graphs.clear();
+  drop_rollout_graphs(c);
   return MDR_OK;
 }
 
@@ -875,20 +863,17 @@ static int stage_recs(const void* src, int n, void* dst, hipStream_t st) {
   return MDR_OK;
 }
 
+// the tick records and the actor rollouts' obs scalars: one unit, its capacity d_ticks'
 static int ensure_ticks(mdr_ctx* c, int n) {
-  if (n > c->ticks_cap) {
-    HIP_TRY(hipDeviceSynchronize());  // queued graphs may still read the old buffers
-    hipFree(c->d_ticks);
-    hipFree(c->d_obs_sc);
-    c->d_ticks = nullptr;
-    c->d_obs_sc = nullptr;
-    int cap = n < 128 ? 128 : n;
-    HIP_TRY(hipMalloc(&c->d_ticks, cap * sizeof(TickArgs)));
-    HIP_TRY(hipMalloc(&c->d_obs_sc, (size_t)cap * 4 * sizeof(double)));
-    c->ticks_cap = cap;
-    destroy_graphs(c);
-  }
-  return MDR_OK;
+  if ((size_t)n <= c->d_ticks.capacity()) return MDR_OK;
+  HIP_TRY(hipDeviceSynchronize());  // queued graphs may still read the old buffers
+  destroy_graphs(c);                // (they hold the old addresses: gone before the buffers are)
+  const size_t cap = n < 128 ? 128 : n;
+  return grow_unit([&] { c->d_ticks.reset(), c->d_obs_sc.reset(); },
+                   [&] {
+                     if (int rc = dev_reserve(c->d_ticks, cap, "d_ticks")) return rc;
+                     return dev_reserve(c->d_obs_sc, cap * 4, "d_obs_sc");
+                   });
 }
 
 static int stage_ticks(mdr_ctx* c, int n, const mdr_tick* ticks, hipStream_t st) {
@@ -1072,7 +1057,7 @@ static int step_event_pair(mdr_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
 static int launch_count(mdr_ctx* c, int mode, const uint8_t* action, int64_t act_stride, const TickArgs* tk,
                         uint64_t tick0, int K, unsigned long long* slot, uint64_t* onb, uint32_t* wah,
                         const uint32_t* w_in, hipStream_t st, bool p_only) {
-  if (int rc = mdr_window_geometry_check(c->kp.n, c->onb_bytes, c->wah_bytes)) return rc;
+  if (int rc = mdr_window_geometry_check(c->kp.n, dev_bytes(c->d_onb), dev_bytes(c->d_wah))) return rc;
   const unsigned grid = win_grid(c, kCountWaves);
   unsigned* ticket = p_only ? c->d_tickets : nullptr;
 #define MDR_COUNT(A)                                                                                  \
@@ -1092,7 +1077,7 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
                               const TickArgs* tk, int K, int la_K, const double* rec, double* reward,
                               int64_t rew_stride, uint64_t* onb, uint32_t* wah, unsigned long long* next_slot,
                               const WinDrv& dv, hipStream_t st) {
-  if (int rc = mdr_window_geometry_check(c->kp.n, c->onb_bytes, c->wah_bytes)) return rc;
+  if (int rc = mdr_window_geometry_check(c->kp.n, dev_bytes(c->d_onb), dev_bytes(c->d_wah))) return rc;
   const unsigned grid = win_grid(c);
   hipEvent_t t0, t1;
   if (int rc = step_event_pair(c, &t0, &t1)) return rc;
@@ -1102,7 +1087,7 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
   WinPen wp{};
   if (common) {
     if (!c->d_wpen || !c->d_wres) return fail(MDR_ESTATE, "window launch: no penalty partial rows");
-    if (int rc = mdr_window_pen_check(c->kp.n, c->wpen_bytes)) return rc;
+    if (int rc = mdr_window_pen_check(c->kp.n, dev_bytes(c->d_wpen))) return rc;
     wp = WinPen{c->d_wpen, c->d_wres + 2 * kWindowMax};
   }
 #define MDR_SW_L(A, SI, KA_, FO, CO)                                                                      \
@@ -1283,15 +1268,10 @@ static int window_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
 // the second ON-mask / end-word set of the count-ahead pipeline (allocated on first use)
 static bool pipe_buffers(mdr_ctx* c) {
   if (c->d_onb2 && c->d_wah2) return true;
-  if (hipMalloc(&c->d_onb2, c->onb_bytes) != hipSuccess || hipMalloc(&c->d_wah2, c->wah_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    hipFree(c->d_onb2);
-    hipFree(c->d_wah2);
-    c->d_onb2 = nullptr;
-    c->d_wah2 = nullptr;
-    return false;
-  }
-  return true;
+  if (!c->d_onb2.reserve(c->d_onb.capacity()) && !c->d_wah2.reserve(c->d_wah.capacity())) return true;
+  (void)hipGetLastError();  // (the caller runs the windows unpipelined: no error is left behind)
+  c->d_onb2.reset(), c->d_wah2.reset();  // both or neither
+  return false;
 }
 
 // n ticks of a bang-bang source as ceil(n / win) closed-loop windows of near-equal size
@@ -1339,13 +1319,13 @@ static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, dou
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, kp, tk + t0, K, r, rew_stride, slot, extra...);
     };
     if (stats) {  // (the partial rows this launch's geometry writes)
-      if (int rc = mdr_window_stats_check(kp.n, c->wstat_bytes)) return rc;
+      if (int rc = mdr_window_stats_check(kp.n, dev_bytes(c->d_wstat))) return rc;
       if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, true, false, double*>, wstat);
       else closed(k_step_closed<kActDeadband, kWinHpt, true, false, double*>, wstat);
     } else if (common) {  // (grid x K pairs, a quarter of what the per-wave rows of k_step_window need)
-      if (int rc = mdr_window_pen_check(kp.n, c->wpen_bytes)) return rc;
-      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, false, true, double*>, c->d_wpen);
-      else closed(k_step_closed<kActDeadband, kWinHpt, false, true, double*>, c->d_wpen);
+      if (int rc = mdr_window_pen_check(kp.n, dev_bytes(c->d_wpen))) return rc;
+      if (mode == MDR_ACT_BANGBANG) closed(k_step_closed<kActBangBang, kWinHpt, false, true, double*>, c->d_wpen.get());
+      else closed(k_step_closed<kActDeadband, kWinHpt, false, true, double*>, c->d_wpen.get());
     } else if (mode == MDR_ACT_BANGBANG) {
       closed(k_step_closed<kActBangBang, kWinHpt, false, false>);
     } else {
@@ -1534,13 +1514,10 @@ static bool consecutive(const mdr_tick* ticks, int n) {
 // windows' block partials, or the per-tick form's k_tick_stats partials and a P scalar
 static int rollout_stats_scratch(mdr_ctx* c, int mode, bool need_p) {
   if (closed_ok(c, mode, true)) {
-    if (c->d_wstat) return MDR_OK;
-    const size_t bytes = mdr_window_stats_bytes(c->kp.n);
-    HIP_TRY(hipMalloc(&c->d_wstat, bytes));
-    c->wstat_bytes = bytes;
-    return MDR_OK;
+    return dev_reserve(c->d_wstat, mdr_window_stats_bytes(c->kp.n) / sizeof(double), "d_wstat");
   }
-  if (need_p && !c->d_stat_p) HIP_TRY(hipMalloc(&c->d_stat_p, sizeof(double)));
+  if (need_p)
+    if (int rc = dev_reserve(c->d_stat_p, 1, "d_stat_p")) return rc;
   return tick_scratch(c);
 }
 
@@ -1826,55 +1803,57 @@ hipError_t greedy_sort(void* tmp, size_t& bytes, const double* kin, double* kout
   return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kin, kout, vin, vout, (int)n, 0, 64, st);
 }
 
+// the greedy scratch is one unit: emptied as a whole, with its capacities
+void greedy_clear(mdr_ctx* c) {
+  c->g_key.reset(), c->g_key2.reset(), c->g_ps.reset(), c->g_incl.reset();
+  c->g_idx.reset(), c->g_idx2.reset(), c->g_ls.reset(), c->g_tmp.reset();
+  c->g_kpos.reset(), c->g_extra.reset();
+  c->g_part.reset(), c->g_hist.reset(), c->g_sel_rec.reset(), c->g_win.reset();
+  c->g_sorted.reset(), c->g_map.reset(), c->g_range.reset(), c->g_tickets.reset();
+  c->g_sel = nullptr;
+  c->g_cap = 0, c->gq_parts_cap = 0;
+}
+
 int greedy_scratch(mdr_ctx* c, int64_t n) {
   if (c->g_cap >= n) return MDR_OK;
-  hipFree(c->g_key); hipFree(c->g_key2); hipFree(c->g_ps); hipFree(c->g_incl);
-  hipFree(c->g_idx); hipFree(c->g_idx2); hipFree(c->g_ls); hipFree(c->g_tmp);
-  hipFree(c->g_kpos); hipFree(c->g_extra);
-  hipFree(c->g_part); hipFree(c->g_hist); hipFree(c->g_sel); hipFree(c->g_win);
-  hipFree(c->g_sorted); hipFree(c->g_map); hipFree(c->g_range); hipFree(c->g_tickets);
-  c->g_map = nullptr; c->g_range = nullptr; c->g_tickets = nullptr;
-  c->g_part = nullptr; c->g_hist = nullptr; c->g_sel = nullptr; c->g_win = nullptr;
-  c->g_sorted = nullptr;
   c->gq_keys_ready = false;
   c->fz_ready = false;
   c->gq_hist_dirty = false;
-  HIP_TRY(hipMalloc(&c->g_key, n * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_key2, n * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_ps, n * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_incl, n * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_idx, n * sizeof(int)));
-  HIP_TRY(hipMalloc(&c->g_idx2, n * sizeof(int)));
-  HIP_TRY(hipMalloc(&c->g_ls, n));
-  HIP_TRY(hipMalloc(&c->g_kpos, 2 * sizeof(int64_t)));
-  HIP_TRY(hipMalloc(&c->g_extra, 64 * sizeof(int64_t)));
-  // (min, max) partials: k_gq_keys' grid, or the grid of the step kernel whose epilogue writes the
-  // keys (k_step_pipe: a block per kStepGqWaves x tpw x 128 houses, tpw >= 2)
-  c->gq_parts_cap = (int)std::max<int64_t>(kGqParts, (n + 1023) / 1024);
-  HIP_TRY(hipMalloc(&c->g_part, 2 * (size_t)c->gq_parts_cap * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_hist, kGqHistWords * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->g_hist, 0, kGqHistWords * sizeof(unsigned)));  // (the kernels re-zero what they read)
-  HIP_TRY(hipMalloc(&c->g_sel, kGqSelBytes));
-  HIP_TRY(hipMalloc(&c->g_map, kGqCells * sizeof(uint32_t)));
-  {
+  const int rc = grow_unit([&] { greedy_clear(c); }, [&]() -> int {
+    if (int rc = dev_reserve(c->g_key, n, "g_key")) return rc;
+    if (int rc = dev_reserve(c->g_key2, n, "g_key2")) return rc;
+    if (int rc = dev_reserve(c->g_ps, n, "g_ps")) return rc;
+    if (int rc = dev_reserve(c->g_incl, n, "g_incl")) return rc;
+    if (int rc = dev_reserve(c->g_idx, n, "g_idx")) return rc;
+    if (int rc = dev_reserve(c->g_idx2, n, "g_idx2")) return rc;
+    if (int rc = dev_reserve(c->g_ls, n, "g_ls")) return rc;
+    if (int rc = dev_reserve(c->g_kpos, 2, "g_kpos")) return rc;
+    if (int rc = dev_reserve(c->g_extra, 64, "g_extra")) return rc;
+    // (min, max) partials: k_gq_keys' grid, or the grid of the step kernel whose epilogue writes the
+    // keys (k_step_pipe: a block per kStepGqWaves x tpw x 128 houses, tpw >= 2)
+    const int parts = (int)std::max<int64_t>(kGqParts, (n + 1023) / 1024);
+    if (int rc = dev_reserve(c->g_part, 2 * (size_t)parts, "g_part")) return rc;
+    c->gq_parts_cap = parts;
+    if (int rc = dev_reserve(c->g_hist, kGqHistWords, "g_hist", true)) return rc;  // (the kernels re-zero what they read)
+    if (int rc = dev_reserve(c->g_sel_rec, kGqSelBytes, "g_sel")) return rc;
+    c->g_sel = reinterpret_cast<GqSel*>(c->g_sel_rec.get());
+    if (int rc = dev_reserve(c->g_map, kGqCells, "g_map")) return rc;
     unsigned char init[kGqSelBytes] = {};
     uint32_t map[kGqCells];
     gq_sel_init(init, map);
     HIP_TRY(hipMemcpy(c->g_sel, init, kGqSelBytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->g_map, map, sizeof(map), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMalloc(&c->g_win, (kGqCap + 1) * sizeof(uint4)));  // (sharded: [0] = the count header)
-  HIP_TRY(hipMalloc(&c->g_range, 2 * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->g_tickets, kTicketWords * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->g_tickets, 0, kTicketWords * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->g_sorted, kGqCap * sizeof(uint4)));
-  size_t b1 = 0, b2 = 0;
-  HIP_TRY(greedy_sort(nullptr, b1, c->g_key, c->g_key2, c->g_idx, c->g_idx2, n, nullptr));
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b2, c->g_ps, c->g_incl, (int)n));
-  c->g_tmp_bytes = b1 > b2 ? b1 : b2;
-  HIP_TRY(hipMalloc(&c->g_tmp, c->g_tmp_bytes));
-  c->g_cap = n;
-  return MDR_OK;
+    if (int rc = dev_reserve(c->g_win, kGqCap + 1, "g_win")) return rc;  // (sharded: [0] = the count header)
+    if (int rc = dev_reserve(c->g_range, 2, "g_range")) return rc;
+    if (int rc = dev_reserve(c->g_tickets, kTicketWords, "g_tickets", true)) return rc;
+    if (int rc = dev_reserve(c->g_sorted, kGqCap, "g_sorted")) return rc;
+    size_t b1 = 0, b2 = 0;
+    HIP_TRY(greedy_sort(nullptr, b1, c->g_key, c->g_key2, c->g_idx, c->g_idx2, n, nullptr));
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, b2, c->g_ps.get(), c->g_incl.get(), (int)n));
+    return dev_reserve(c->g_tmp, b1 > b2 ? b1 : b2, "g_tmp");
+  });
+  if (!rc) c->g_cap = n;
+  return rc;
 }
 
 // before a producer (k_gq_keys, the step's GQ epilogue) adds to g_hist: counts an earlier producer
@@ -1882,7 +1861,7 @@ int greedy_scratch(mdr_ctx* c, int64_t n) {
 // are zeroed first, so the select never sees the sum of two states
 int gq_hist_produce(mdr_ctx* c, hipStream_t st) {
   if (c->gq_hist_dirty) {
-    hipLaunchKernelGGL(k_zero_u64, dim3(64), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(c->g_hist),
+    hipLaunchKernelGGL(k_zero_u64, dim3(64), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(c->g_hist.get()),
                        (int64_t)(kGqHistWords / 2));
     LAUNCH_CHECK("k_zero_u64 (g_hist)");
   }
@@ -1977,13 +1956,13 @@ int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
   }
   hipLaunchKernelGGL(k_greedy_keys, dim3(blocks(n, 256)), dim3(256), 0, st, c->kp, c->g_key, c->g_idx);
   LAUNCH_CHECK("k_greedy_keys");
-  size_t b = c->g_tmp_bytes;
+  size_t b = c->g_tmp.capacity();
   HIP_TRY(greedy_sort(c->g_tmp, b, c->g_key, c->g_key2, c->g_idx, c->g_idx2, n, st));
   hipLaunchKernelGGL(k_greedy_gather, dim3(blocks(n, 256)), dim3(256), 0, st, c->kp, c->g_idx2, c->g_ps,
                      c->g_ls);
   LAUNCH_CHECK("k_greedy_gather");
-  b = c->g_tmp_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->g_tmp, b, c->g_ps, c->g_incl, n, st));
+  b = c->g_tmp.capacity();
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->g_tmp.get(), b, c->g_ps.get(), c->g_incl.get(), n, st));
   hipLaunchKernelGGL(k_greedy_walk, dim3(1), dim3(256), 0, st, (int64_t)n, c->g_incl, c->g_ps, c->g_ls,
                      budget, pmin, c->g_kpos, c->g_extra, 64);
   LAUNCH_CHECK("k_greedy_walk");
@@ -2025,47 +2004,42 @@ int mdr_greedy_state(mdr_ctx* c, uint64_t* out) {
 }  // extern "C"
 
 namespace {
-// the fused tick's buffers (mdr_kernels.h GqfBufs), for a cluster of n houses
-int gqf_scratch(mdr_ctx* c, int64_t n) {
-  if (c->fz_cap_n >= n && c->fz.par[0]) return MDR_OK;
-  HIP_TRY(hipDeviceSynchronize());
-  hipFree(c->fz.par[0]); hipFree(c->fz.bkt[0]); hipFree(c->fz.mbkt); hipFree(c->fz.map[0]); hipFree(c->fz.sel);
-  hipFree(c->fz.dec);
-  unsigned long long* keep_stamps = c->fz.stamps;
+// the fused tick's buffers (mdr_kernels.h GqfBufs), for a cluster of n houses: one unit, but for the
+// stamps (mdr_greedy_fused_stamps), which outlive a regrow
+void gqf_clear(mdr_ctx* c) {
+  c->fz_regions.reset(), c->fz_bkt.reset(), c->fz_mbkt.reset(), c->fz_maps.reset(), c->fz_sel.reset(), c->fz_dec.reset();
   c->fz = GqfBufs{};
-  c->fz.stamps = keep_stamps;
+  c->fz.stamps = c->fz_stamps;
+  c->fz_cap_n = 0;
+}
+
+int gqf_scratch(mdr_ctx* c, int64_t n) {
+  if (c->fz_cap_n >= n) return MDR_OK;
+  HIP_TRY(hipDeviceSynchronize());
   c->fz_ready = false;
   // bucket capacity: 4x the houses a (copy, bin) holds on average under an equi-depth map, >= 32
   const int64_t avg = (n + (int64_t)gq_bins_eff(c->kp.n_global) * kGqCopies - 1) / ((int64_t)gq_bins_eff(c->kp.n_global) * kGqCopies);
   const int cap = (int)std::max<int64_t>(32, 4 * avg);
-  unsigned* regions = nullptr;
-  HIP_TRY(hipMalloc(&regions, (2 * (size_t)kGqfParWords + kGqfMissWords) * sizeof(unsigned)));
-  HIP_TRY(hipMemset(regions, 0, (2 * (size_t)kGqfParWords + kGqfMissWords) * sizeof(unsigned)));
-  c->fz.par[0] = regions;
-  c->fz.par[1] = regions + kGqfParWords;
-  c->fz.miss = regions + 2 * kGqfParWords;
-  uint4* bk = nullptr;
   const size_t nb = (size_t)kGqCopies * kGqBand * 64 * cap;
-  HIP_TRY(hipMalloc(&bk, 2 * nb * sizeof(uint4)));
-  c->fz.bkt[0] = bk;
-  c->fz.bkt[1] = bk + nb;
-  HIP_TRY(hipMalloc(&c->fz.mbkt, (size_t)kGqCopies * 128 * cap * sizeof(uint4)));
-  c->fz.cap = cap;
-  c->fz.mcap = cap;
-  uint32_t* maps = nullptr;
-  HIP_TRY(hipMalloc(&maps, 2 * kGqCells * sizeof(uint32_t)));
-  c->fz.map[0] = maps;
-  c->fz.map[1] = maps + kGqCells;
-  HIP_TRY(hipMalloc(&c->fz.sel, kGqSelBytes));
-  {
+  const int rc = grow_unit([&] { gqf_clear(c); }, [&]() -> int {
+    if (int rc = dev_reserve(c->fz_regions, 2 * (size_t)kGqfParWords + kGqfMissWords, "fz.par", true)) return rc;
+    if (int rc = dev_reserve(c->fz_bkt, 2 * nb, "fz.bkt")) return rc;
+    if (int rc = dev_reserve(c->fz_mbkt, (size_t)kGqCopies * 128 * cap, "fz.mbkt")) return rc;
+    if (int rc = dev_reserve(c->fz_maps, 2 * (size_t)kGqCells, "fz.map")) return rc;
+    if (int rc = dev_reserve(c->fz_sel, kGqSelBytes, "fz.sel")) return rc;
     unsigned char init[kGqSelBytes] = {};
     uint32_t map[kGqCells];
     gqf_sel_init(init, map);
-    HIP_TRY(hipMemcpy(c->fz.sel, init, kGqSelBytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->fz.map[0], map, sizeof(map), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->fz.map[1], map, sizeof(map), hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMalloc(&c->fz.dec, (size_t)n));
+    HIP_TRY(hipMemcpy(c->fz_sel, init, kGqSelBytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->fz_maps, map, sizeof(map), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->fz_maps + kGqCells, map, sizeof(map), hipMemcpyHostToDevice));
+    return dev_reserve(c->fz_dec, (size_t)n, "fz.dec");
+  });
+  if (rc) return rc;
+  unsigned* par = c->fz_regions;  // the kernels' views, once the unit is whole
+  c->fz = GqfBufs{{par, par + kGqfParWords}, par + 2 * kGqfParWords, {c->fz_bkt, c->fz_bkt + nb}, c->fz_mbkt,
+                  {c->fz_maps, c->fz_maps + kGqCells}, reinterpret_cast<GqSel*>(c->fz_sel.get()), c->fz_dec,
+                  cap, cap, c->fz_stamps};
   c->fz_cap_n = n;
   c->fz_par = 0;
   return MDR_OK;
@@ -2101,15 +2075,13 @@ int mdr_greedy_fused_stamps(mdr_ctx* c, int on, uint64_t* out) {
   if (!c) return fail(MDR_EARG, "mdr_greedy_fused_stamps: null ctx");
   if (out && c->fz.stamps)
     HIP_TRY(hipMemcpy(out, c->fz.stamps, kGqSelBlocks * kGqfStampWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  if (on && !c->fz.stamps) {
-    HIP_TRY(hipMalloc(&c->fz.stamps, kGqSelBlocks * kGqfStampWords * sizeof(uint64_t)));
-    HIP_TRY(hipMemset(c->fz.stamps, 0, kGqSelBlocks * kGqfStampWords * sizeof(uint64_t)));
-  }
+  if (on)
+    if (int rc = dev_reserve(c->fz_stamps, (size_t)kGqSelBlocks * kGqfStampWords, "fz.stamps", true)) return rc;
   if (!on && c->fz.stamps) {
     HIP_TRY(hipDeviceSynchronize());
-    hipFree(c->fz.stamps);
-    c->fz.stamps = nullptr;
+    c->fz_stamps.reset();
   }
+  c->fz.stamps = c->fz_stamps;
   return MDR_OK;
 }
 
@@ -2385,13 +2357,13 @@ int mdr_greedy_select(mdr_ctx* c, int64_t n, const double* key, const double* po
   hipStream_t st = S(stream);
   hipLaunchKernelGGL(k_greedy_iota, dim3(blocks(n, 256)), dim3(256), 0, st, n, c->g_idx);
   LAUNCH_CHECK("k_greedy_iota");
-  size_t b = c->g_tmp_bytes;
+  size_t b = c->g_tmp.capacity();
   HIP_TRY(greedy_sort(c->g_tmp, b, key, c->g_key2, c->g_idx, c->g_idx2, n, st));
   hipLaunchKernelGGL(k_greedy_gather_rows, dim3(blocks(n, 256)), dim3(256), 0, st, n, c->g_idx2, power, lock,
                      c->g_ps, c->g_ls);
   LAUNCH_CHECK("k_greedy_gather_rows");
-  b = c->g_tmp_bytes;
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->g_tmp, b, c->g_ps, c->g_incl, (int)n, st));
+  b = c->g_tmp.capacity();
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(c->g_tmp.get(), b, c->g_ps.get(), c->g_incl.get(), (int)n, st));
   double pmin = INFINITY;
   for (int k = 0; k < c->cfg.n_cap; ++k) pmin = fmin(pmin, c->cfg.cap_table[k] / c->cfg.cop);
   hipLaunchKernelGGL(k_greedy_walk, dim3(1), dim3(256), 0, st, n, c->g_incl, c->g_ps, c->g_ls, budget, pmin,
@@ -2581,7 +2553,7 @@ int mdr_set_rollout_window(mdr_ctx* c, int ticks) {
 int mdr_cluster_stats(mdr_ctx* c, const double* reward, double* out, void* stream) {
   if (!c || !out) return fail(MDR_EARG, "mdr_cluster_stats: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_cluster_stats: context not bound");
-  if (!c->d_stats) HIP_TRY(hipMalloc(&c->d_stats, sizeof(double) * kStats * kStatsBlocks));
+  if (int rc = dev_reserve(c->d_stats, (size_t)kStats * kStatsBlocks, "d_stats")) return rc;
   const unsigned nb = (unsigned)std::min<int64_t>(kStatsBlocks, (c->kp.n + 255) / 256);
   hipLaunchKernelGGL(k_cluster_stats, dim3(nb), dim3(256), 0, S(stream), c->kp, reward, c->d_stats);
   LAUNCH_CHECK("k_cluster_stats");
@@ -2741,15 +2713,10 @@ int net_width(const mdr_actor_net& a) {
 int chain_ensure(mdr_ctx* c, int F, hipStream_t st) {
   const size_t w4 = (size_t)((net_width(c->net) + 3) & ~3);
   const size_t need = ((size_t)F + 2 * w4) * (size_t)c->kp.n * sizeof(float);
-  if (need <= c->chain_cap) return MDR_OK;
+  if (need <= dev_bytes(c->d_chain)) return MDR_OK;
   HIP_TRY(hipStreamSynchronize(st));
-  hipFree(c->d_chain);
-  c->d_chain = nullptr;
-  HIP_TRY(hipMalloc(&c->d_chain, need));
-  c->chain_cap = need;
-  for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second);
-  c->actor_graphs.clear();
-  return MDR_OK;
+  drop_actor_graphs(c);
+  return dev_reserve(c->d_chain, need / sizeof(float), "d_chain");
 }
 
 // The packed weight image for this obs layout (k_actor_pack from the loaded fp32 weights): packed
@@ -2763,14 +2730,11 @@ int actor_ensure_packed(mdr_ctx* c, const mdr_obs_spec* sp, hipStream_t st) {
   const std::vector<int> key{d.n_own, d.own4, d.msg_w, d.m4, d.n_comm, d.mb, d.ks1, d.nf, d.ring, d.lo,
                              c->actor.precision, d.f16};
   if (key == c->actor_key) return MDR_OK;
-  if ((size_t)d.off_end > c->actor_cap) {
+  if ((size_t)d.off_end > c->d_actor.capacity()) {
     HIP_TRY(hipStreamSynchronize(st));
-    hipFree(c->d_actor);
-    c->d_actor = nullptr;
-    HIP_TRY(hipMalloc(&c->d_actor, d.off_end));
-    c->actor_cap = d.off_end;
-    for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second);
-    c->actor_graphs.clear();
+    drop_actor_graphs(c);
+    c->actor_key.clear();  // (no image until k_actor_pack below has one to write)
+    if (int rc = dev_reserve(c->d_actor, d.off_end, "d_actor")) return rc;
   }
   const mdr_actor_spec& a = c->actor;
   const float* w1 = c->d_actor_raw;
@@ -2869,7 +2833,7 @@ int launch_actor(mdr_ctx* c, const mdr_obs_spec* sp, const ObsArgs& o, const dou
                  const TickArgs* tkp, const ActorOut& out_in, hipStream_t st) {
   if (!actor_fused_ok(c, sp)) return launch_actor_chain(c, sp, o, p_dev, tick, tkp, out_in, st);
   ActorOut out = out_in;
-  out.ovf = reinterpret_cast<unsigned*>(c->d_flags) + 1;  // (mdr_actor_status; read by the fp16 form only)
+  out.ovf = reinterpret_cast<unsigned*>(c->d_flags.get()) + 1;  // (mdr_actor_status; read by the fp16 form only)
   out.head = c->actor_head;  // (mdr_actor_set_head)
   out.eps = c->d_eps;
   ActorDims d;
@@ -2964,16 +2928,11 @@ int mdr_actor_load_net(mdr_ctx* c, const mdr_actor_net* a, const float* const* w
   // captured actor graphs hold the chain's weight pointers and the fused / chain choice: they stay
   // valid while the buffer and the net's shape do (a PPO update reloads weights of the same shape)
   const bool same = c->actor_ready && memcmp(&c->net, a, sizeof(mdr_actor_net)) == 0;
-  if (!same || nraw * sizeof(float) > c->actor_raw_cap) {
-    for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second);
-    c->actor_graphs.clear();
-  }
-  if (nraw * sizeof(float) > c->actor_raw_cap) {
+  if (!same || nraw > c->d_actor_raw.capacity()) drop_actor_graphs(c);
+  if (nraw > c->d_actor_raw.capacity()) {
     HIP_TRY(hipStreamSynchronize(S(stream)));
-    hipFree(c->d_actor_raw);
-    c->d_actor_raw = nullptr;
-    HIP_TRY(hipMalloc(&c->d_actor_raw, nraw * sizeof(float)));
-    c->actor_raw_cap = nraw * sizeof(float);
+    c->actor_ready = false;  // (no weights until the copies below are queued)
+    if (int rc = dev_reserve(c->d_actor_raw, nraw, "d_actor_raw")) return rc;
   }
   float* r = c->d_actor_raw;
   int in = a->n_in;
@@ -3062,8 +3021,8 @@ int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars*
   if (int rc = check_actor_obs(c, sp, "mdr_actor_profile", S(stream))) return rc;
   hipStream_t st = S(stream);
   const int nb = c->n_cu * 16;  // waves (at most 16 per block, one block per CU)
-  unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)nb * 8 * sizeof(unsigned long long)));
+  Dev<unsigned long long> d;
+  if (int rc = dev_reserve(d, (size_t)nb * 8, "mdr_actor_profile: cycles")) return rc;
   HIP_TRY(hipMemsetAsync(d, 0, (size_t)nb * 8 * sizeof(unsigned long long), st));
   ActorOut out{nullptr, nullptr, nullptr, nullptr, nullptr, d};
   int rc = launch_actor(c, sp, obs_args(c, sp, sc), p_dev, 0, nullptr, out, st);
@@ -3081,7 +3040,6 @@ int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars*
   } else if (!rc) {
     rc = fail(MDR_EHIP, "mdr_actor_profile: readback");
   }
-  hipFree(d);
   return rc;
 }
 
@@ -3089,25 +3047,13 @@ int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars*
 // the block partials belong to the context: allocated (zeroed) before any capture that uses them;
 // every launch overwrites the partials it then reads, so no node ever has to clear them
 static int tick_scratch(mdr_ctx* c) {
-  if (c->d_tick_part) return MDR_OK;
-  HIP_TRY(hipMalloc(&c->d_tick_part, sizeof(double) * kStats * kTickBlocks));
-  HIP_TRY(hipMemset(c->d_tick_part, 0, sizeof(double) * kStats * kTickBlocks));
-  return MDR_OK;
+  return dev_reserve(c->d_tick_part, (size_t)kStats * kTickBlocks, "d_tick_part", true);
 }
 
 // mdr_greedy_rollout_stats' slabs: a batch of kTickRowsBatch ticks' block partials and cluster powers
 static int rows_scratch(mdr_ctx* c) {
-  if (c->d_rows_part && c->d_rows_p) return MDR_OK;
-  const size_t bytes = sizeof(double) * kStats * kTickBlocks * kTickRowsBatch;
-  if (!c->d_rows_part) {
-    HIP_TRY(hipMalloc(&c->d_rows_part, bytes));
-    HIP_TRY(hipMemset(c->d_rows_part, 0, bytes));
-  }
-  if (!c->d_rows_p) {
-    HIP_TRY(hipMalloc(&c->d_rows_p, sizeof(double) * kTickRowsBatch));
-    HIP_TRY(hipMemset(c->d_rows_p, 0, sizeof(double) * kTickRowsBatch));
-  }
-  return MDR_OK;
+  if (int rc = dev_reserve(c->d_rows_part, (size_t)kStats * kTickBlocks * kTickRowsBatch, "d_rows_part", true)) return rc;
+  return dev_reserve(c->d_rows_p, kTickRowsBatch, "d_rows_p", true);
 }
 
 static int check_tick_stats_ctx(mdr_ctx* c, const char* who) {
@@ -3380,7 +3326,8 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
     }
     return MDR_OK;
   };
-  if (!action && !c->d_act) HIP_TRY(hipMalloc(&c->d_act, c->kp.n));  // context-owned action row
+  if (!action)  // context-owned action row
+    if (int rc = dev_reserve(c->d_act, c->kp.n, "d_act")) return rc;
   if (stats)
     if (int rc = tick_scratch(c)) return rc;  // (before any capture)
   if (!use_graph) {
@@ -3392,7 +3339,7 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
                            (int64_t)(uintptr_t)reward, rew_stride, (int64_t)(uintptr_t)p_dev,
                            (int64_t)(uintptr_t)sp->comm_table,
                            (int64_t)(uintptr_t)sp->halo_msg, sp->n_feat | ((int64_t)c->actor_head << 32),
-                           (int64_t)(uintptr_t)c->d_actor};
+                           (int64_t)(uintptr_t)c->d_actor.get()};
   // (the head, mdr_actor_set_head, is baked into the captured launches, so it is part of the key above
   // n_feat — MDR_HEAD_SOFTMAX = 0 leaves the softmax keys as they were; epsilon is not: the kernels load it)
   if (snap)  // (longer keys: never equal to a rollout's without snapshots)
@@ -3488,14 +3435,12 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
   if (int rc = refresh_if_dirty(c, st)) return rc;
   if (int rc = stage_ticks(c, n, ticks, st)) return rc;
   if (int rc = stage_recs(osc, n, c->d_obs_sc, st)) return rc;
-  if (!action && !c->d_act) HIP_TRY(hipMalloc(&c->d_act, c->kp.n));
-  const size_t hbytes = (size_t)2 * (lo + hi) * M * sizeof(float);
-  if (halo && hbytes > c->halo_bytes) {
+  if (!action)
+    if (int rc = dev_reserve(c->d_act, c->kp.n, "d_act")) return rc;
+  const size_t hrows = (size_t)2 * (lo + hi) * M;
+  if (halo && hrows > c->d_halo.capacity()) {
     HIP_TRY(hipStreamSynchronize(st));
-    hipFree(c->d_halo);
-    c->d_halo = nullptr;
-    HIP_TRY(hipMalloc(&c->d_halo, hbytes));
-    c->halo_bytes = hbytes;
+    if (int rc = dev_reserve(c->d_halo, hrows, "d_halo")) return rc;
   }
   float* mine = c->d_halo;                                    // [hi first | lo last] of this shard
   float* recv = c->d_halo ? c->d_halo + (size_t)(lo + hi) * M : nullptr;  // [lo before | hi after]
@@ -3509,12 +3454,9 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
     const int W = lo + hi;
     const size_t rows_words = ((size_t)c->world * W * M + 1) / 2;  // floats, two per u64 word
     const size_t words = c->slab_len + rows_words;
-    if (3 * words * sizeof(unsigned long long) > c->c5_bytes) {
+    if (3 * words > c->d_c5.capacity()) {
       HIP_TRY(hipStreamSynchronize(st));
-      hipFree(c->d_c5);
-      c->d_c5 = nullptr;
-      HIP_TRY(hipMalloc(&c->d_c5, 3 * words * sizeof(unsigned long long)));
-      c->c5_bytes = 3 * words * sizeof(unsigned long long);
+      if (int rc = dev_reserve(c->d_c5, 3 * words, "d_c5")) return rc;
     }
     auto buf = [&](int t) { return c->d_c5 + (size_t)(t % 3) * words; };
     auto rows = [&](int t) { return reinterpret_cast<float*>(buf(t) + c->slab_len); };
@@ -3659,16 +3601,9 @@ int mdr_interp_load(mdr_ctx* c, const mdr_interp_spec* sp) {
   a.cfg[0] = sp->cfg_ua; a.cfg[1] = sp->cfg_cm; a.cfg[2] = sp->cfg_ca; a.cfg[3] = sp->cfg_hm;
   const size_t bytes = (size_t)(ng + total + MDR_MAX_CAP) * sizeof(double);
   HIP_TRY(hipSetDevice(c->cfg.device));
-  if (bytes > c->interp_bytes) {
-    HIP_TRY(hipDeviceSynchronize());  // a previous table may still be read by queued launches
-    hipFree(c->d_interp);
-    c->d_interp = nullptr;
-    c->interp_bytes = 0;
-    if (hipMalloc(&c->d_interp, bytes) != hipSuccess) return fail(MDR_ENOMEM, "mdr_interp_load: table");
-    c->interp_bytes = bytes;
-  } else {
-    HIP_TRY(hipDeviceSynchronize());
-  }
+  HIP_TRY(hipDeviceSynchronize());  // a previous table may still be read by queued launches
+  c->interp_ready = false;          // (c->interp views the old table until the copies below succeed)
+  if (c->d_interp.reserve(bytes / sizeof(double))) return fail(MDR_ENOMEM, "mdr_interp_load: table");
   HIP_TRY(hipMemcpy(c->d_interp, sp->grid, ng * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_interp + ng, sp->values, total * sizeof(double), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_interp + ng + total, c->cfg.cap_table, MDR_MAX_CAP * sizeof(double),
