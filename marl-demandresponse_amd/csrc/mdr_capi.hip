@@ -21,6 +21,7 @@
 #include "mdr_interp.h"
 #include "mdr_obs_dev.h"
 #include "mdr_kernels.h"
+#include "mdr_validity.h"
 
 using namespace mdr;
 
@@ -126,8 +127,7 @@ struct mdr_ctx {
   Dev<unsigned long long> d_slab;        // kSlabs x kCountShards x n_cap count slabs (ring of 3 on
                                          // the step path, 4 in the overlapped sharded pipeline)
   int slab_len = 0;
-  int ring = 0;                          // slab of the current tick
-  bool counts_ready = false;             // current slab filled (phase 1 or previous lookahead)
+  Validity v;                            // what the host believes the buffers hold (mdr_validity.h)
   Dev<double> d_pen_partial;             // 2 per block of k_step_t
   Dev<double> d_partial2;
   Dev<double> d_wpen;                    // common-penalty windows: {sum pen/N, max pen} [kWindowMax][tiles_padded][2]
@@ -152,17 +152,15 @@ struct mdr_ctx {
   int win = kWindowMax;                  // ticks per k_step_window launch (0: one-tick path)
   Dev<unsigned long long> d_wslab;       // 3 window count slots (mdr_kernels.hip K1W: slab | red | rec)
   int wslab_len = 0;
-  bool wslab_dirty = true;               // the slots' shard part must be zero when a rollout starts
   Dev<uint64_t> d_onb;                   // per-tick ON lane masks of the next window [tiles][HPT][kWindowMax]
   Dev<uint32_t> d_wah;                   // FSM word at the end of the next window, per house
   Dev<uint64_t> d_onb2;                  // second set for the count-ahead pipeline (pipe_buffers: a unit)
   Dev<uint32_t> d_wah2;
-  bool coef_dirty = true;
   Dev<int> d_flags;                      // [0] params_bad
   Dev<unsigned> d_tickets;               // k_count_window's grid_last_block counters (zero between uses)
   // rollout tick drivers (a unit with d_obs_sc: ensure_ticks)
   Dev<TickArgs> d_ticks;
-  std::map<GraphKey, std::pair<hipGraphExec_t, int>> graphs;  // exec, ring phase at end
+  std::map<GraphKey, std::pair<hipGraphExec_t, int>> graphs;  // exec, the ring at the end of its capture
   // greedy scratch: one unit (greedy_scratch / greedy_clear), sized for g_cap houses
   int64_t g_cap = 0;
   Dev<double> g_key, g_key2, g_ps, g_incl;
@@ -181,16 +179,10 @@ struct mdr_ctx {
   Dev<double> g_range;                   // sharded select: this shard's (min, -max) key range (k_gq_range)
   Dev<uint4> g_sorted;                   // the window in (key, house) order (k_gq_select)
   int gq_parts_cap = 0;                  // g_part capacity in (min, max) pairs
-  bool gq_keys_ready = false;            // keys + superbin histogram of the current state are in place
-  bool gq_hist_dirty = false;            // a producer added counts to g_hist that no select has consumed
-  bool gq_slab_zeroed = false;           // the codes' producer zeroed the slab the decisions count into
-                                         // (not when its step counted a lookahead there)
   bool gq_band = true;                   // MDR_OPT_GQ_BAND: k_gq_binsc (the predicted band) vs k_gq_bins
   // the fused greedy tick (mdr_greedy_rollout; mdr_kernels.h GqfBufs)
   bool gq_adaptive = true;               // MDR_OPT_GQ_ADAPTIVE: mdr_greedy_rollout skips the band on budget jumps
   bool gq_band_skip = false;             // (set around one mdr_ctrl_greedy call by mdr_greedy_rollout)
-  double gq_s1 = NAN, gq_s2 = NAN;       // the last two budgets mdr_greedy_rollout decided for
-  bool gq_map_stale = true;              // the state was written since the key maps were last built (k_gq_remap)
   bool gq_fused = false;                 // MDR_OPT_GQ_FUSED (r06: slower than the band form)
   GqfBufs fz{};                          // views of the blocks below, as the kernels take them
   Dev<unsigned> fz_regions;              // par[0] | par[1] | miss
@@ -200,9 +192,6 @@ struct mdr_ctx {
   Dev<uint8_t> fz_dec;
   Dev<unsigned long long> fz_stamps;     // stamps: not of the unit (it survives a regrow)
   int64_t fz_cap_n = 0;                  // the cluster size the unit is allocated for (gqf_scratch / gqf_clear)
-  int fz_par = 0;                        // the parity the last producer wrote
-  bool fz_ready = false;                 // ... for the current state (the last step's GQ = 2 epilogue)
-  int gq_nparts = 0;                     //   (from the last step's epilogue: its grid's partials)
   // multi-GPU
   ncclComm_t comm = nullptr;
   struct {                               // mdr_comm_host: the caller's collectives instead of RCCL
@@ -216,14 +205,6 @@ struct mdr_ctx {
   hipEvent_t ev_k1[kSlabs] = {}, ev_ar[kSlabs] = {}, ev_pc = nullptr;
   hipEvent_t ev[16] = {};
   std::vector<hipEvent_t>* step_events = nullptr;  // mdr_time_step_kernels: events around each step launch
-  struct {                               // mdr_rollout_begin: the first window already counted
-    bool on = false;
-    int n = 0, mode = 0;
-    uint64_t tick0 = 0;
-    const uint8_t* action = nullptr;
-    int64_t act_stride = 0;
-    bool sharded = false;                // counts allreduced over the ranks (for mdr_rollout_sharded)
-  } begun;
   // MA-PPO actor (row P): packed weight image, per-tick obs scalars of actor rollouts
   Dev<unsigned char> d_actor;
   Dev<float> d_actor_raw;        // the loaded fp32 weights (w1 b1 w2 b2 w3 b3), packed per obs layout
@@ -242,7 +223,7 @@ struct mdr_ctx {
   Dev<double> d_tick_part;     // k_tick_stats block partials
   Dev<double> d_rows_part;     // mdr_greedy_rollout_stats: [kTickRowsBatch][kTickBlocks][kStats] block partials
   Dev<double> d_rows_p;        //   and the batch's [kTickRowsBatch] cluster powers
-  std::map<std::vector<int64_t>, hipGraphExec_t> actor_graphs;
+  std::map<std::vector<int64_t>, std::pair<hipGraphExec_t, int>> actor_graphs;  // (as graphs)
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
   int64_t graphs_guarded = 0;            // captured graphs the memset guard walked (graph_memset_guard)
   int64_t graph_nodes_checked = 0;       //   and their nodes
@@ -335,7 +316,7 @@ int launch_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, co
   static_assert(MDR_ACT_BANGBANG == kActBangBang && MDR_ACT_DEADBAND_BANGBANG == kActDeadband,
                 "the kernels take the bang-bang sources by their public ids");
   hipLaunchKernelGGL(k_power_counts, dim3(blocks(c->kp.n, 256 * kPcHouses)), dim3(256), 0, st, c->kp, action, mode,
-                     tick, tkp, slab ? slab : slab_at(c, c->ring));
+                     tick, tkp, slab ? slab : slab_at(c, c->v.ring()));
   LAUNCH_CHECK("k_power_counts");
   return MDR_OK;
 }
@@ -343,11 +324,11 @@ int launch_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, co
 // parameter-derived state (the fast-division range flag) after a change; called before any
 // launch sequence is captured, so graphs never contain it
 int refresh_if_dirty(mdr_ctx* c, hipStream_t st) {
-  if (!c->coef_dirty) return MDR_OK;
+  if (!c->v.coef_dirty()) return MDR_OK;
   HIP_TRY(hipMemsetAsync(c->d_flags, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_refresh, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp, c->d_flags);
   LAUNCH_CHECK("k_refresh");
-  c->coef_dirty = false;
+  c->v.coef_refreshed();
   return MDR_OK;
 }
 
@@ -416,10 +397,7 @@ int launch_step_on(mdr_ctx* c, const uint8_t* action, int mode, TickArgs tk, con
     LAUNCH_CHECK("k_step_pipe");
     // (a lookahead's counts are in nxt: k_gq_keys leaves them, mdr_ctrl_greedy zeroes the slab)
     if (gq && !epi) return launch_gq_keys(c, st, lookahead ? nullptr : nxt);
-    if (epi) {
-      c->gq_nparts = (int)nb;
-      c->gq_slab_zeroed = true;  // (the GQ epilogue zeroes its next slab; epi implies no lookahead)
-    }
+    if (epi) c->v.keys_from_epilogue((int)nb);
     return MDR_OK;
   }
   if (c->fastdiv) {
@@ -438,14 +416,10 @@ int launch_step_on(mdr_ctx* c, const uint8_t* action, int mode, TickArgs tk, con
 int launch_step(mdr_ctx* c, const uint8_t* action, int mode, TickArgs tk, const TickArgs* tkp,
                 double* reward, int lookahead, int ctrl, uint8_t* ctrl_out, double* p_out,
                 hipStream_t st) {
-  c->gq_keys_ready = false;
-  c->fz_ready = false;
   int rc = launch_step_on(c, action, mode, tk, tkp, reward, lookahead, ctrl, ctrl_out, p_out,
-                          slab_at(c, c->ring), slab_at(c, c->ring + 1), slab_at(c, c->ring + 2), 0, st);
+                          slab_at(c, c->v.ring()), slab_at(c, c->v.ring() + 1), slab_at(c, c->v.ring() + 2), 0, st);
   if (rc) return rc;
-  c->ring = (c->ring + 1) % 3;
-  c->counts_ready = lookahead != 0;
-  c->gq_keys_ready = ctrl == MDR_CTRL_GREEDY_KEYS;
+  c->v.step_issued(lookahead != 0, ctrl == MDR_CTRL_GREEDY_KEYS);
   return MDR_OK;
 }
 
@@ -453,17 +427,13 @@ int launch_step(mdr_ctx* c, const uint8_t* action, int mode, TickArgs tk, const 
 
 extern "C" {
 
-// an early first-window count (mdr_rollout_begin) is only valid for the mdr_rollout that follows
-// it directly: every other entry point that changes the state or uses the slots discards it
-static void drop_begun(mdr_ctx* c) {
-  if (c && c->begun.on) {
-    c->begun.on = false;
-    c->wslab_dirty = true;
-  }
-  if (c) {
-    c->gq_keys_ready = false;  // (every such entry point may change the state)
-    c->fz_ready = false;
-  }
+// An entry point that may write the house state or the count slabs is entered (c may be null: the
+// checks follow).  An early first-window count (mdr_rollout_begin) is only valid for the mdr_rollout
+// that follows it directly, so it is discarded too.
+static void enter_writer(mdr_ctx* c) {
+  if (!c) return;
+  c->v.drop_early_count();
+  c->v.state_may_change();
 }
 
 #ifndef MDR_SRC_HASH
@@ -501,9 +471,9 @@ int mdr_graph_info(mdr_ctx* c, int64_t* out, int n) {
 // bytes passed, non-zero 64-bit words after replay 1 (slabs pre-filled with 0xA5), after replay 2
 // (re-filled), after replay 3 (not re-filled), non-zero words after a kernel (k_zero_u64) zeroing}
 int mdr_graph_memset_probe(mdr_ctx* c, int64_t* out, int n, void* stream) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c || !out || n < 13) return fail(MDR_EARG, "mdr_graph_memset_probe: need out[13]");
-  c->counts_ready = false;  // (the slabs are overwritten)
+  Sequence seq(c->v, Sequence::kRollout);  // (the slabs are overwritten)
   for (int k = 0; k < n; ++k) out[k] = 0;
   hipStream_t st = S(stream);
   HIP_TRY(hipStreamSynchronize(st));
@@ -559,7 +529,7 @@ int mdr_graph_memset_probe(mdr_ctx* c, int64_t* out, int n, void* stream) {
   hipGraphExecDestroy(ex);
   if (rc) return rc;
   if ((rc = zero_slabs(c, st))) return rc;
-  return nonzero(&out[12]);
+  return seq.end(nonzero(&out[12]));
 }
 
 int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
@@ -671,7 +641,7 @@ static void drop_rollout_graphs(mdr_ctx* c) {
 }
 
 static void drop_actor_graphs(mdr_ctx* c) {
-  for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second);
+  for (auto& g : c->actor_graphs) hipGraphExecDestroy(g.second.first);
   c->actor_graphs.clear();
 }
 
@@ -701,7 +671,7 @@ int mdr_destroy(mdr_ctx* c) {
 }
 
 int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
-  drop_begun(c);
+  enter_writer(c);  // (writes no state; kept as it was: DESIGN §7.2, the sites kept for compatibility)
   if (!c) return fail(MDR_EARG, "mdr_set_option: null ctx");
   switch (option) {
     case MDR_OPT_STEP_TPW:
@@ -716,8 +686,8 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
     case MDR_OPT_HALO_OVERLAP: c->halo_overlap = value != 0; break;
     case MDR_OPT_HALO_IN_COUNTS: c->halo_in_counts = value != 0; break;
     case MDR_OPT_GQ_BAND: c->gq_band = value != 0; break;
-    case MDR_OPT_GQ_FUSED:  // (the other form's key map was last fitted to an older state: re-fit it)
-      c->gq_map_stale = c->gq_map_stale || c->gq_fused != (value != 0);
+    case MDR_OPT_GQ_FUSED:
+      if (c->gq_fused != (value != 0)) c->v.map_form_switched();
       c->gq_fused = value != 0;
       break;
     case MDR_OPT_GQ_ADAPTIVE: c->gq_adaptive = value != 0; break;
@@ -745,7 +715,7 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
 }
 
 int mdr_bind(mdr_ctx* c, const mdr_soa* s) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c || !s) return fail(MDR_EARG, "mdr_bind: null argument");
   if (!s->t_air || !s->t_mass || !s->hvac || !s->ua || !s->ca || !s->cm || !s->hm || !s->target ||
       !s->cap_idx)
@@ -761,16 +731,13 @@ int mdr_bind(mdr_ctx* c, const mdr_soa* s) {
   k.target = s->target;
   k.cap_idx = s->cap_idx;
   c->bound = true;
-  c->counts_ready = false;
-  c->coef_dirty = true;
-  c->gq_map_stale = true;
-  c->gq_s1 = c->gq_s2 = NAN;
+  c->v.state_replaced();
   drop_rollout_graphs(c);
   return MDR_OK;
 }
 
 int mdr_populate(mdr_ctx* c, const mdr_pop_spec* sp, void* stream) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c || !sp) return fail(MDR_EARG, "mdr_populate: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_populate: context not bound");
   if (sp->n_draw < 0 || sp->n_draw > MDR_MAX_CAP) return fail(MDR_EARG, "mdr_populate: n_draw out of range");
@@ -781,37 +748,35 @@ int mdr_populate(mdr_ctx* c, const mdr_pop_spec* sp, void* stream) {
   memcpy(a.draw_idx, sp->draw_idx, sizeof(a.draw_idx));
   hipLaunchKernelGGL(k_populate, dim3(blocks(c->kp.n, 256)), dim3(256), 0, S(stream), c->kp, a);
   LAUNCH_CHECK("k_populate");
-  c->counts_ready = false;
-  c->coef_dirty = true;
-  c->gq_map_stale = true;
-  c->gq_s1 = c->gq_s2 = NAN;
+  c->v.state_replaced();
   return MDR_OK;
 }
 
 int mdr_power_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, void* stream) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c) return fail(MDR_EARG, "mdr_power_counts: null ctx");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_power_counts: context not bound");
   if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
     return fail(MDR_EARG, "mdr_power_counts: bad action source");
+  Sequence seq(c->v);
   // (re)compute this tick's counts from zero (a previous lookahead may have filled the slab)
-  HIP_TRY(hipMemsetAsync(slab_at(c, c->ring), 0, c->slab_len * sizeof(unsigned long long), S(stream)));
+  HIP_TRY(hipMemsetAsync(slab_at(c, c->v.ring()), 0, c->slab_len * sizeof(unsigned long long), S(stream)));
   int rc = launch_counts(c, action, mode, tick, nullptr, S(stream));
   if (rc) return rc;
-  c->counts_ready = true;
-  return MDR_OK;
+  c->v.counts_produced();
+  return seq.ok();
 }
 
 int mdr_counts_buffer(mdr_ctx* c, int64_t** ptr, int* len) {
   if (!c || !ptr || !len) return fail(MDR_EARG, "mdr_counts_buffer: null argument");
-  *ptr = reinterpret_cast<int64_t*>(slab_at(c, c->ring));
+  *ptr = reinterpret_cast<int64_t*>(slab_at(c, c->v.ring()));
   *len = c->slab_len;
   return MDR_OK;
 }
 
 int mdr_step(mdr_ctx* c, const uint8_t* action, int mode, const mdr_tick* tick, double* reward,
              int lookahead, int ctrl, uint8_t* ctrl_out, double* p_out, void* stream) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c || !tick || !reward) return fail(MDR_EARG, "mdr_step: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_step: context not bound");
   if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
@@ -819,9 +784,10 @@ int mdr_step(mdr_ctx* c, const uint8_t* action, int mode, const mdr_tick* tick, 
   if (lookahead && (!check_mode(lookahead) || !lookahead_ok(lookahead)))
     return fail(MDR_EARG, "mdr_step: bad lookahead source");
   if (ctrl < MDR_CTRL_NONE || ctrl > MDR_CTRL_GREEDY_KEYS) return fail(MDR_EARG, "mdr_step: bad ctrl");
-  if (!c->counts_ready) return fail(MDR_ESTATE, "mdr_step: no cluster-power counts for this tick (call mdr_power_counts)");
-  return launch_step(c, action, mode, to_tick(tick), nullptr, reward, lookahead, ctrl, ctrl_out, p_out,
-                     S(stream));
+  if (!c->v.counts_ready()) return fail(MDR_ESTATE, "mdr_step: no cluster-power counts for this tick (call mdr_power_counts)");
+  Sequence seq(c->v);
+  return seq.end(launch_step(c, action, mode, to_tick(tick), nullptr, reward, lookahead, ctrl, ctrl_out, p_out,
+                             S(stream)));
 }
 
 int mdr_penalty_partials(mdr_ctx* c, void* stream) {
@@ -842,7 +808,7 @@ int mdr_reward_finalize(mdr_ctx* c, const mdr_tick* tick, double* reward, void* 
   if (!c || !tick || !reward) return fail(MDR_EARG, "mdr_reward_finalize: null argument");
   // the tick's counts are in the slab just before the current one
   hipLaunchKernelGGL(k_reward_finalize, dim3(blocks(c->kp.n, 256)), dim3(256), 0, S(stream), c->kp,
-                     to_tick(tick), slab_at(c, c->ring - 1), c->d_partial2, reward);
+                     to_tick(tick), slab_at(c, c->v.ring() - 1), c->d_partial2, reward);
   LAUNCH_CHECK("k_reward_finalize");
   return MDR_OK;
 }
@@ -963,9 +929,9 @@ static bool closed_ok(const mdr_ctx* c, int mode, bool stats = false) {
 // the window slots' shard part is zero between rollouts (k_win_reduce zeroes what it reads);
 // after allocation or a failed launch sequence it is cleared once, outside any graph
 static int wslab_clean(mdr_ctx* c, hipStream_t st) {
-  if (!c->wslab_dirty || !c->d_wslab) return MDR_OK;
+  if (!c->v.slots_dirty() || !c->d_wslab) return MDR_OK;
   HIP_TRY(hipMemsetAsync(c->d_wslab, 0, 3 * sizeof(unsigned long long) * c->wslab_len, st));
-  c->wslab_dirty = false;
+  c->v.slots_cleaned();
   return MDR_OK;
 }
 
@@ -1127,8 +1093,7 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
 }
 
 // ---- the open-loop window sequencers (window_launches, window_launches_direct,
-// window_pipeline).  Window w of the WinPlan counts into slot w % 3 of d_wslab; each sequencer sets
-// wslab_dirty before its first launch and clears it only once the last one is issued.
+// window_pipeline).  Window w of the WinPlan counts into slot w % 3 of d_wslab, under a SlotsGuard.
 struct WinSeq {  // the per-window pieces the three share
   mdr_ctx* c;
   const RolloutArgs& a;
@@ -1181,13 +1146,12 @@ static int win_common_unsharded(const mdr_ctx* c, bool shd) {
 static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream_t st) {
   if (int rc = win_common_unsharded(c, shd)) return rc;
   const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   if (int rc = launch_count(c, a.mode, a.action, a.act_stride, c->d_ticks, 0, s.plan.size(0), s.slot(0), c->d_onb,
                             c->d_wah, nullptr, st, false))
     return rc;
   if (int rc = s.staged_windows(0, shd)) return rc;
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 enum FirstCounts {  // where the first window's per-tick counts of a direct sequence come from
@@ -1205,7 +1169,7 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
   if (int rc = win_common_unsharded(c, first == kBegunAllreduced)) return rc;
   const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
   const int K = s.plan.size(0), nw = s.plan.count();
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   if (first == kCountNow)
     if (int rc = launch_count(c, a.mode, a.action, a.act_stride, nullptr, host_ticks[0].tick, K, s.slot(0), c->d_onb,
                               c->d_wah, nullptr, st, true))
@@ -1226,8 +1190,7 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
   if (a.n > K)
     if (int rc = stage_recs(host_ticks + K, a.n - K, c->d_ticks + K, st)) return rc;
   if (int rc = s.staged_windows(1, false)) return rc;
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 // The count-ahead pipeline (sharded, comm stream present, drivers staged).  An open-loop source's FSM
@@ -1241,7 +1204,7 @@ static int window_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
   hipStream_t cs = c->comm_stream;
   uint64_t* onbs[2] = {c->d_onb, c->d_onb2};
   uint32_t* wahs[2] = {c->d_wah, c->d_wah2};
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state and staged ticks, before the first count
   HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
   for (int w = 0; w < nw; ++w) {
@@ -1261,8 +1224,7 @@ static int window_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
     if (int rc = s.step(w, 0, onbs[w % 2], wahs[w % 2], s.slot(w))) return rc;
     HIP_TRY(hipEventRecord(c->ev_k1[w % kSlabs], st));
   }
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 // the second ON-mask / end-word set of the count-ahead pipeline (allocated on first use)
@@ -1304,7 +1266,7 @@ static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, dou
   unsigned long long* slot = c->d_wslab;
   const double* rec = reinterpret_cast<const double*>(win_red_ptr(c, slot) + (size_t)kWindowMax * ncap);
   const unsigned grid = win_grid(c);
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   for (int w = 0; w < nw; ++w) {
     const int K = plan.size(w), t0 = plan.start(w);
     double* r = a.rew_row(t0);
@@ -1357,8 +1319,7 @@ static int closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, dou
       LAUNCH_CHECK("k_closed_stats");
     }
   }
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 // ---- the sharded closed-loop window sequencers: a bang-bang source under
@@ -1409,15 +1370,14 @@ struct ClosedShardSeq {
 // one stream: step -> sum -> allreduce -> finish per window
 static int closed_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
   const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   for (int w = 0; w < s.plan.count(); ++w) {
     if (int rc = s.step(w, st)) return rc;
     if (int rc = s.sum(w, st)) return rc;
     if (s.finished(w))
       if (int rc = s.reduce_finish(w, st)) return rc;
   }
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 // two streams, a reward row per tick (rew_stride != 0: every window is finished): the compute stream
@@ -1435,7 +1395,7 @@ static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t
   const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
   const int nw = s.plan.count();
   hipStream_t cs = c->comm_stream;
-  c->wslab_dirty = true;  // until the sequence is fully issued
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   auto compute = [&](int w) -> int {
     if (int rc = s.step(w, st)) return rc;
     if (w >= 3) HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(w - 3) % kSlabs], 0));
@@ -1452,8 +1412,7 @@ static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t
     HIP_TRY(hipEventRecord(c->ev_ar[w % kSlabs], cs));
   }
   HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(nw - 1) % kSlabs], 0));
-  c->wslab_dirty = false;
-  return MDR_OK;
+  return slots.done();
 }
 
 // (per-tick stats rows, defined with mdr_tick_stats below)
@@ -1476,7 +1435,7 @@ static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, do
   if (closed_ok(c, mode, stats != nullptr)) return closed_launches(c, a, st, stats);
   double* const p_tick = a.p_out ? a.p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
   if (int rc = zero_slabs(c, st)) return rc;
-  c->ring = 0;
+  c->v.slabs_zeroed();
   const bool la = lookahead_ok(mode);
   for (int t = 0; t < n; ++t) {
     const uint8_t* act = a.act_row(t);
@@ -1493,7 +1452,7 @@ static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, do
       hipLaunchKernelGGL(k_pen_reduce, dim3(1), dim3(256), 0, st, c->d_pen_partial, c->pen_blocks, c->d_partial2);
       LAUNCH_CHECK("k_pen_reduce");
       hipLaunchKernelGGL(k_reward_finalize_dev, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp,
-                         (const TickArgs*)(c->d_ticks + t), (const unsigned long long*)slab_at(c, c->ring - 1),
+                         (const TickArgs*)(c->d_ticks + t), (const unsigned long long*)slab_at(c, c->v.ring() - 1),
                          (const double*)c->d_partial2, r);
       LAUNCH_CHECK("k_reward_finalize");
     }
@@ -1549,9 +1508,8 @@ enum {
 };
 static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const RolloutArgs& a, int flags) {
   if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
-  if (flags & kDropBegun) drop_begun(c);
-  c->gq_keys_ready = false;
-  c->fz_ready = false;
+  if (flags & kDropBegun) c->v.drop_early_count();
+  c->v.state_may_change();
   if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
   if ((flags & kShardedOnly) && !has_comm(c))
     return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
@@ -1565,7 +1523,7 @@ static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const Rollou
 // ids tick0 + j and its P-only reduce consumed the slot's shards: only the direct sequence can follow
 // it, whatever use_graph asks.)  sharded: a single window, its counts allreduced already.
 static bool begun_matches(const mdr_ctx* c, const RolloutArgs& a, const mdr_tick* ticks, bool sharded) {
-  const auto& b = c->begun;
+  const EarlyCount& b = c->v.early();
   return b.on && b.sharded == sharded && b.n == a.n && b.mode == a.mode && b.tick0 == ticks[0].tick &&
          b.action == a.action && b.act_stride == a.act_stride && (!sharded || (has_comm(c) && a.n <= c->win)) &&
          window_ok(c, a.mode) && consecutive(ticks, a.n);
@@ -1587,45 +1545,34 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
   hipStream_t st = S(stream);
   double* const srow = stats ? stats + (size_t)row0 * kTickRow : nullptr;
   const bool counted = begun_matches(c, a, ticks, false);
-  if (c->begun.on && !counted) c->wslab_dirty = true;  // an unmatched early count: clear its shards
-  c->begun.on = false;
+  if (counted) c->v.early_consumed();
+  else c->v.drop_early_count();  // an unmatched early count: its shards are cleared below
+  Sequence seq(c->v, Sequence::kRollout);
   int rc = refresh_if_dirty(c, st);
   if (rc) return rc;
   if (counted || (!use_graph && window_ok(c, a.mode) && consecutive(ticks, a.n))) {
     rc = ensure_ticks(c, a.n);
     if (!rc) rc = wslab_clean(c, st);
     if (!rc) rc = window_launches_direct(c, a, ticks, counted ? kBegun : kCountNow, st);
-    c->counts_ready = false;
-    return rc;
+    return seq.end(rc);
   }
   rc = stage_ticks(c, a.n, ticks, st);
   if (!rc) rc = wslab_clean(c, st);
   if (!rc && stats) rc = rollout_stats_scratch(c, a.mode, !a.p_out);
   if (rc) return rc;
-  if (!use_graph) {
-    rc = rollout_launches(c, a, st, srow);
-    c->counts_ready = false;
-    return rc;
-  }
+  if (!use_graph) return seq.end(rollout_launches(c, a, st, srow));
   const GraphKey key{a, stats, stats ? row0 : 0};
   auto it = c->graphs.find(key);
   if (it == c->graphs.end()) {
     hipGraphExec_t ex;
     rc = capture_graph(c, [&](hipStream_t cs) { return rollout_launches(c, a, cs, srow); }, &ex);
-    if (rc) {
-      c->wslab_dirty = true;
-      return rc;
-    }
-    it = c->graphs.emplace(key, std::make_pair(ex, c->ring)).first;
+    if (rc) return rc;
+    it = c->graphs.emplace(key, std::make_pair(ex, c->v.ring())).first;
   }
-  if (hipGraphLaunch(it->second.first, st) != hipSuccess) {
-    c->wslab_dirty = true;
-    return fail(MDR_EHIP, std::string(who) + ": hipGraphLaunch");
-  }
+  if (hipGraphLaunch(it->second.first, st) != hipSuccess) return fail(MDR_EHIP, std::string(who) + ": hipGraphLaunch");
   ++c->graph_launches[0];
-  c->ring = it->second.second;
-  c->counts_ready = false;
-  return MDR_OK;
+  c->v.graph_replayed(it->second.second);
+  return seq.ok();
 }
 
 int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
@@ -1642,8 +1589,7 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
                       void* stream) {
   const RolloutArgs a{n, action, act_stride, mode, nullptr, 0, nullptr};
   if (int rc = rollout_preamble(c, "mdr_rollout_begin", true, a, 0)) return rc;
-  if (c->begun.on) c->wslab_dirty = true;  // a previous early count that no rollout consumed
-  c->begun.on = false;
+  c->v.drop_early_count();  // a previous one that no rollout consumed
   if (!window_ok(c, mode)) return MDR_OK;
   // a sharded context (RCCL attached): single-window rollouts only, counts allreduced here, so
   // the matching mdr_rollout_sharded launches just the KA step kernel
@@ -1651,11 +1597,12 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
   if (sharded && n > c->win) return MDR_OK;
   if (common_sharded(c)) return MDR_OK;  // (mdr_rollout / _sharded refuse these)
   hipStream_t st = S(stream);
+  Sequence seq(c->v);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = wslab_clean(c, st);
   if (rc) return rc;
   const int k0 = WinPlan(n, c->win).size(0);
-  c->wslab_dirty = true;
+  SlotsGuard slots(c->v);
   // the window's P (the counts need no drivers): the matching direct mdr_rollout then launches the
   // step kernel with the drivers as arguments (k_step_window<..., KA>), nothing in between — on one
   // GPU the count kernel's last block reduces; sharded, the reduce follows the counts' allreduce
@@ -1666,9 +1613,9 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
     // (the KA step derives each tick's P from these totals itself: no k_win_records launch, r06)
     if (int rc2 = comm_allreduce(c, win_red_ptr(c, c->d_wslab), (size_t)k0 * c->kp.n_cap, 0, st)) return rc2;
   }
-  c->wslab_dirty = false;
-  c->begun = {true, n, mode, tick0, action, act_stride, sharded};
-  return MDR_OK;
+  slots.done();
+  c->v.early_counted(EarlyCount{true, n, mode, tick0, action, act_stride, sharded});
+  return seq.ok();
 }
 
 // Measurement: one rollout as direct launches (no graph, drivers staged first) with an event pair
@@ -1677,12 +1624,13 @@ int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, 
 // event.
 int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
                           int mode, double* reward, int64_t rew_stride, void* stream, float* ms, int* launches) {
-  drop_begun(c);  // (a refused call discards an early count too)
+  enter_writer(c);  // (a refused call discards an early count too)
   const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, nullptr};
   if (int rc = rollout_preamble(c, "mdr_time_step_kernels", ticks && reward && ms && launches, a, 0)) return rc;
   if (common_sharded(c))  // (mdr_rollout's refusal)
     return fail(MDR_EARG, "mdr_time_step_kernels: common penalty modes on a sharded context need the per-step API");
   hipStream_t st = S(stream);
+  Sequence seq(c->v, Sequence::kRollout);
   int rc = refresh_if_dirty(c, st);
   if (!rc) rc = stage_ticks(c, n, ticks, st);
   if (!rc) rc = wslab_clean(c, st);
@@ -1691,7 +1639,6 @@ int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_
   c->step_events = &evs;
   rc = rollout_launches(c, a, st);
   c->step_events = nullptr;
-  c->counts_ready = false;
   float total = 0.0f;
   if (!rc && !evs.empty() && hipEventSynchronize(evs.back()) != hipSuccess) rc = fail(MDR_EHIP, "event sync");
   for (size_t i = 0; !rc && i + 1 < evs.size(); i += 2) {
@@ -1703,7 +1650,7 @@ int mdr_time_step_kernels(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_
   if (rc) return rc;
   *ms = total;
   *launches = (int)(evs.size() / 2);
-  return MDR_OK;
+  return seq.ok();
 }
 
 // ------------------------------------------------------------------------------------ obs
@@ -1816,9 +1763,7 @@ void greedy_clear(mdr_ctx* c) {
 
 int greedy_scratch(mdr_ctx* c, int64_t n) {
   if (c->g_cap >= n) return MDR_OK;
-  c->gq_keys_ready = false;
-  c->fz_ready = false;
-  c->gq_hist_dirty = false;
+  c->v.scratch_regrown();
   const int rc = grow_unit([&] { greedy_clear(c); }, [&]() -> int {
     if (int rc = dev_reserve(c->g_key, n, "g_key")) return rc;
     if (int rc = dev_reserve(c->g_key2, n, "g_key2")) return rc;
@@ -1860,12 +1805,11 @@ int greedy_scratch(mdr_ctx* c, int64_t n) {
 // left unconsumed (two GQ steps with no greedy call between, or keys dropped by a state change)
 // are zeroed first, so the select never sees the sum of two states
 int gq_hist_produce(mdr_ctx* c, hipStream_t st) {
-  if (c->gq_hist_dirty) {
+  if (c->v.hist_add()) {
     hipLaunchKernelGGL(k_zero_u64, dim3(64), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(c->g_hist.get()),
                        (int64_t)(kGqHistWords / 2));
     LAUNCH_CHECK("k_zero_u64 (g_hist)");
   }
-  c->gq_hist_dirty = true;
   return MDR_OK;
 }
 
@@ -1877,7 +1821,7 @@ int launch_gq_keys(mdr_ctx* c, hipStream_t st, unsigned long long* slab, bool lo
                      c->g_sel, c->g_map, slab);
   LAUNCH_CHECK("k_gq_keys");
   // (sharded, local_map = false: every rank's map must stay the one built from the allreduced range)
-  if (c->gq_map_stale && local_map) {  // (a written state: cells over its key range, then the codes again)
+  if (c->v.map_stale() && local_map) {  // (a written state: cells over its key range, then the codes again)
     unsigned char* sel = reinterpret_cast<unsigned char*>(c->g_sel);
     hipLaunchKernelGGL(k_gq_remap, dim3(1), dim3(256), 0, st, c->kp, (const double*)c->g_part, (int)kGqParts,
                        c->g_hist + kGqBins * 4, c->g_sel, c->g_map,
@@ -1886,10 +1830,9 @@ int launch_gq_keys(mdr_ctx* c, hipStream_t st, unsigned long long* slab, bool lo
     hipLaunchKernelGGL(k_gq_keys, dim3(kGqParts), dim3(kGqThreads), 0, st, c->kp, gq_codes(c), c->g_part, c->g_hist,
                        c->g_sel, c->g_map, slab);
     LAUNCH_CHECK("k_gq_keys (remapped)");
-    c->gq_map_stale = false;
+    c->v.maps_fitted();
   }
-  c->gq_nparts = kGqParts;
-  c->gq_slab_zeroed = slab != nullptr;
+  c->v.keys_from_kernel(kGqParts, slab != nullptr);
   return MDR_OK;
 }
 
@@ -1900,23 +1843,22 @@ extern "C" {
 int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
   if (!c || !action) return fail(MDR_EARG, "mdr_ctrl_greedy: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_ctrl_greedy: context not bound");
-  const bool keys_ready = c->gq_keys_ready && c->g_cap >= c->kp.n;  // (the last step's epilogue wrote them)
-  drop_begun(c);
-  c->gq_keys_ready = false;  // (the histogram is consumed below)
-  c->fz_ready = false;
+  const bool keys_ready = c->v.take_keys() && c->g_cap >= c->kp.n;  // (the last step's epilogue wrote them)
+  enter_writer(c);
+  Sequence seq(c->v);
   int rc = greedy_scratch(c, c->kp.n);
   if (rc) return rc;
   hipStream_t st = S(stream);
   const int n = (int)c->kp.n;
   double pmin = INFINITY;
   for (int k = 0; k < c->cfg.n_cap; ++k) pmin = fmin(pmin, c->cfg.cap_table[k] / c->cfg.cop);
-  unsigned long long* slab = slab_at(c, c->ring);  // the counts of the actions decided here
+  unsigned long long* slab = slab_at(c, c->v.ring());  // the counts of the actions decided here
   if (c->kp.n_cap <= 4 && !c->greedy_sort) {
     // histogram select (mdr_kernels.hip k_gq_*): no sort of the whole cluster, no host
     // synchronisation; k_gq_select decides exactly what the candidate window cannot
     if (!keys_ready) {
       if (int rc2 = launch_gq_keys(c, st, slab)) return rc2;
-    } else if (!c->gq_slab_zeroed) {
+    } else if (!c->v.slab_zeroed()) {
       // the producing step counted a lookahead into this slab: the decisions replace those counts
       hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, st, slab, (int64_t)c->slab_len);
       LAUNCH_CHECK("k_zero_u64 (decision slab)");
@@ -1931,11 +1873,11 @@ int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
       LAUNCH_CHECK("k_gq_binsc");
       hipLaunchKernelGGL(k_gq_finish, dim3(kGqSelBlocks), dim3(1024), 0, st, c->kp, (const uint32_t*)gq_codes(c),
                          c->g_win, c->g_sorted, budget, pmin, c->g_sel, action, slab, c->g_hist, c->g_tickets,
-                         (const double*)c->g_part, c->gq_nparts, c->g_map);
+                         (const double*)c->g_part, c->v.nparts(), c->g_map);
       LAUNCH_CHECK("k_gq_finish");
-      c->gq_hist_dirty = false;
-      c->counts_ready = true;
-      return MDR_OK;
+      c->v.hist_consumed();
+      c->v.counts_produced();
+      return seq.ok();
     } else {
       hipLaunchKernelGGL(k_gq_bins, dim3(kGqParts), dim3(kGqThreads), 0, st, c->kp, gq_codes(c), c->g_hist, budget,
                          c->g_sel, slab);
@@ -1948,11 +1890,11 @@ int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
     // DESIGN.md §3.3)
     hipLaunchKernelGGL(k_gq_select, dim3(kGqSelBlocks), dim3(1024), 0, st, c->kp, (const uint4*)c->g_win,
                        c->g_sorted, budget, pmin, c->g_sel, action, slab, c->g_hist, (const uint4*)nullptr, 0,
-                       c->g_tickets, (const double*)c->g_part, c->gq_nparts, c->g_map);
+                       c->g_tickets, (const double*)c->g_part, c->v.nparts(), c->g_map);
     LAUNCH_CHECK("k_gq_select");
-    c->gq_hist_dirty = false;
-    c->counts_ready = true;
-    return MDR_OK;
+    c->v.hist_consumed();
+    c->v.counts_produced();
+    return seq.ok();
   }
   hipLaunchKernelGGL(k_greedy_keys, dim3(blocks(n, 256)), dim3(256), 0, st, c->kp, c->g_key, c->g_idx);
   LAUNCH_CHECK("k_greedy_keys");
@@ -1972,8 +1914,8 @@ int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
   // the counts of these actions, as the histogram form leaves them
   HIP_TRY(hipMemsetAsync(slab, 0, c->slab_len * sizeof(unsigned long long), st));
   if (int rc2 = launch_counts(c, action, MDR_ACT_BUFFER, 0, nullptr, st)) return rc2;
-  c->counts_ready = true;
-  return MDR_OK;
+  c->v.counts_produced();
+  return seq.ok();
 }
 
 int mdr_greedy_diag(mdr_ctx* c, uint64_t* out) {
@@ -2016,7 +1958,7 @@ void gqf_clear(mdr_ctx* c) {
 int gqf_scratch(mdr_ctx* c, int64_t n) {
   if (c->fz_cap_n >= n) return MDR_OK;
   HIP_TRY(hipDeviceSynchronize());
-  c->fz_ready = false;
+  c->v.fused_scratch_regrown();
   // bucket capacity: 4x the houses a (copy, bin) holds on average under an equi-depth map, >= 32
   const int64_t avg = (n + (int64_t)gq_bins_eff(c->kp.n_global) * kGqCopies - 1) / ((int64_t)gq_bins_eff(c->kp.n_global) * kGqCopies);
   const int cap = (int)std::max<int64_t>(32, 4 * avg);
@@ -2041,7 +1983,6 @@ int gqf_scratch(mdr_ctx* c, int64_t n) {
                   {c->fz_maps, c->fz_maps + kGqCells}, reinterpret_cast<GqSel*>(c->fz_sel.get()), c->fz_dec,
                   cap, cap, c->fz_stamps};
   c->fz_cap_n = n;
-  c->fz_par = 0;
   return MDR_OK;
 }
 
@@ -2053,7 +1994,7 @@ int launch_step_fused(mdr_ctx* c, const TickArgs& tk, double* reward, uint8_t* a
   const unsigned nb = blocks(blocks(kp.n, 128), kStepGqWaves * tpw);
   if ((int)nb > c->gq_parts_cap) return fail(MDR_ESTATE, "fused greedy: the step grid exceeds the partials buffer");
   GqOut go{act_out, nullptr, c->g_part, nullptr, nullptr, nullptr};
-  unsigned long long *cur = slab_at(c, c->ring), *nxt = slab_at(c, c->ring + 1), *zer = slab_at(c, c->ring + 2);
+  unsigned long long *cur = slab_at(c, c->v.ring()), *nxt = slab_at(c, c->v.ring() + 1), *zer = slab_at(c, c->v.ring() + 2);
   if (tpw >= 4)
     hipLaunchKernelGGL((k_step_pipe<4, MDR_ACT_BUFFER, 0, 2>), dim3(nb), dim3(64 * kStepGqWaves), 0, st, kp,
                        (const uint8_t*)c->fz.dec, tk, (const TickArgs*)nullptr, cur, reward, p_out, nxt, zer, go, c->fz, par);
@@ -2061,8 +2002,7 @@ int launch_step_fused(mdr_ctx* c, const TickArgs& tk, double* reward, uint8_t* a
     hipLaunchKernelGGL((k_step_pipe<2, MDR_ACT_BUFFER, 0, 2>), dim3(nb), dim3(64 * kStepGqWaves), 0, st, kp,
                        (const uint8_t*)c->fz.dec, tk, (const TickArgs*)nullptr, cur, reward, p_out, nxt, zer, go, c->fz, par);
   LAUNCH_CHECK("k_step_pipe (fused greedy)");
-  c->gq_nparts = (int)nb;
-  c->ring = (c->ring + 1) % 3;
+  c->v.fused_step_issued((int)nb);
   return MDR_OK;
 }
 }  // namespace
@@ -2122,22 +2062,23 @@ static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t*
   const bool fused = c->gq_fused && !c->greedy_sort && c->kp.n_cap <= 4 && c->tpw >= 1 && c->fastdiv &&
                      c->kp.penalty_mode == MDR_PEN_INDIVIDUAL_L2 && n > 0;
   if (fused) {
-    const bool ready = c->fz_ready && c->fz_cap_n >= c->kp.n;  // (the last step produced this state's counts)
-    drop_begun(c);
+    const bool ready = c->v.take_fused() && c->fz_cap_n >= c->kp.n;  // (the last step produced this state's counts)
+    enter_writer(c);
+    Sequence seq(c->v, Sequence::kRollout);
     if (int rc = refresh_if_dirty(c, st)) return rc;
     if (int rc = greedy_scratch(c, c->kp.n)) return rc;  // (the partials, tickets and sorted window)
     if (int rc = gqf_scratch(c, c->kp.n)) return rc;
     double pmin = INFINITY;
     for (int k = 0; k < c->cfg.n_cap; ++k) pmin = fmin(pmin, c->cfg.cap_table[k] / c->cfg.cop);
-    int par = c->fz_par;
+    int par = c->v.fused_parity();
     if (!ready) {  // the current state's keys: the producer without a step, into parity par
       hipLaunchKernelGGL(k_zero_u64, dim3(64), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(c->fz.par[par]),
                          (int64_t)(kGqfParWords / 2));
       LAUNCH_CHECK("k_zero_u64 (fused producer region)");
       const unsigned g = blocks(c->kp.n, kGqStage);
-      hipLaunchKernelGGL(k_gq_keys2, dim3(g), dim3(kGqThreads), 0, st, c->kp, c->fz, par, c->g_part, slab_at(c, c->ring));
+      hipLaunchKernelGGL(k_gq_keys2, dim3(g), dim3(kGqThreads), 0, st, c->kp, c->fz, par, c->g_part, slab_at(c, c->v.ring()));
       LAUNCH_CHECK("k_gq_keys2");
-      if (c->gq_map_stale) {  // (a written state: parity par's cells over its key range, then the producer again)
+      if (c->v.map_stale()) {  // (a written state: parity par's cells over its key range, then the producer again)
         unsigned char* fs = reinterpret_cast<unsigned char*>(c->fz.sel);
         hipLaunchKernelGGL(k_gq_remap, dim3(1), dim3(256), 0, st, c->kp, (const double*)c->g_part, (int)g, c->fz.par[par],
                            c->fz.sel, c->fz.map[par], reinterpret_cast<double*>(fs + gq_kmin_offset(par)),
@@ -2146,15 +2087,15 @@ static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t*
         hipLaunchKernelGGL(k_zero_u64, dim3(64), dim3(256), 0, st, reinterpret_cast<unsigned long long*>(c->fz.par[par]),
                            (int64_t)(kGqfParWords / 2));
         LAUNCH_CHECK("k_zero_u64 (fused producer region, remapped)");
-        hipLaunchKernelGGL(k_gq_keys2, dim3(g), dim3(kGqThreads), 0, st, c->kp, c->fz, par, c->g_part, slab_at(c, c->ring));
+        hipLaunchKernelGGL(k_gq_keys2, dim3(g), dim3(kGqThreads), 0, st, c->kp, c->fz, par, c->g_part, slab_at(c, c->v.ring()));
         LAUNCH_CHECK("k_gq_keys2 (remapped)");
-        c->gq_map_stale = false;
+        c->v.maps_fitted();
       }
-      c->gq_nparts = (int)g;
+      c->v.fused_keys_from_kernel((int)g);
     }
     for (int t = 0; t < n; ++t) {
       hipLaunchKernelGGL(k_gq_decide2, dim3(kGqSelBlocks), dim3(1024), 0, st, c->kp, c->fz, par, ticks[t].s_prev, pmin,
-                         slab_at(c, c->ring), c->g_tickets, (const double*)c->g_part, c->gq_nparts);
+                         slab_at(c, c->v.ring()), c->g_tickets, (const double*)c->g_part, c->v.nparts());
       LAUNCH_CHECK("k_gq_decide2");
       double* r = reward + (int64_t)t * rew_stride;
       if (int rc = launch_step_fused(c, to_tick(&ticks[t]), r, action ? action + (int64_t)t * act_stride : nullptr,
@@ -2164,10 +2105,8 @@ static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t*
       if (stats)
         if (int rc = greedy_rows_tick(c, t, n, r, stats, p_out, st)) return rc;
     }
-    c->fz_par = par;
-    c->fz_ready = true;
-    c->counts_ready = false;
-    return MDR_OK;
+    c->v.fused_produced(par);
+    return seq.ok();
   }
   // the adaptive band (MDR_OPT_GQ_ADAPTIVE): the band is predicted from the crossing's
   // trend, so a budget whose change departs from the last change by more than four superbins' worth of
@@ -2177,17 +2116,16 @@ static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t*
   for (int k = 0; k < c->cfg.n_cap; ++k) pavg += c->cfg.cap_table[k] / c->cfg.cop;
   pavg /= c->cfg.n_cap > 0 ? c->cfg.n_cap : 1;
   const double jump = 4.0 * ((double)c->kp.n_global * 64.0 / (double)gq_bins_eff(c->kp.n_global)) * pavg;
+  Sequence seq(c->v);  // (not a kRollout: every tick's step says what it leaves, and n may be 0)
   for (int t = 0; t < n; ++t) {
     uint8_t* a = action + (int64_t)t * act_stride;
     double* r = reward + (int64_t)t * rew_stride;
     const double sb = ticks[t].s_prev;
-    c->gq_band_skip = c->gq_adaptive && c->gq_s1 == c->gq_s1 && c->gq_s2 == c->gq_s2 &&
-                      !(fabs((sb - c->gq_s1) - (c->gq_s1 - c->gq_s2)) <= jump);
+    c->gq_band_skip = c->gq_adaptive && c->v.budget_jumps(sb, jump);
     const int rc0 = mdr_ctrl_greedy(c, sb, a, stream);
     c->gq_band_skip = false;
     if (rc0) return rc0;
-    c->gq_s2 = c->gq_s1;
-    c->gq_s1 = sb;
+    c->v.budget_decided(sb);
     if (int rc = launch_step(c, a, MDR_ACT_BUFFER, to_tick(&ticks[t]), nullptr, r, 0, MDR_CTRL_GREEDY_KEYS, nullptr,
                              stats ? c->d_rows_p + t % kTickRowsBatch : p_out, st))
       return rc;
@@ -2198,7 +2136,7 @@ static int greedy_rollout_seq(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t*
     if (stats)  // the post-step state with this tick's final rewards
       if (int rc = greedy_rows_tick(c, t, n, r, stats, p_out, st)) return rc;
   }
-  return MDR_OK;
+  return seq.ok();
 }
 
 int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action, int64_t act_stride,
@@ -2257,17 +2195,16 @@ int mdr_gq_shard_begin(mdr_ctx* c, void* stream) {
   if (!c) return fail(MDR_EARG, "mdr_gq_shard_begin: null context");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_gq_shard_begin: context not bound");
   if (c->kp.n_cap > 4) return fail(MDR_EARG, "mdr_gq_shard_begin: more than 4 capacity classes (use the all-gather form)");
-  const bool keys_ready = c->gq_keys_ready && c->g_cap >= c->kp.n;
-  drop_begun(c);
-  c->gq_keys_ready = false;
-  c->fz_ready = false;
+  const bool keys_ready = c->v.take_keys() && c->g_cap >= c->kp.n;
+  enter_writer(c);
+  Sequence seq(c->v);
   if (int rc = greedy_scratch(c, c->kp.n)) return rc;
   hipStream_t st = S(stream);
   if (!keys_ready)
     if (int rc = launch_gq_keys(c, st, nullptr, false)) return rc;
-  hipLaunchKernelGGL(k_gq_range, dim3(1), dim3(256), 0, st, c->g_part, c->gq_nparts, c->g_range);
+  hipLaunchKernelGGL(k_gq_range, dim3(1), dim3(256), 0, st, c->g_part, c->v.nparts(), c->g_range);
   LAUNCH_CHECK("k_gq_range");
-  return MDR_OK;
+  return seq.ok();
 }
 
 int mdr_gq_shard_buffers(mdr_ctx* c, void** super_hist, int64_t* n_super, void** bin_hist, int64_t* n_bin,
@@ -2317,7 +2254,7 @@ int mdr_gq_shard_select(mdr_ctx* c, double budget, const void* gathered, int wor
                      static_cast<const uint4*>(gathered), world, c->g_tickets, (const double*)c->g_range, -1,
                      c->g_map);
   LAUNCH_CHECK("k_gq_select (sharded)");
-  c->gq_hist_dirty = false;
+  c->v.hist_consumed();
   return MDR_OK;
 }
 
@@ -2451,6 +2388,7 @@ int rollout_sharded_overlap(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
                             MDR_CTRL_NONE, nullptr, nullptr, t >= 1 ? slab(t - 1) : nullptr, slab(t + 1),
                             slab(t + 2), 1, st);
     if (rc) return rc;
+    c->v.step_issued(true, false, /*keep_ring=*/true);  // (this pipeline's own ring of kSlabs)
     HIP_TRY(hipEventRecord(c->ev_k1[t % kSlabs], st));
   }
   HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(n - 1) % kSlabs], 0));
@@ -2459,8 +2397,7 @@ int rollout_sharded_overlap(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
   LAUNCH_CHECK("k_reward_state");
   // leave the step path's invariant (slab ring+1 zero) behind
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
-  c->ring = 0;
-  c->counts_ready = false;
+  c->v.slabs_zeroed();
   return MDR_OK;
 }
 
@@ -2469,17 +2406,16 @@ int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
   const TickArgs* ticks = c->d_ticks;
   const int n = a.n, mode = a.mode;
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
-  c->ring = 0;
+  c->v.slabs_zeroed();
   const bool la = lookahead_ok(mode);
   for (int t = 0; t < n; ++t) {
     if (!la || t == 0)
       if (int rc = launch_counts(c, a.act_row(t), mode, 0, ticks + t, st)) return rc;
-    if (int rc = comm_allreduce(c, slab_at(c, c->ring), c->slab_len, 0, st)) return rc;
+    if (int rc = comm_allreduce(c, slab_at(c, c->v.ring()), c->slab_len, 0, st)) return rc;
     int rc = launch_step(c, a.act_row(t), mode, TickArgs{}, ticks + t, a.rew_row(t), la ? mode : 0, MDR_CTRL_NONE,
                          nullptr, t == n - 1 ? a.p_out : nullptr, st);
     if (rc) return rc;
   }
-  c->counts_ready = false;
   return MDR_OK;
 }
 
@@ -2494,17 +2430,17 @@ int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
   // a single window begun by mdr_rollout_begin on this sharded context (count, allreduce, P-only
   // reduce already issued): only the KA step kernel is left, with these drivers as its arguments.
   // (Such a call passes every check of the preamble: mdr_rollout_begin made them.)
-  const bool begun = c && ticks && n >= 1 && begun_matches(c, a, ticks, true);
+  const bool counted = c && ticks && n >= 1 && begun_matches(c, a, ticks, true);
   if (int rc = rollout_preamble(c, "mdr_rollout_sharded", ticks && reward, a,
-                                (begun ? 0 : kDropBegun) | kShardedOnly | kNoCommon))
+                                (counted ? 0 : kDropBegun) | kShardedOnly | kNoCommon))
     return rc;
   hipStream_t st = S(stream);
-  if (begun) {
-    c->begun.on = false;
+  Sequence seq(c->v, Sequence::kRollout);
+  if (counted) {
+    c->v.early_consumed();
     int rc = ensure_ticks(c, n);
     if (!rc) rc = window_launches_direct(c, a, ticks, kBegunAllreduced, st);
-    c->counts_ready = false;
-    return rc;
+    return seq.end(rc);
   }
   int rc = refresh_if_dirty(c, st);
   if (rc) return rc;
@@ -2514,21 +2450,17 @@ int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
     rc = wslab_clean(c, st);
     if (rc) return rc;
     const bool pipe = c->win_pipe && c->comm_stream && pipe_buffers(c);
-    rc = pipe ? window_pipeline(c, a, st) : window_launches(c, a, true, st);
-    c->counts_ready = false;
-    return rc;
+    return seq.end(pipe ? window_pipeline(c, a, st) : window_launches(c, a, true, st));
   }
   if (closed_ok(c, mode)) {  // (individual_L2: the preamble refused the common penalty modes)
     rc = wslab_clean(c, st);
     if (rc) return rc;
     const bool pipe = c->win_pipe && c->comm_stream && rew_stride != 0;  // (one shared row: one stream)
-    rc = pipe ? closed_sharded_pipeline(c, a, st) : closed_sharded_serial(c, a, st);
-    c->counts_ready = false;
-    return rc;
+    return seq.end(pipe ? closed_sharded_pipeline(c, a, st) : closed_sharded_serial(c, a, st));
   }
   const bool can_overlap = lookahead_ok(mode) && rew_stride != 0 && c->comm_stream;
-  if (can_overlap && c->tick_overlap) return rollout_sharded_overlap(c, a, st);
-  return rollout_sharded_serial(c, a, st);
+  if (can_overlap && c->tick_overlap) return seq.end(rollout_sharded_overlap(c, a, st));
+  return seq.end(rollout_sharded_serial(c, a, st));
 }
 
 int mdr_rollout_sharded_mode(mdr_ctx* c, int* window_pipeline, int* tick_overlap) {
@@ -2539,7 +2471,7 @@ int mdr_rollout_sharded_mode(mdr_ctx* c, int* window_pipeline, int* tick_overlap
 }
 
 int mdr_set_rollout_window(mdr_ctx* c, int ticks) {
-  drop_begun(c);
+  enter_writer(c);  // (writes no state; kept as it was: DESIGN §7.2, the sites kept for compatibility)
   if (!c || ticks < 0 || ticks > kWindowMax) return fail(MDR_EARG, "mdr_set_rollout_window: ticks outside 0..32");
   if (ticks > 0 && !c->d_wslab) return fail(MDR_EARG, "mdr_set_rollout_window: more than 4 capacity classes");
   if (ticks != c->win) {
@@ -2563,17 +2495,15 @@ int mdr_cluster_stats(mdr_ctx* c, const double* reward, double* out, void* strea
 }
 
 int mdr_params_changed(mdr_ctx* c) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c) return fail(MDR_EARG, "mdr_params_changed: null ctx");
-  c->coef_dirty = true;
-  c->gq_map_stale = true;
-  c->gq_s1 = c->gq_s2 = NAN;
+  c->v.params_replaced();
   return MDR_OK;
 }
 
 // ------------------------------------------------------------------------------------ diagnostics
 int mdr_probe_stream(mdr_ctx* c, double* reward, void* stream) {
-  drop_begun(c);
+  enter_writer(c);  // (writes no state; kept as it was: DESIGN §7.2, the sites kept for compatibility)
   if (!c || !reward) return fail(MDR_EARG, "mdr_probe_stream: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_probe_stream: context not bound");
   hipLaunchKernelGGL(k_probe_stream, dim3(blocks(c->kp.n, 512)), dim3(256), 0, S(stream), c->kp, reward);
@@ -2998,20 +2928,21 @@ int mdr_actor_fused(mdr_ctx* c, const mdr_obs_spec* sp) {
 int mdr_actor_act(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const double* p_dev,
                   uint64_t tick, uint8_t* action, float* prob, float* probs, float* obs_out, int count_next,
                   void* stream) {
-  drop_begun(c);
+  enter_writer(c);
   if (!c || !sp || !sc) return fail(MDR_EARG, "mdr_actor_act: null argument");
   if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_act: context not bound");
   if (int rc = check_actor_obs(c, sp, "mdr_actor_act", S(stream))) return rc;
   hipStream_t st = S(stream);
+  Sequence seq(c->v);
   ActorOut out{action, prob, probs, obs_out, nullptr, nullptr};
   if (count_next) {
     // the counts of the tick these actions drive go into the current slab (from zero)
-    out.count_next = slab_at(c, c->ring);
+    out.count_next = slab_at(c, c->v.ring());
     HIP_TRY(hipMemsetAsync(out.count_next, 0, c->slab_len * sizeof(unsigned long long), st));
   }
   if (int rc = launch_actor(c, sp, obs_args(c, sp, sc), p_dev, tick, nullptr, out, st)) return rc;
-  if (count_next) c->counts_ready = true;
-  return MDR_OK;
+  if (count_next) c->v.counts_produced();
+  return seq.ok();
 }
 
 int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const double* p_dev,
@@ -3280,7 +3211,7 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
                               int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
                               const mdr_snap* snap, int row0, double* stats, int64_t stats_rows, int64_t stats_row0,
                               void* stream, const char* who) {
-  drop_begun(c);
+  enter_writer(c);
   if (snap)
     if (int rc = check_snap_struct(snap, who)) return rc;
   if (stats && (stats_rows < 0 || stats_row0 < 0 || n < 0 || stats_row0 > stats_rows - n))
@@ -3295,6 +3226,7 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
   if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
     return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
   hipStream_t st = S(stream);
+  Sequence seq(c->v, Sequence::kRollout);
   if (int rc = refresh_if_dirty(c, st)) return rc;
   if (int rc = stage_ticks(c, n, ticks, st)) return rc;
   // per-tick obs scalars [s, solar, t_od, -] next to the tick drivers (same capacity)
@@ -3303,14 +3235,14 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
   ObsArgs o = obs_args(c, sp, &osc[0]);
   auto launches = [&](hipStream_t ls) -> int {
     if (int rc = zero_slabs(c, ls)) return rc;
-    c->ring = 0;
+    c->v.slabs_zeroed();
     for (int t = 0; t < n; ++t) {
       // the current slab is zero here: the memset above (t = 0), then the previous two steps
       // (each zeroes the slab two ahead and a BUFFER step writes no lookahead)
       ObsArgs ot = o;
       ot.sc_dev = c->d_obs_sc + 4 * t;
       ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act, prob ? prob + (int64_t)t * prob_stride : nullptr,
-                   nullptr, nullptr, slab_at(c, c->ring), nullptr};
+                   nullptr, nullptr, slab_at(c, c->v.ring()), nullptr};
       // the state and scalars this tick's actor reads, into snapshot row row0 + t
       if (snap)
         if (int rc = launch_snap(c, snap, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{}, ls)) return rc;
@@ -3330,11 +3262,7 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
     if (int rc = dev_reserve(c->d_act, c->kp.n, "d_act")) return rc;
   if (stats)
     if (int rc = tick_scratch(c)) return rc;  // (before any capture)
-  if (!use_graph) {
-    const int rc = launches(st);
-    c->counts_ready = false;
-    return rc;
-  }
+  if (!use_graph) return seq.end(launches(st));
   std::vector<int64_t> key{n, (int64_t)(uintptr_t)action, act_stride, (int64_t)(uintptr_t)prob, prob_stride,
                            (int64_t)(uintptr_t)reward, rew_stride, (int64_t)(uintptr_t)p_dev,
                            (int64_t)(uintptr_t)sp->comm_table,
@@ -3354,14 +3282,13 @@ static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const md
   if (it == c->actor_graphs.end()) {
     hipGraphExec_t ex;
     if (int rc = capture_graph(c, launches, &ex)) return rc;
-    it = c->actor_graphs.emplace(key, ex).first;
-  } else {
-    c->ring = n % 3;
+    // (the ring at the end of the capture: n steps from slab 0, n % 3)
+    it = c->actor_graphs.emplace(key, std::make_pair(ex, c->v.ring())).first;
   }
-  HIP_TRY(hipGraphLaunch(it->second, st));
+  HIP_TRY(hipGraphLaunch(it->second.first, st));
   ++c->graph_launches[1];
-  c->counts_ready = false;
-  return MDR_OK;
+  c->v.graph_replayed(it->second.second);
+  return seq.ok();
 }
 
 int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -3403,7 +3330,7 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
                                       int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                                       const mdr_snap* snap, const mdr_snap_halo* shalo, int row0, void* stream,
                                       const char* who) {
-  if (c) drop_begun(c);
+  enter_writer(c);
   if (snap)
     if (int rc = check_snap_struct(snap, who)) return rc;
   if (snap && shalo)
@@ -3432,6 +3359,7 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
   if (halo && c->kp.n < (lo > hi ? lo : hi))
     return fail(MDR_EARG, "mdr_actor_rollout_sharded: shard smaller than the ring half-width");
   hipStream_t st = S(stream);
+  Sequence seq(c->v, Sequence::kRollout);
   if (int rc = refresh_if_dirty(c, st)) return rc;
   if (int rc = stage_ticks(c, n, ticks, st)) return rc;
   if (int rc = stage_recs(osc, n, c->d_obs_sc, st)) return rc;
@@ -3487,18 +3415,16 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
                          (const TickArgs*)(c->d_ticks + t), lo, hi, c->rank, c->world, rows(t));
       LAUNCH_CHECK("k_halo_step_pack");
       if (int rc = comm_allreduce(c, buf(t), words, 0, st)) return rc;
-      c->gq_keys_ready = false;
-      c->fz_ready = false;
       if (int rc = launch_step_on(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
                                   reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, buf(t),
                                   buf(t + 1), buf(t + 2), 0, st))
         return rc;
+      c->v.step_issued(false, false, /*keep_ring=*/true);  // (d_c5's own ring of 3)
     }
-    c->counts_ready = false;
-    return MDR_OK;
+    return seq.ok();
   }
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
-  c->ring = 0;
+  c->v.slabs_zeroed();
   // overlap (fused actor, >= 4 tiles, a comm stream): per tick the halo is packed and exchanged on the
   // comm stream while the interior tiles' actor runs on the compute stream; the first and last
   // tile follow once it has landed.  They are the only readers of the halo when lo, hi <= 32 and
@@ -3512,7 +3438,7 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
     ObsArgs ot = o;
     ot.sc_dev = c->d_obs_sc + 4 * t;
     ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act,
-                 prob ? prob + (int64_t)t * prob_stride : nullptr, nullptr, nullptr, slab_at(c, c->ring), nullptr};
+                 prob ? prob + (int64_t)t * prob_stride : nullptr, nullptr, nullptr, slab_at(c, c->v.ring()), nullptr};
     if (overlap) {
       HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state after the previous step
       HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
@@ -3539,13 +3465,12 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
                                     recv, recv ? recv + (size_t)lo * M : nullptr, lo * M, hi * M, st))
         return rc;
     if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, out, st)) return rc;
-    if (int rc = comm_allreduce(c, slab_at(c, c->ring), c->slab_len, 0, st)) return rc;
+    if (int rc = comm_allreduce(c, slab_at(c, c->v.ring()), c->slab_len, 0, st)) return rc;
     if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
                              reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, st))
       return rc;
   }
-  c->counts_ready = false;
-  return MDR_OK;
+  return seq.ok();
 }
 
 int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
