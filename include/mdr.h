@@ -205,12 +205,18 @@ int mdr_params_changed(mdr_ctx* ctx);
  *                           Open-loop sources only: the closed-loop windows of the bang-bang
  *                           sources (k_step_closed) always run the EXACT form and ignore it — a
  *                           decision compares T with a threshold, so a last-bit difference could
- *                           flip an action and fork the trajectory */
+ *                           flip an action and fork the trajectory
+ *   MDR_OPT_WINDOW_GROUP    directly launched window rollouts (mdr_rollout without a graph, one
+ *                           GPU, individual_L2): 1..4 = that many consecutive windows per step
+ *                           launch (k_step_group: state, parameters and per-window coefficients
+ *                           loaded and formed once per group, one reduce launch per group; default
+ *                           4), 0 = one k_step_window launch per window.  Bit-identical results
+ *                           either way; graphs, sharded and common-penalty rollouts ignore it */
 enum { MDR_OPT_STEP_TPW = 1, MDR_OPT_FASTDIV = 2, MDR_OPT_WINDOW_PIPELINE = 3, MDR_OPT_SHARDED_OVERLAP = 4,
        MDR_OPT_GREEDY_SORT = 5, MDR_OPT_FORCE_HALO = 6, MDR_OPT_WINDOW_THERMAL = 7,
        MDR_OPT_HALO_OVERLAP = 9, MDR_OPT_ACTOR_GENERIC = 10, MDR_OPT_HALO_IN_COUNTS = 12,
        MDR_OPT_GQ_BAND = 13, MDR_OPT_ACTOR_FP32_FORM = 14, MDR_OPT_GQ_FUSED = 15, MDR_OPT_GQ_ADAPTIVE = 16,
-       MDR_OPT_ACTOR_GRID = 17 };
+       MDR_OPT_ACTOR_GRID = 17, MDR_OPT_WINDOW_GROUP = 18 };
 enum { MDR_FP32_F16_SPLIT = 0, MDR_FP32_BF16_SPLIT3 = 1 };
 /* (8 was MDR_OPT_ACTOR_PINGPONG, a k_actor schedule measured slower and retired in r04: rejected) */
 enum { MDR_THERMAL_EXACT = 0, MDR_THERMAL_AFFINE = 1 };
@@ -225,6 +231,11 @@ size_t mdr_window_onb_bytes(int64_t n_local, int waves);
  * window launch over n_local houses; MDR_EARG otherwise.  Every k_count_window / k_step_window
  * launch checks its context's buffers with it, so a new launch geometry cannot overrun them. */
 int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size_t wah_bytes);
+/* ... for a k_step_group launch: MDR_OK when group rows of onb_bytes cover `windows` (1..4) windows
+ * of mask rows for every tile of the 4-wave grid over n_local houses (windows *
+ * mdr_window_onb_bytes(n_local, 4)) and wah_bytes an end word per house; MDR_EARG otherwise.  Every
+ * k_step_group launch checks its context's buffers with it. */
+int mdr_window_group_check(int64_t n_local, int windows, size_t onb_bytes, size_t wah_bytes);
 /* Bytes of the per-tick, per-wave penalty partial rows ([32][tiles_padded][2] doubles, tiles of 128
  * houses rounded up to whole 4-wave blocks) that a common-penalty window launch over n_local houses
  * writes: ceil(ceil(n_local / 128) / 4) * 4 * 32 * 2 * 8.  0 for n_local < 0. */

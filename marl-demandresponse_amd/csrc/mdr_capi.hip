@@ -150,9 +150,12 @@ struct mdr_ctx {
   Dev<unsigned long long> d_c5;          // that path's ring of 3 x [count slab | world x halo rows]
   int thermal = MDR_THERMAL_AFFINE;      // MDR_OPT_WINDOW_THERMAL: k_step_window's per-tick update
   int win = kWindowMax;                  // ticks per k_step_window launch (0: one-tick path)
-  Dev<unsigned long long> d_wslab;       // 3 window count slots (mdr_kernels.hip K1W: slab | red | rec)
+  Dev<unsigned long long> d_wslab;       // kWinSlots window count slots (mdr_kernels.hip K1W: slab | red | rec)
   int wslab_len = 0;
-  Dev<uint64_t> d_onb;                   // per-tick ON lane masks of the next window [tiles][HPT][kWindowMax]
+  Dev<uint64_t> d_onb;                   // per-tick ON lane masks of the next window [tiles][kWindowMax][HPT],
+                                         // then (from onb_rows on) the group rows [tiles][kWinGroup][kWindowMax][HPT]
+  size_t onb_rows = 0;                   // u64 words of the first part (the whole buffer before window groups)
+  int win_group = kWinGroup;             // MDR_OPT_WINDOW_GROUP: windows per k_step_group launch (0: k_step_window)
   Dev<uint32_t> d_wah;                   // FSM word at the end of the next window, per house
   Dev<uint64_t> d_onb2;                  // second set for the count-ahead pipeline (pipe_buffers: a unit)
   Dev<uint32_t> d_wah2;
@@ -603,7 +606,8 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     // the tiles up to whole blocks (up to kCountWaves tiles per block), and the waves of a ragged
     // last block store and load the mask rows of their (empty) tiles too
     const size_t tiles64 = whole_blocks(win_tiles(cfg->n_local) + 1, kCountWaves) * kWinHpt + 1;
-    if (c->d_wslab.reserve((size_t)3 * c->wslab_len) || c->d_onb.reserve(tiles64 * kWindowMax) ||
+    c->onb_rows = tiles64 * kWindowMax;
+    if (c->d_wslab.reserve((size_t)kWinSlots * c->wslab_len) || c->d_onb.reserve((1 + kWinGroup) * c->onb_rows) ||
         c->d_wah.reserve((size_t)cfg->n_local + 1))
       return cleanup(fail(MDR_ENOMEM, "window count slabs"));
   } else {
@@ -701,6 +705,10 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
         return fail(MDR_EARG, "mdr_set_option: ACTOR_FP32_FORM must be MDR_FP32_F16_SPLIT or MDR_FP32_BF16_SPLIT3");
       c->actor_fp32_bf16 = value == MDR_FP32_BF16_SPLIT3;
       c->actor_key.clear();  // (packed again for the form)
+      break;
+    case MDR_OPT_WINDOW_GROUP:
+      if (value < 0 || value > kWinGroup) return fail(MDR_EARG, "mdr_set_option: WINDOW_GROUP outside 0..4");
+      c->win_group = (int)value;
       break;
     case MDR_OPT_WINDOW_THERMAL:
       if (value != MDR_THERMAL_EXACT && value != MDR_THERMAL_AFFINE)
@@ -930,7 +938,7 @@ static bool closed_ok(const mdr_ctx* c, int mode, bool stats = false) {
 // after allocation or a failed launch sequence it is cleared once, outside any graph
 static int wslab_clean(mdr_ctx* c, hipStream_t st) {
   if (!c->v.slots_dirty() || !c->d_wslab) return MDR_OK;
-  HIP_TRY(hipMemsetAsync(c->d_wslab, 0, 3 * sizeof(unsigned long long) * c->wslab_len, st));
+  HIP_TRY(hipMemsetAsync(c->d_wslab, 0, kWinSlots * sizeof(unsigned long long) * c->wslab_len, st));
   c->v.slots_cleaned();
   return MDR_OK;
 }
@@ -952,6 +960,20 @@ extern "C" int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size
                               std::to_string(need) + " B");
   if (wah_bytes < (size_t)n_local * sizeof(uint32_t))
     return fail(MDR_EARG, "window launch: end-word buffer shorter than the shard");
+  return MDR_OK;
+}
+
+// k_step_group: every wave of the grid (4 tiles per block) reads and stores `windows` windows of
+// mask rows per tile, and one end word per house
+extern "C" int mdr_window_group_check(int64_t n_local, int windows, size_t onb_bytes, size_t wah_bytes) {
+  if (n_local < 1) return fail(MDR_EARG, "window group launch: no houses");
+  if (windows < 1 || windows > kWinGroup) return fail(MDR_EARG, "window group launch: windows outside 1..4");
+  const size_t need = (size_t)windows * mdr_window_onb_bytes(n_local, 4);
+  if (onb_bytes < need)
+    return fail(MDR_EARG, "window group launch: ON-mask rows of " + std::to_string(onb_bytes) +
+                              " B, the launch geometry touches " + std::to_string(need) + " B");
+  if (wah_bytes < (size_t)n_local * sizeof(uint32_t))
+    return fail(MDR_EARG, "window group launch: end-word buffer shorter than the shard");
   return MDR_OK;
 }
 
@@ -1092,6 +1114,51 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
   return MDR_OK;
 }
 
+// one k_step_group launch: the (ACT, SIMPLE, KA, FORM) instantiation for this context (individual_L2)
+static int launch_step_group(mdr_ctx* c, int mode, bool ka, const uint8_t* action, int64_t act_stride,
+                             const TickArgs* tk, const WinGrp& g, double* reward, int64_t rew_stride,
+                             const WinDrv& dv, hipStream_t st) {
+  if (c->d_onb.capacity() < c->onb_rows) return fail(MDR_ESTATE, "window group launch: no group mask rows");
+  if (int rc = mdr_window_group_check(c->kp.n, kWinGroup, dev_bytes(c->d_onb) - c->onb_rows * sizeof(uint64_t),
+                                      dev_bytes(c->d_wah)))
+    return rc;
+  if (g.nw < 1 || g.nw > kWinGroup || g.la_nw < 0 || g.la_nw > kWinGroup)
+    return fail(MDR_EARG, "window group launch: windows outside 1..4");
+  for (int i = 0; i < kWinGroup; ++i)
+    if (g.K[i] < 0 || g.K[i] > kWindowMax || g.la_K[i] < 0 || g.la_K[i] > kWindowMax)
+      return fail(MDR_EARG, "window group launch: a window of more than 32 ticks");
+  const unsigned grid = win_grid(c);
+  const KParams kp = c->kp;
+  uint64_t* onb = c->d_onb + c->onb_rows;  // the group rows, behind the first window's
+#define MDR_SG_L(A, SI, KA_, FO)                                                                               \
+  hipLaunchKernelGGL((k_step_group<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, act_stride, tk, g, \
+                     reward, rew_stride, onb, (uint32_t*)c->d_wah, dv)
+#define MDR_SG_F(A, SI, KA_)                                                         \
+  do {                                                                               \
+    if (c->thermal == MDR_THERMAL_AFFINE) MDR_SG_L(A, SI, KA_, MDR_THERMAL_AFFINE);  \
+    else MDR_SG_L(A, SI, KA_, MDR_THERMAL_EXACT);                                    \
+  } while (0)
+#define MDR_SG_K(A, SI)              \
+  do {                               \
+    if (ka) MDR_SG_F(A, SI, true);   \
+    else MDR_SG_F(A, SI, false);     \
+  } while (0)
+#define MDR_SG_S(A)                          \
+  do {                                       \
+    if (win_simple(c)) MDR_SG_K(A, true);    \
+    else MDR_SG_K(A, false);                 \
+  } while (0)
+  if (mode == MDR_ACT_RANDOM) MDR_SG_S(MDR_ACT_RANDOM);
+  else if (mode == MDR_ACT_ALWAYS_ON) MDR_SG_S(MDR_ACT_ALWAYS_ON);
+  else MDR_SG_S(MDR_ACT_BUFFER);
+#undef MDR_SG_S
+#undef MDR_SG_K
+#undef MDR_SG_F
+#undef MDR_SG_L
+  LAUNCH_CHECK("k_step_group");
+  return MDR_OK;
+}
+
 // ---- the open-loop window sequencers (window_launches, window_launches_direct,
 // window_pipeline).  Window w of the WinPlan counts into slot w % 3 of d_wslab, under a SlotsGuard.
 struct WinSeq {  // the per-window pieces the three share
@@ -1154,6 +1221,55 @@ static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream
   return slots.done();
 }
 
+// The direct sequence's windows in groups of G <= kWinGroup (MDR_OPT_WINDOW_GROUP): behind
+// the first window's count, k_step_group<KA>({w0}; counting w1..wG ahead), the later drivers' staging,
+// then per group one reduce launch and one k_step_group (counting the next group ahead).  Window w
+// counts into slot w % kWinSlots.
+static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tick* host_ticks) {
+  mdr_ctx* c = s.c;
+  const RolloutArgs& a = s.a;
+  const int nw = s.plan.count(), K0 = s.plan.size(0), ncap = c->kp.n_cap;
+  auto slot = [&](int w) { return c->d_wslab + (size_t)(w % kWinSlots) * c->wslab_len; };
+  auto rec = [&](int w) {
+    return reinterpret_cast<const double*>(win_red_ptr(c, slot(w)) + (size_t)kWindowMax * ncap);
+  };
+  auto ahead = [&](WinGrp& g, int w1) {  // the lookahead over the group that starts at window w1
+    g.la_nw = std::max(0, std::min(G, nw - w1));
+    for (int i = 0; i < g.la_nw; ++i) g.la_K[i] = s.plan.size(w1 + i), g.la_slot[i] = slot(w1 + i);
+  };
+  static const WinDrv none{};
+  {
+    WinGrp g{};
+    g.nw = 1, g.K[0] = K0, g.rec[0] = rec(0), g.first_onb = c->d_onb;
+    ahead(g, 1);
+    if (int rc = launch_step_group(c, a.mode, true, a.act_row(0), a.act_stride, s.tk(0), g, a.rew_row(0), a.rew_stride,
+                                   dv, s.st))
+      return rc;
+  }
+  if (a.n > K0)
+    if (int rc = stage_recs(host_ticks + K0, a.n - K0, c->d_ticks + K0, s.st)) return rc;
+  for (int w = 1; w < nw; w += G) {
+    const int cnt = std::min(G, nw - w), t0 = s.plan.start(w);
+    WinRed r{};
+    WinGrp g{};
+    r.nw = g.nw = cnt;
+    for (int i = 0; i < cnt; ++i) {
+      r.K[i] = g.K[i] = s.plan.size(w + i);
+      r.slot[i] = slot(w + i);
+      r.tk[i] = s.tk(w + i);
+      g.rec[i] = rec(w + i);
+    }
+    r.p_out = w + cnt == nw ? a.p_out : nullptr;  // the rollout's last P
+    hipLaunchKernelGGL(k_win_reduce_group, dim3(r.K[0], cnt), dim3(64 * ncap), 0, s.st, c->kp, r);  // (the larger windows first)
+    LAUNCH_CHECK("k_win_reduce_group");
+    ahead(g, w + cnt);
+    if (int rc = launch_step_group(c, a.mode, false, a.act_row(t0), a.act_stride, s.tk(w), g, a.rew_row(t0),
+                                   a.rew_stride, none, s.st))
+      return rc;
+  }
+  return MDR_OK;
+}
+
 enum FirstCounts {  // where the first window's per-tick counts of a direct sequence come from
   kCountNow,        // counted here; the count kernel's last block does the P-only reduce
   kBegun,           // the same launch, already issued by mdr_rollout_begin
@@ -1185,6 +1301,11 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
   dv.tick0 = host_ticks[0].tick;
   if (nw == 1) dv.p_out = a.p_out;
   if (first == kBegunAllreduced) dv.red = win_red_ptr(c, s.slot(0));
+  // an unsharded context under individual_L2: the windows in groups (MDR_OPT_WINDOW_GROUP)
+  if (c->win_group > 0 && first != kBegunAllreduced && !has_comm(c) && c->world <= 1 && !win_common(c)) {
+    if (int rc = window_groups(s, c->win_group, dv, host_ticks)) return rc;
+    return slots.done();
+  }
   if (int rc = s.step(0, nw > 1 ? s.plan.size(1) : 0, c->d_onb, c->d_wah, s.slot(1), &dv)) return rc;
   if (int rc = s.finish(0)) return rc;
   if (a.n > K)
@@ -1230,7 +1351,7 @@ static int window_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
 // the second ON-mask / end-word set of the count-ahead pipeline (allocated on first use)
 static bool pipe_buffers(mdr_ctx* c) {
   if (c->d_onb2 && c->d_wah2) return true;
-  if (!c->d_onb2.reserve(c->d_onb.capacity()) && !c->d_wah2.reserve(c->d_wah.capacity())) return true;
+  if (!c->d_onb2.reserve(c->onb_rows) &&!c->d_wah2.reserve(c->d_wah.capacity())) return true;
   (void)hipGetLastError();  // (the caller runs the windows unpipelined: no error is left behind)
   c->d_onb2.reset(), c->d_wah2.reset();  // both or neither
   return false;

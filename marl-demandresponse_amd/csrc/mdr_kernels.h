@@ -175,6 +175,37 @@ template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool COMMON = false>
 __global__ void k_step_window(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, int K,
                               int la_K, const double* rec, double* reward, int64_t rew_stride, uint64_t* onb,
                               uint32_t* wah, unsigned long long* next_slot, WinDrv dv, WinPen pen);
+// A GROUP of consecutive windows of one rollout call per launch (k_step_group, the direct sequence of
+// an unsharded context under individual_L2): state, parameters and per-window coefficients are loaded
+// and formed once, the group's windows are stepped back to back, then the FSM runs ahead over the next
+// group's windows.  No wave waits for another wave's data: a launch depends on completed launches only.
+constexpr int kWinGroup = 4;  // windows per launch at most (MDR_OPT_WINDOW_GROUP: 1..kWinGroup)
+// window count slots: window w of a grouped call in slot w % kWinSlots, so the stepped group's tick
+// records and the counted group's shards never share a slot (the other sequencers use the first 3)
+constexpr int kWinSlots = 2 * kWinGroup;
+struct WinGrp {
+  int nw, la_nw;                           // windows stepped; windows counted ahead (0: none)
+  int K[kWinGroup], la_K[kWinGroup];       // their ticks (WinPlan sizes)
+  const double* rec[kWinGroup];            // the stepped windows' tick records (KA: rec[0], P only)
+  unsigned long long* la_slot[kWinGroup];  // the counted windows' slots
+  const uint64_t* first_onb;               // KA: the first window's mask rows as k_count_window left them
+};
+// onb: the group rows [tile][kWinGroup][kWindowMax][HPT] — read (the stepped windows'; KA reads
+// first_onb instead), then replaced by the counted windows'; wah: the end word after the last
+// stepped window, replaced by the one after the last counted window.  action / tkp / reward: at the
+// group's first tick.  KA: the group is the call's first window alone, its drivers in dv.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+__global__ void k_step_group(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, WinGrp g,
+                             double* reward, int64_t rew_stride, uint64_t* onb, uint32_t* wah, WinDrv dv);
+// k_win_reduce for the windows of a group in one launch: block (j, w) is tick j of window w
+struct WinRed {
+  int nw;
+  int K[kWinGroup];
+  unsigned long long* slot[kWinGroup];
+  const TickArgs* tk[kWinGroup];
+  double* p_out;  // <- P of the last window's last tick, or null
+};
+__global__ void k_win_reduce_group(KParams p, WinRed r);
 // one block per tick j: res[j] = {sum, max} of part[j][0..ntile) in index order
 __global__ void k_win_pen_reduce(const double* part, int ntile, double* res);
 // reward rows j0 + blockIdx.y of a common-penalty window from res / sig (k_reward_finalize's expression)

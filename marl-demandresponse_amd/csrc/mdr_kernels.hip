@@ -1077,6 +1077,14 @@ __global__ void __launch_bounds__(256) k_win_reduce(KParams p, unsigned long lon
   win_reduce_body(p, slot, nt, tkp ? tkp + blockIdx.x : nullptr, p_out);
 }
 
+// k_win_reduce for every window of a group in one launch (grid: the largest window's ticks x the
+// group's windows; a block past its window's ticks has nothing to do)
+__global__ void __launch_bounds__(256) k_win_reduce_group(KParams p, WinRed r) {
+  const int w = blockIdx.y, K = r.K[w];
+  if ((int)blockIdx.x >= K) return;  // (block-uniform)
+  win_reduce_body(p, r.slot[w], K, r.tk[w] + blockIdx.x, w == r.nw - 1 ? r.p_out : nullptr);
+}
+
 // Sharded closed-loop windows: win_reduce_body's shard sum without the record (its own statements,
 // so k_win_reduce's code stays the parent's).  Block j sums this rank's 64 shards of tick j per class
 // into red and zeroes them; the K x n_cap totals in red are then allreduced (<= 1 KiB) and
@@ -1697,6 +1705,239 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
   }
 }
 
+// A group of g.nw <= kWinGroup consecutive windows of one rollout call, then the lookahead over the
+// g.la_nw windows of the next group (mdr_kernels.h WinGrp; individual_L2 only).  k_step_window's
+// pieces in k_step_window's order, with what it does once per window split in two:
+//   * once per launch: state, parameters, class, end word, thresholds, AffWin / RcWin, and at the end
+//     the state's write-back and the lookahead;
+//   * once per window: the tick loop, word for word (the same expressions in the same order), over
+//     that window's mask rows and tick records.
+// Between two windows of a group the values take the round trip they take between two k_step_window
+// launches, so no result moves by a bit: AFFINE stores Celsius (tk - 273.0) and reloads it
+// (+ 273.0), and win_finite is formed again from the coefficients and the new tk, tmk, hk; EXACT
+// carries T, Tm as they are.  params_ok is read once (nothing changes it inside a rollout call).
+// The group's last end word is the one in wah on entry: the producer of the group's masks left it
+// after its last window.  Each counted window has its own LDS count rows, so one barrier separates
+// the lookahead's runs from their flushes.  No wave waits for another wave's data.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+__global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __restrict__ action,
+                                                    int64_t act_stride, const TickArgs* __restrict__ tkp, WinGrp g,
+                                                    double* __restrict__ reward, int64_t rew_stride,
+                                                    uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
+                                                    WinDrv dv) {
+  constexpr bool AFF = FORM == MDR_THERMAL_AFFINE;
+  __shared__ unsigned s_cnt[kWinGroup][4][kWinMax * kWinCap];
+  const int wv = threadIdx.x >> 6;
+  const WinTile<HPT> t(p);
+  uint64_t* onb_w = onb + (size_t)t.tile * kWinGroup * HPT * kWinMax;  // this wave's rows [kWinGroup][kWinMax][HPT]
+  // the stepped windows' rows (KA: the first window's, from the count kernel)
+  const uint64_t* onb_r = KA ? g.first_onb + (size_t)t.tile * HPT * kWinMax : onb_w;
+  // KA: lane j = tick j's negated signal penalty (k_step_window's)
+  uint32_t ns_lo = 0, ns_hi = 0;
+  if (KA) {
+    const int K = g.K[0];
+    const double* rec = g.rec[0];
+    const int l = (int)(threadIdx.x & 63) < K ? (int)(threadIdx.x & 63) : 0;
+    const double P = rec[l * kWinRec];
+    if (dv.p_out && blockIdx.x == 0 && threadIdx.x == 0) *dv.p_out = rec[(K - 1) * kWinRec];  // (last window)
+    const double ns = win_nsig(p, P, dv.s_prev[l]);
+    ns_lo = (uint32_t)__double_as_longlong(ns);
+    ns_hi = (uint32_t)((uint64_t)__double_as_longlong(ns) >> 32);
+  }
+
+  // ---- state + parameters, once per launch
+  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
+  uint32_t w_end[HPT];
+  int cls[HPT];
+  const bool params_ok = !*p.params_bad && p.fast_tick_ok;
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    const uint32_t i = t.idx[h];
+    T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
+    ca[h] = p.ca[i]; cm[h] = p.cm[i];
+    w_end[h] = wah[i];
+    cls[h] = p.cap_idx[i];
+  }
+  double q_on[kWinCap];
+#pragma unroll
+  for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
+  double qc[HPT], lo_tg[HPT], hi_tg[HPT];  // heat when ON; deadbandL2 thresholds (utils.py:4-23)
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    qc[h] = q_on[0];
+#pragma unroll
+    for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
+    hi_tg[h] = tg[h] + p.deadband / 2.0;
+    lo_tg[h] = tg[h] - p.deadband / 2.0;
+  }
+  // per-house constants of the form
+  RcWin rw[AFF ? 1 : HPT];
+  AffWin aw[AFF ? HPT : 1];
+  double tk[HPT], tmk[HPT], hk[HPT];  // AFFINE: Kelvin state, Kelvin penalty threshold
+#pragma unroll
+  for (int h = 0; h < HPT; ++h) {
+    if constexpr (AFF) {
+      aw[h] = aff_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt, qc[h], params_ok);
+      hk[h] = hi_tg[h] + 273.0;
+    } else if (params_ok) {
+      rw[h] = rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
+    } else {  // IEEE division (identical bits; parameters outside the fast-division range)
+      rw[h].k = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
+      rw[h].rCa.nb = -ca[h];
+      rw[h].rc.nb = -ua[h];
+      rw[h].rd.nb = -(rw[h].k.r2 - rw[h].k.r1);
+      rw[h].UaHm = ua[h] + hm[h];
+    }
+  }
+
+  const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
+  const double nalpha = -p.alpha_temp;
+  auto lane_nsig = [&](int j) { return __longlong_as_double((long long)readlane_u64(ns_lo, ns_hi, j)); };
+  int tick_off = 0;  // the window's first tick, from the group's
+  for (int gi = 0; gi < g.nw; ++gi) {
+    const int K = g.K[gi];
+    const double* __restrict__ rec = g.rec[gi];
+    const uint64_t* onb_g = onb_r + gi * (kWinMax * HPT);
+    // ---- what a k_step_window launch forms from the state it loads
+    bool win_finite = true;  // AFFINE: every coefficient and temperature finite
+    if constexpr (AFF) {
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        tk[h] = T[h] + 273.0;
+        tmk[h] = Tm[h] + 273.0;
+        const AffWin& a = aw[h];
+        const double s = a.tt + a.tm + a.tq + a.to + a.qt + a.mt + a.mm + a.mq + a.mo + a.qm + tk[h] + tmk[h] + hk[h];
+        win_finite = win_finite && (s - s == 0.0);
+      }
+      win_finite = __all(win_finite);
+    }
+
+    // ---- the K ticks: heat source from the stored ON masks, thermal update, reward
+    // the tick's scalars (record, ON masks) are loaded one tick ahead (scalar loads, no vector work)
+    double r_od = KA ? dv.od_k[0] : rec[0], r_sol = KA ? dv.solar[0] : rec[1], r_sig = KA ? lane_nsig(0) : rec[2];
+    uint64_t r_ok = KA ? (uint64_t)(dv.ok & 1u) : __double_as_longlong(rec[3]);  // 1.0 or 0.0: compared as bits (scalar unit)
+    uint64_t r_on[HPT];
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) r_on[h] = onb_g[h];
+    for (int j = 0; j < K; ++j) {
+      const double od_k = r_od, solar = r_sol, nsig = r_sig;
+      const bool tick_ok = r_ok != 0;
+      uint64_t on_m[HPT];
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) on_m[h] = r_on[h];
+      const int jn = j + 1 < K ? j + 1 : j;
+      if (KA) {
+        r_od = dv.od_k[jn];
+        r_sol = dv.solar[jn];
+        r_sig = lane_nsig(jn);
+        r_ok = (dv.ok >> jn) & 1u;
+      } else {
+        r_od = rec[jn * kWinRec + 0];
+        r_sol = rec[jn * kWinRec + 1];
+        r_sig = rec[jn * kWinRec + 2];
+        r_ok = __double_as_longlong(rec[jn * kWinRec + 3]);
+      }
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) r_on[h] = onb_g[jn * HPT + h];
+      char* rrow = reinterpret_cast<char*>(reward + (int64_t)(tick_off + j) * rew_stride);
+      // the reward from the new Celsius temperature Tn (Kelvin tkn on the affine path)
+      auto reward_of = [&](int h, double Tn, double tkn, auto fast_c) {
+        constexpr bool F = decltype(fast_c)::value;
+        if (SIMPLE) {  // (k_step_window's reward_of: see there)
+          if (AFF && F) {
+            const double x = tkn - hk[h];
+            return __builtin_fma(nalpha, x * x, nsig);
+          }
+          const double x = Tn - hi_tg[h];
+          const double pen = F ? x * x : deadband_l2_0(hi_tg[h], Tn);
+          return nalpha * pen + nsig;
+        }
+        double pen = 0.0;
+        if (hi_tg[h] < Tn) { const double x = Tn - hi_tg[h]; pen = x * x; }
+        else if (lo_tg[h] > Tn) { const double x = lo_tg[h] - Tn; pen = x * x; }
+        const double tpen = p.alpha_temp * pen;
+        return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + -nsig);
+      };
+      if constexpr (AFF) {
+        auto houses = [&](auto fast_c) {
+#pragma unroll
+          for (int h = 0; h < HPT; ++h) {
+            const AffWin& a = aw[h];
+            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
+            const double ut = __builtin_fma(a.to, od_k, __builtin_fma(a.tq, solar, on ? a.qt : 0.0));
+            const double um = __builtin_fma(a.mo, od_k, __builtin_fma(a.mq, solar, on ? a.qm : 0.0));
+            const double tkn = __builtin_fma(a.tt, tk[h], __builtin_fma(a.tm, tmk[h], ut));
+            const double tmkn = __builtin_fma(a.mt, tk[h], __builtin_fma(a.mm, tmk[h], um));
+            tk[h] = tkn;
+            tmk[h] = tmkn;
+            const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
+            if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          }
+        };
+        if (win_finite && tick_ok) houses(std::true_type());
+        else houses(std::false_type());
+      } else {
+        // all lanes in range: the comparison masks themselves (v_cmp writes a lane mask) against exec
+        uint64_t ok_m = ~0ull;
+#pragma unroll
+        for (int h = 0; h < HPT; ++h)
+          ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
+        const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
+        auto houses = [&](auto fast_c) {
+          constexpr bool F = decltype(fast_c)::value;
+#pragma unroll
+          for (int h = 0; h < HPT; ++h) {
+            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
+            const double q = on ? qc[h] : 0.0;
+            double Tn, Tmn;
+            rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, solar, od_k, Tn, Tmn);
+            T[h] = Tn;
+            Tm[h] = Tmn;
+            const double r = reward_of(h, Tn, 0.0, fast_c);
+            if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          }
+        };
+        if (fast) houses(std::true_type());
+        else houses(std::false_type());
+      }
+    }
+    if constexpr (AFF) {  // (the Celsius a k_step_window launch stores; the next window reloads it)
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        T[h] = tk[h] - 273.0;
+        Tm[h] = tmk[h] - 273.0;
+      }
+    }
+    tick_off += K;
+  }
+
+  // ---- state back, once per launch (the FSM word at the group's end came with the ON masks)
+#pragma unroll
+  for (int h = 0; h < HPT; ++h)
+    if (t.v[h]) {
+      const uint32_t i = t.i0 + 64u * h;
+      p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w_end[h];
+    }
+
+  // ---- lookahead: the next group's ON masks, end word and class counts, window by window
+  if (g.la_nw > 0) {
+    uint64_t cmk[HPT][kWinCap];
+    win_classes<HPT>(t, cls, cmk);
+    for (int li = 0; li < g.la_nw; ++li) {
+      const int la_K = g.la_K[li];
+      win_run<ACT, HPT>(p, w_end, cmk, t, KA ? nullptr : tkp + tick_off, KA ? dv.tick0 + (uint64_t)tick_off : 0, la_K,
+                        ACT == MDR_ACT_BUFFER ? action + (int64_t)tick_off * act_stride : nullptr, act_stride,
+                        s_cnt[li][wv], onb_w + li * (kWinMax * HPT));
+      tick_off += la_K;
+    }
+#pragma unroll
+    for (int h = 0; h < HPT; ++h)
+      if (t.v[h]) wah[t.i0 + 64u * h] = w_end[h];
+    __syncthreads();
+    for (int li = 0; li < g.la_nw; ++li) win_flush(p, g.la_K[li], s_cnt[li], g.la_slot[li]);
+  }
+}
+
 // --------------------------------------------------------------------------------------- K1C
 // Temporally blocked step for the CLOSED-LOOP bang-bang sources (BangBangController /
 // DeadbandBangBangController, bangbang_controllers.py:25-65): one launch steps a window of K <= 32
@@ -2062,6 +2303,18 @@ template __global__ void k_step_closed<kActDeadband, kWinHpt, false, true, doubl
 MDR_INST_WIN(MDR_ACT_RANDOM)
 MDR_INST_WIN(MDR_ACT_ALWAYS_ON)
 MDR_INST_WIN(MDR_ACT_BUFFER)
+
+#define MDR_INST_GRP_F(A, SI, KA_, FO)                                                                         \
+  template __global__ void k_step_group<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
+                                                                 WinGrp, double*, int64_t, uint64_t*, uint32_t*, WinDrv);
+#define MDR_INST_GRP(A)                                                                                    \
+  MDR_INST_GRP_F(A, true, false, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, false, MDR_THERMAL_EXACT)     \
+  MDR_INST_GRP_F(A, true, true, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, true, MDR_THERMAL_EXACT)       \
+  MDR_INST_GRP_F(A, true, false, MDR_THERMAL_AFFINE) MDR_INST_GRP_F(A, false, false, MDR_THERMAL_AFFINE)   \
+  MDR_INST_GRP_F(A, true, true, MDR_THERMAL_AFFINE) MDR_INST_GRP_F(A, false, true, MDR_THERMAL_AFFINE)
+MDR_INST_GRP(MDR_ACT_RANDOM)
+MDR_INST_GRP(MDR_ACT_ALWAYS_ON)
+MDR_INST_GRP(MDR_ACT_BUFFER)
 
 #define MDR_INST_PIPE(T, A, LA, G)                                                                    \
   template __global__ void k_step_pipe<T, A, LA, G>(KParams, const uint8_t*, TickArgs, const TickArgs*, \
