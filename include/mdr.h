@@ -685,7 +685,7 @@ int mdr_actor_rollout_snap(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, con
  * p_host with the device scalar, as in mdr_snapshot) — the post-step obs' cluster_hvac_power that
  * TrainingManager.test reads (training_manager.py:279-291) —, [13..15] = 0.  Asynchronous: two kernel
  * launches, a fixed summation order, no atomics.  Single shard: a communicator or world > 1 gives
- * MDR_ESTATE.  MDR_EARG: ctx or out16 NULL. */
+ * MDR_ESTATE (a shard's partial row: mdr_tick_stats_sharded).  MDR_EARG: ctx or out16 NULL. */
 int mdr_tick_stats(mdr_ctx* ctx, const double* reward, const double* p_dev, double p_host, double* out16,
                    void* stream);
 /* mdr_actor_rollout_snap (snap may be NULL) that also writes tick t's row — the state after its
@@ -752,6 +752,69 @@ int mdr_actor_rollout_sharded_snap(mdr_ctx* ctx, int n_ticks, const mdr_tick* ti
 int mdr_obs_gather_sharded(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_snap* snap, const mdr_snap_halo* halo,
                            int rows, const int64_t* idx, int64_t m, float* obs, void* stream);
 
+/* ---- stats rows of a house-sharded cluster: one exact exchange per call -------- */
+/* The single-shard entry points above (mdr_tick_stats, mdr_rollout_stats[_path], mdr_actor_rollout_stats,
+ * mdr_greedy_rollout_stats) keep their MDR_ESTATE on a context with a communicator; these are the
+ * sharded forms.  A row is twelve reductions over houses plus the cluster power, and nobody reads it
+ * before the call returns, so the ranks' PARTIAL rows of a whole call of m ticks are combined once,
+ * behind the call: rank r writes only X[r] of the context-owned exchange slab X[world][m][16] (all zero
+ * between calls), ONE in-place double sum-allreduce of world * m * 16 elements assembles it — every
+ * element has exactly one non-zero contributor, so the sum is exact in any order, tree or backend (a
+ * -0.0 partial arrives as +0.0) — and k_stats_rows_combine forms row t in rank order (slot 2 by fmax,
+ * the other eleven by +; [12] = P, global on every rank already; [13..15] = 0), writes it to the
+ * caller's rows and zeroes the slab again.  The rows are bit-identical on every rank and between
+ * communicators; at world 1 they are the single-shard rows; against the single process at world > 1
+ * the sum slots differ by the regrouping of the same addends only. */
+/* bytes of the slab of an m-row call (host only); 0: world < 1, m < 1, or overflow */
+size_t mdr_stats_exchange_bytes(int world, int m);
+/* World and rank of the slab on a shard WITHOUT a communicator of the library's (exchanges driven by
+ * the caller, e.g. torch.distributed); a context with one answers MDR_OK for its own pair, MDR_ESTATE
+ * for another.  MDR_EARG: ctx NULL, world < 1, rank outside [0, world). */
+int mdr_stats_exchange_ranks(mdr_ctx* ctx, int world, int rank);
+/* Reserve the slab for an m-row call and return it (*count = world * m * 16 doubles): what a caller
+ * driving the exchange itself sum-allreduces between mdr_tick_stats_sharded and mdr_stats_rows_combine.
+ * MDR_EARG: dev_ptr, count or ctx NULL, m < 1.  MDR_ESTATE: neither a communicator nor a shard. */
+int mdr_stats_exchange_buffer(mdr_ctx* ctx, int m, double** dev_ptr, int64_t* count);
+/* This rank's partial row `row` of an m-row call: mdr_tick_stats' two launches into X[rank][row]
+ * ([0..11] this shard's values with N = n_global, [12] P, [13..15] 0).  MDR_EARG: row outside [0, m),
+ * ctx NULL, m < 1.  MDR_ESTATE: neither a communicator nor a shard (n_local < n_global). */
+int mdr_tick_stats_sharded(mdr_ctx* ctx, const double* reward, const double* p_dev, double p_host, int m, int row,
+                           void* stream);
+/* The combine of an m-row call of mdr_tick_stats_sharded rows, after the caller's sum-allreduce of the
+ * slab: rows -> stats[stats_row0 .. stats_row0 + m][16], the slab zeroed.  MDR_EARG (the row range
+ * first): stats_row0 < 0 or stats_row0 + m > stats_rows, stats or ctx NULL, m < 1. */
+int mdr_stats_rows_combine(mdr_ctx* ctx, int m, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream);
+/* ... with the allreduce over the context's communicator (RCCL or mdr_comm_host) in front of it.
+ * MDR_ESTATE: no communicator. */
+int mdr_stats_rows_exchange(mdr_ctx* ctx, int m, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream);
+/* mdr_rollout_sharded that also writes tick t's row into stats[stats_row0 + t][16]; stats == NULL is
+ * mdr_rollout_sharded launch for launch.  Bang-bang sources under individual_L2, <= 4 classes, the
+ * window on: the same closed-loop window sequencers with k_step_closed<..., STATS>, and per window
+ * k_closed_stats_part (this rank's raw sums, S = sum pen_i in slot 4, its ON totals per class in
+ * [12..15]) behind k_win_shard_sum and before the window's allreduce rewrites those totals; the
+ * combine's closed form sums the class totals (exact integers) and forms P, the signal term and slot 4
+ * with k_closed_stats' expressions and N = n_global — the rows need no collective of their own per
+ * window.  Window 0 or more classes: one launch per tick on one stream, every tick's P on the device
+ * and mdr_tick_stats' launches behind each step (never the lagged-reward overlap form).  Either way
+ * ONE exchange and combine on the caller's stream after the last finish.  MDR_EARG: the row range
+ * (checked before anything is staged or launched), an open-loop window source (mdr_rollout_stats'
+ * message), the common penalty modes. */
+int mdr_rollout_sharded_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
+                              int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
+                              double* p_out, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream);
+/* Which of those applies, without launching: MDR_STATS_CLOSED_WINDOWS, MDR_STATS_PER_TICK, or the
+ * refusal mdr_rollout_sharded_stats would give. */
+int mdr_rollout_sharded_stats_path(mdr_ctx* ctx, int action_mode);
+/* mdr_actor_rollout_sharded_snap (snap may be NULL) that also writes tick t's row: in all three forms
+ * of the loop tick t's partial row follows its step on the compute stream, before tick t + 1's snapshot
+ * and actor (and before a stride-0 reward row is overwritten); one exchange after the loop.
+ * stats == NULL is the _snap call launch for launch. */
+int mdr_actor_rollout_sharded_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const mdr_obs_scalars* obs_sc,
+                                    const mdr_obs_spec* obs, uint8_t* action, int64_t act_stride, float* prob,
+                                    int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                                    const mdr_snap* snap, const mdr_snap_halo* halo, int row0, double* stats,
+                                    int64_t stats_rows, int64_t stats_row0, void* stream);
+
 /* ---- interpolated base power ---------------------------------------- */
 /* Replaces PowerInterpolator (server/app/core/environment/power_grid/interpolation.py:24-264) as
  * PowerGrid.power_step calls it every interp_update_period seconds (power_grid.py:149-161): the
@@ -811,8 +874,8 @@ int mdr_rccl_allgather(mdr_ctx* ctx, const void* send, void* recv, int64_t bytes
  * allreduce and the finish run on the communicator's side stream beside the next window's step
  * kernel; one shared row (rew_stride == 0) finishes the last window's last tick only, on one
  * stream.  With mdr_set_rollout_window(0) or more classes they take the per-tick loops above.
- * Refused (MDR_EARG): the common penalty modes.  No stats rows on a sharded context
- * (mdr_rollout_stats: MDR_ESTATE). */
+ * Refused (MDR_EARG): the common penalty modes.  Stats rows on a sharded context:
+ * mdr_rollout_sharded_stats (mdr_rollout_stats keeps its MDR_ESTATE). */
 int mdr_rollout_sharded(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                         int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                         double* p_out, void* stream);

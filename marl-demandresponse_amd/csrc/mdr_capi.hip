@@ -226,6 +226,8 @@ struct mdr_ctx {
   Dev<double> d_tick_part;     // k_tick_stats block partials
   Dev<double> d_rows_part;     // mdr_greedy_rollout_stats: [kTickRowsBatch][kTickBlocks][kStats] block partials
   Dev<double> d_rows_p;        //   and the batch's [kTickRowsBatch] cluster powers
+  Dev<double> d_xstat;         // sharded stats rows: the exchange slab X[world][m][kTickRow], all zero between calls
+  int x_world = 0, x_rank = 0; // mdr_stats_exchange_ranks: the slab's world / rank on a shard without a communicator
   std::map<std::vector<int64_t>, std::pair<hipGraphExec_t, int>> actor_graphs;  // (as graphs)
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
   int64_t graphs_guarded = 0;            // captured graphs the memset guard walked (graph_memset_guard)
@@ -1456,12 +1458,23 @@ struct ClosedShardSeq {
   mdr_ctx* c;
   const RolloutArgs& a;
   WinPlan plan;
+  double* xpart = nullptr;  // mdr_rollout_sharded_stats: this rank's partial rows X[rank][0..n) (null: no rows)
   unsigned long long* slot(int w) const { return c->d_wslab + (size_t)(w % 3) * c->wslab_len; }
   bool finished(int w) const { return a.rew_stride || w == plan.count() - 1; }
   int step(int w, hipStream_t st) const {
     const int K = plan.size(w), t0 = plan.start(w);
     const unsigned grid = win_grid(c);
-    if (a.mode == MDR_ACT_BANGBANG)
+    if (xpart) {  // the STATS instantiations (untouched kernels), their block partials into d_wstat
+      if (int rc = mdr_window_stats_check(c->kp.n, dev_bytes(c->d_wstat))) return rc;
+      if (a.mode == MDR_ACT_BANGBANG)
+        hipLaunchKernelGGL((k_step_closed<kActBangBang, kWinHpt, true, false, double*>), dim3(grid), dim3(256), 0, st,
+                           c->kp, (const TickArgs*)(c->d_ticks + t0), K, a.rew_row(t0), a.rew_stride, slot(w),
+                           c->d_wstat.get());
+      else
+        hipLaunchKernelGGL((k_step_closed<kActDeadband, kWinHpt, true, false, double*>), dim3(grid), dim3(256), 0, st,
+                           c->kp, (const TickArgs*)(c->d_ticks + t0), K, a.rew_row(t0), a.rew_stride, slot(w),
+                           c->d_wstat.get());
+    } else if (a.mode == MDR_ACT_BANGBANG)
       hipLaunchKernelGGL((k_step_closed<kActBangBang, kWinHpt, false, false>), dim3(grid), dim3(256), 0, st, c->kp,
                          (const TickArgs*)(c->d_ticks + t0), K, a.rew_row(t0), a.rew_stride, slot(w));
     else
@@ -1473,6 +1486,16 @@ struct ClosedShardSeq {
   int sum(int w, hipStream_t st) const {
     hipLaunchKernelGGL(k_win_shard_sum, dim3(plan.size(w)), dim3(64 * c->kp.n_cap), 0, st, c->kp, slot(w));
     LAUNCH_CHECK("k_win_shard_sum");
+    return MDR_OK;
+  }
+  // the window's partial stats rows, behind sum(w) on its stream and BEFORE allreduce(w) rewrites red
+  // in place with the cluster's totals (a no-op without rows)
+  int part(int w, hipStream_t st) const {
+    if (!xpart) return MDR_OK;
+    hipLaunchKernelGGL(k_closed_stats_part, dim3(plan.size(w)), dim3(kTickBlock), 0, st, c->kp,
+                       (const double*)c->d_wstat.get(), (int)win_grid(c),
+                       (const unsigned long long*)win_red_ptr(c, slot(w)), xpart + (size_t)plan.start(w) * kTickRow);
+    LAUNCH_CHECK("k_closed_stats_part");
     return MDR_OK;
   }
   // the window's allreduce and reward finish, both ordered on st
@@ -1489,12 +1512,13 @@ struct ClosedShardSeq {
 };
 
 // one stream: step -> sum -> allreduce -> finish per window
-static int closed_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
-  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
+static int closed_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* xpart = nullptr) {
+  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win), xpart};
   SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
   for (int w = 0; w < s.plan.count(); ++w) {
     if (int rc = s.step(w, st)) return rc;
     if (int rc = s.sum(w, st)) return rc;
+    if (int rc = s.part(w, st)) return rc;
     if (s.finished(w))
       if (int rc = s.reduce_finish(w, st)) return rc;
   }
@@ -1512,8 +1536,10 @@ static int closed_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t s
 // (One shared row has a single allreduce and finish, behind the last step: nothing to run beside
 // them, and the two stream hand-offs measured 8 % of a 1M-house call — mdr_rollout_sharded sends it
 // to closed_sharded_serial.)
-static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
-  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win)};
+// With stats rows, part(w) sits on the compute stream behind sum(w) and before ev_k1[w]: it has read
+// red before allreduce(w) starts, and d_wstat before step(w + 1) rewrites it.
+static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* xpart = nullptr) {
+  const ClosedShardSeq s{c, a, WinPlan(a.n, c->win), xpart};
   const int nw = s.plan.count();
   hipStream_t cs = c->comm_stream;
   SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
@@ -1521,6 +1547,7 @@ static int closed_sharded_pipeline(mdr_ctx* c, const RolloutArgs& a, hipStream_t
     if (int rc = s.step(w, st)) return rc;
     if (w >= 3) HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[(w - 3) % kSlabs], 0));
     if (int rc = s.sum(w, st)) return rc;
+    if (int rc = s.part(w, st)) return rc;
     HIP_TRY(hipEventRecord(c->ev_k1[w % kSlabs], st));
     return MDR_OK;
   };
@@ -1543,6 +1570,11 @@ static int launch_tick_stats(mdr_ctx* c, const double* reward, const double* p_d
                              hipStream_t st);
 static int launch_tick_partials(mdr_ctx* c, const double* reward, double* partial, unsigned* nb_out, hipStream_t st);
 static int rows_scratch(mdr_ctx* c);
+// (stats rows on a sharded context, defined with mdr_tick_stats_sharded below)
+static int check_stats_rows(const char* who, int64_t n, int64_t stats_rows, int64_t stats_row0);
+static int stats_exchange_reserve(mdr_ctx* c, int m, const char* who);
+static double* stats_part_rows(mdr_ctx* c, int m, int row);
+static int stats_rows_exchange(mdr_ctx* c, int m, bool closed, double* rows, hipStream_t st);
 
 // The launch sequence of a rollout with staged drivers (d_ticks), so a captured graph is reusable:
 // the window sequence (open-loop sources), the closed-loop window sequence (bang-bang sources under
@@ -2523,9 +2555,12 @@ int rollout_sharded_overlap(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
 }
 
 // Serial sharded ticks on one stream: [phase 1 if needed] -> allreduce(counts) -> k_step.
-int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+// xpart (mdr_rollout_sharded_stats): every tick's P on the device and mdr_tick_stats' two launches
+// behind its step, into this rank's partial row t.
+int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* xpart = nullptr) {
   const TickArgs* ticks = c->d_ticks;
   const int n = a.n, mode = a.mode;
+  double* const p_tick = a.p_out ? a.p_out : c->d_stat_p.get();  // (rows: every tick's P, for its row)
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
   c->v.slabs_zeroed();
   const bool la = lookahead_ok(mode);
@@ -2534,8 +2569,10 @@ int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
       if (int rc = launch_counts(c, a.act_row(t), mode, 0, ticks + t, st)) return rc;
     if (int rc = comm_allreduce(c, slab_at(c, c->v.ring()), c->slab_len, 0, st)) return rc;
     int rc = launch_step(c, a.act_row(t), mode, TickArgs{}, ticks + t, a.rew_row(t), la ? mode : 0, MDR_CTRL_NONE,
-                         nullptr, t == n - 1 ? a.p_out : nullptr, st);
+                         nullptr, xpart ? p_tick : t == n - 1 ? a.p_out : nullptr, st);
     if (rc) return rc;
+    if (xpart)
+      if (int rc2 = launch_tick_stats(c, a.rew_row(t), p_tick, 0.0, xpart + (size_t)t * kTickRow, st)) return rc2;
   }
   return MDR_OK;
 }
@@ -2544,18 +2581,73 @@ int rollout_sharded_serial(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
 
 extern "C" {
 
-int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
-                        int64_t act_stride, int mode, double* reward, int64_t rew_stride, double* p_out,
-                        void* stream) {
+// who writes the stats rows of a sharded rollout from this action source (mdr_rollout_stats_path's
+// answers without its single-shard refusal), or why nobody does
+static int rollout_sharded_stats_path(mdr_ctx* c, int mode, const std::string& who) {
+  if (window_ok(c, mode))
+    return fail(MDR_EARG, who + ": no stats rows from the open-loop window rollout (k_step_window); use the "
+                                "bang-bang sources, or mdr_set_rollout_window(0) for one launch per tick");
+  return closed_ok(c, mode, true) ? MDR_STATS_CLOSED_WINDOWS : MDR_STATS_PER_TICK;
+}
+
+int mdr_rollout_sharded_stats_path(mdr_ctx* c, int mode) {
+  const char* const who = "mdr_rollout_sharded_stats";
+  if (!c) return fail(MDR_EARG, "mdr_rollout_sharded_stats_path: null ctx");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_sharded_stats_path: context not bound");
+  if (!has_comm(c)) return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
+  if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_sharded_stats_path: bad action source");
+  if (win_common(c)) return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
+  return rollout_sharded_stats_path(c, mode, who);
+}
+
+// (stats == nullptr: mdr_rollout_sharded, launch for launch)
+int mdr_rollout_sharded_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
+                              int64_t act_stride, int mode, double* reward, int64_t rew_stride, double* p_out,
+                              double* stats, int64_t stats_rows, int64_t stats_row0, void* stream) {
   const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, p_out};
+  const char* const who = stats ? "mdr_rollout_sharded_stats" : "mdr_rollout_sharded";
+  if (stats)  // (before anything is staged or launched, and before any other answer)
+    if (int rc = check_stats_rows(who, n, stats_rows, stats_row0)) return rc;
   // a single window begun by mdr_rollout_begin on this sharded context (count, allreduce, P-only
   // reduce already issued): only the KA step kernel is left, with these drivers as its arguments.
-  // (Such a call passes every check of the preamble: mdr_rollout_begin made them.)
-  const bool counted = c && ticks && n >= 1 && begun_matches(c, a, ticks, true);
-  if (int rc = rollout_preamble(c, "mdr_rollout_sharded", ticks && reward, a,
-                                (counted ? 0 : kDropBegun) | kShardedOnly | kNoCommon))
+  // (Such a call passes every check of the preamble: mdr_rollout_begin made them.  Never with rows:
+  // the open-loop windows write none.)
+  const bool counted = !stats && c && ticks && n >= 1 && begun_matches(c, a, ticks, true);
+  if (int rc = rollout_preamble(c, who, ticks && reward, a, (counted ? 0 : kDropBegun) | kShardedOnly | kNoCommon))
     return rc;
   hipStream_t st = S(stream);
+  if (stats) {
+    // the partial rows' path and buffers, reserved outside the launch sequence; then the sequence of
+    // mdr_rollout_sharded with the rows' launches in it, and ONE exchange + combine behind it
+    const int path = rollout_sharded_stats_path(c, mode, who);
+    if (path < 0) return path;
+    const bool closed = path == MDR_STATS_CLOSED_WINDOWS;
+    if (int rc = stats_exchange_reserve(c, n, who)) return rc;
+    if (closed) {
+      if (int rc = dev_reserve(c->d_wstat, mdr_window_stats_bytes(c->kp.n) / sizeof(double), "d_wstat")) return rc;
+    } else {
+      if (!p_out)
+        if (int rc = dev_reserve(c->d_stat_p, 1, "d_stat_p")) return rc;
+      if (int rc = tick_scratch(c)) return rc;
+    }
+    Sequence seq(c->v, Sequence::kRollout);
+    int rc = refresh_if_dirty(c, st);
+    if (!rc) rc = stage_ticks(c, n, ticks, st);
+    if (rc) return rc;
+    double* const xpart = stats_part_rows(c, n, 0);
+    if (closed) {
+      rc = wslab_clean(c, st);
+      if (rc) return rc;
+      const bool pipe = c->win_pipe && c->comm_stream && rew_stride != 0;  // (one shared row: one stream)
+      rc = pipe ? closed_sharded_pipeline(c, a, st, xpart) : closed_sharded_serial(c, a, st, xpart);
+    } else {
+      // (never rollout_sharded_overlap: it writes tick t's reward one launch late)
+      rc = rollout_sharded_serial(c, a, st, xpart);
+    }
+    if (!rc) rc = stats_rows_exchange(c, n, closed, stats + (size_t)stats_row0 * kTickRow, st);
+    if (rc) (void)hipMemsetAsync(c->d_xstat, 0, dev_bytes(c->d_xstat), st);  // (the slab's invariant, whatever was written)
+    return seq.end(rc);
+  }
   Sequence seq(c->v, Sequence::kRollout);
   if (counted) {
     c->v.early_consumed();
@@ -2582,6 +2674,13 @@ int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
   const bool can_overlap = lookahead_ok(mode) && rew_stride != 0 && c->comm_stream;
   if (can_overlap && c->tick_overlap) return seq.end(rollout_sharded_overlap(c, a, st));
   return seq.end(rollout_sharded_serial(c, a, st));
+}
+
+int mdr_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action,
+                        int64_t act_stride, int mode, double* reward, int64_t rew_stride, double* p_out,
+                        void* stream) {
+  return mdr_rollout_sharded_stats(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, nullptr, 0, 0,
+                                   stream);
 }
 
 int mdr_rollout_sharded_mode(mdr_ctx* c, int* window_pipeline, int* tick_overlap) {
@@ -3151,6 +3250,131 @@ int mdr_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double
   return launch_tick_stats(c, reward, p_dev, p_host, out16, S(stream));
 }
 
+// ---- stats rows on a house-sharded cluster: the exchange slab, the partial rows
+// and the one exchange + combine per call.  The entry points above keep their single-shard refusals.
+static bool ctx_sharded(const mdr_ctx* c);
+
+// the slab's world and this rank's place in it: the communicator's, or what mdr_stats_exchange_ranks
+// told a shard whose exchanges are driven by the caller
+static int x_world(const mdr_ctx* c) { return has_comm(c) ? c->world : c->x_world > 0 ? c->x_world : 1; }
+static int x_rank(const mdr_ctx* c) { return has_comm(c) ? c->rank : c->x_world > 0 ? c->x_rank : 0; }
+
+static int check_stats_rows(const char* who, int64_t n, int64_t stats_rows, int64_t stats_row0) {
+  if (stats_rows < 0 || stats_row0 < 0 || n < 0 || stats_row0 > stats_rows - n)
+    return fail(MDR_EARG, std::string(who) + ": stats_row0 .. stats_row0 + n_ticks outside [0, stats_rows)");
+  return MDR_OK;
+}
+
+size_t mdr_stats_exchange_bytes(int world, int m) {
+  if (world < 1 || m < 1) return 0;
+  const size_t lim = SIZE_MAX / (sizeof(double) * kTickRow);
+  if ((size_t)world > lim / (size_t)m) return 0;
+  return (size_t)world * (size_t)m * kTickRow * sizeof(double);
+}
+
+// room for an m-row call, grown outside any launch sequence: a queued combine may still read and zero
+// the old slab, so the device is idle before it is freed; a new slab is zero-filled (the invariant)
+static int stats_exchange_reserve(mdr_ctx* c, int m, const char* who) {
+  if (!has_comm(c) && c->x_world < 1 && c->kp.n < c->kp.n_global)
+    return fail(MDR_ESTATE, std::string(who) + ": a shard without a communicator: mdr_stats_exchange_ranks first");
+  const size_t need = mdr_stats_exchange_bytes(x_world(c), m) / sizeof(double);
+  if (!need) return fail(MDR_EARG, std::string(who) + ": m outside 1 .. the exchange slab's limit");
+  if (need <= c->d_xstat.capacity()) return MDR_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  return dev_reserve(c->d_xstat, need, "d_xstat", true);
+}
+
+static double* stats_part_rows(mdr_ctx* c, int m, int row) {
+  return c->d_xstat + ((size_t)x_rank(c) * m + row) * kTickRow;
+}
+
+static int stats_rows_combine(mdr_ctx* c, int m, bool closed, double* rows, hipStream_t st) {
+  if (closed)
+    hipLaunchKernelGGL(k_stats_rows_combine<true>, dim3(m), dim3(64), 0, st, c->kp, c->d_xstat.get(), x_world(c),
+                       x_rank(c), m, (const TickArgs*)c->d_ticks.get(), rows);
+  else
+    hipLaunchKernelGGL(k_stats_rows_combine<false>, dim3(m), dim3(64), 0, st, c->kp, c->d_xstat.get(), x_world(c),
+                       x_rank(c), m, (const TickArgs*)nullptr, rows);
+  LAUNCH_CHECK("k_stats_rows_combine");
+  return MDR_OK;
+}
+
+// ONE in-place double sum-allreduce of the call's world x m x 16 slab (every element has exactly one
+// non-zero contributor: exact in any order), then the rank-order combine
+static int stats_rows_exchange(mdr_ctx* c, int m, bool closed, double* rows, hipStream_t st) {
+  if (int rc = comm_allreduce(c, c->d_xstat.get(), (size_t)x_world(c) * m * kTickRow, 1, st)) return rc;
+  return stats_rows_combine(c, m, closed, rows, st);
+}
+
+int mdr_stats_exchange_ranks(mdr_ctx* c, int world, int rank) {
+  if (!c) return fail(MDR_EARG, "mdr_stats_exchange_ranks: null ctx");
+  if (world < 1) return fail(MDR_EARG, "mdr_stats_exchange_ranks: world < 1");
+  if (rank < 0 || rank >= world) return fail(MDR_EARG, "mdr_stats_exchange_ranks: rank outside [0, world)");
+  if (has_comm(c)) {
+    if (world != c->world || rank != c->rank)
+      return fail(MDR_ESTATE, "mdr_stats_exchange_ranks: the context's communicator has another world / rank");
+    return MDR_OK;
+  }
+  if (world != c->x_world || rank != c->x_rank) {
+    HIP_TRY(hipDeviceSynchronize());  // (another layout: no queued combine may still use the slab)
+    c->d_xstat.reset();
+    c->x_world = world;
+    c->x_rank = rank;
+  }
+  return MDR_OK;
+}
+
+// the checks the three slab entry points share, in the order a call with several faults reports them
+static int check_stats_exchange(mdr_ctx* c, int m, const char* who) {
+  if (!c) return fail(MDR_EARG, std::string(who) + ": null ctx");
+  if (m < 1) return fail(MDR_EARG, std::string(who) + ": m < 1");
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (!ctx_sharded(c))
+    return fail(MDR_ESTATE, std::string(who) + ": neither a communicator nor a shard (single shard: mdr_tick_stats)");
+  return MDR_OK;
+}
+
+int mdr_stats_exchange_buffer(mdr_ctx* c, int m, double** dev_ptr, int64_t* count) {
+  const char* const who = "mdr_stats_exchange_buffer";
+  if (!dev_ptr) return fail(MDR_EARG, std::string(who) + ": null dev_ptr");
+  if (!count) return fail(MDR_EARG, std::string(who) + ": null count");
+  if (int rc = check_stats_exchange(c, m, who)) return rc;
+  if (int rc = stats_exchange_reserve(c, m, who)) return rc;
+  *dev_ptr = c->d_xstat.get();
+  *count = (int64_t)x_world(c) * m * kTickRow;
+  return MDR_OK;
+}
+
+int mdr_tick_stats_sharded(mdr_ctx* c, const double* reward, const double* p_dev, double p_host, int m, int row,
+                           void* stream) {
+  const char* const who = "mdr_tick_stats_sharded";
+  if (m >= 1 && (row < 0 || row >= m)) return fail(MDR_EARG, std::string(who) + ": row outside [0, m)");
+  if (int rc = check_stats_exchange(c, m, who)) return rc;
+  if (int rc = stats_exchange_reserve(c, m, who)) return rc;
+  if (int rc = tick_scratch(c)) return rc;
+  return launch_tick_stats(c, reward, p_dev, p_host, stats_part_rows(c, m, row), S(stream));
+}
+
+static int stats_rows_finish(mdr_ctx* c, int m, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream,
+                             bool exchange, const char* who) {
+  if (int rc = check_stats_rows(who, m, stats_rows, stats_row0)) return rc;
+  if (!stats) return fail(MDR_EARG, std::string(who) + ": null stats");
+  if (int rc = check_stats_exchange(c, m, who)) return rc;
+  if (exchange && !has_comm(c))
+    return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
+  if (int rc = stats_exchange_reserve(c, m, who)) return rc;
+  double* const rows = stats + (size_t)stats_row0 * kTickRow;
+  return exchange ? stats_rows_exchange(c, m, false, rows, S(stream)) : stats_rows_combine(c, m, false, rows, S(stream));
+}
+
+int mdr_stats_rows_combine(mdr_ctx* c, int m, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream) {
+  return stats_rows_finish(c, m, stats, stats_rows, stats_row0, stream, false, "mdr_stats_rows_combine");
+}
+
+int mdr_stats_rows_exchange(mdr_ctx* c, int m, double* stats, int64_t stats_rows, int64_t stats_row0, void* stream) {
+  return stats_rows_finish(c, m, stats, stats_rows, stats_row0, stream, true, "mdr_stats_rows_exchange");
+}
+
 // ---- replay snapshots (mdr.h mdr_snap): argument checks and the k_snap launch
 static int check_snap_struct(const mdr_snap* sn, const char* who) {
   if (sn->struct_bytes != (int32_t)sizeof(mdr_snap))
@@ -3449,9 +3673,11 @@ int mdr_actor_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_
 static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
                                       const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
                                       int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
-                                      const mdr_snap* snap, const mdr_snap_halo* shalo, int row0, void* stream,
-                                      const char* who) {
+                                      const mdr_snap* snap, const mdr_snap_halo* shalo, int row0, double* stats,
+                                      int64_t stats_rows, int64_t stats_row0, void* stream, const char* who) {
   enter_writer(c);
+  if (stats)  // (before anything is staged or launched, and before any other answer)
+    if (int rc = check_stats_rows(who, n, stats_rows, stats_row0)) return rc;
   if (snap)
     if (int rc = check_snap_struct(snap, who)) return rc;
   if (snap && shalo)
@@ -3480,6 +3706,21 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
   if (halo && c->kp.n < (lo > hi ? lo : hi))
     return fail(MDR_EARG, "mdr_actor_rollout_sharded: shard smaller than the ring half-width");
   hipStream_t st = S(stream);
+  if (stats) {  // the exchange slab and k_tick_stats' partials, outside the launch sequence
+    if (int rc = stats_exchange_reserve(c, n, who)) return rc;
+    if (int rc = tick_scratch(c)) return rc;
+  }
+  // tick t's partial row — the state after its step, its reward row (read before a stride-0 buffer is
+  // overwritten by tick t + 1) and P — behind the step on the compute stream, before tick t + 1's
+  // snapshot and actor; one exchange + combine behind the loop (rows_done)
+  auto part_row = [&](int t) -> int {
+    if (!stats) return MDR_OK;
+    return launch_tick_stats(c, reward + (int64_t)t * rew_stride, p_dev, 0.0, stats_part_rows(c, n, t), st);
+  };
+  auto rows_done = [&]() -> int {
+    if (!stats) return MDR_OK;
+    return stats_rows_exchange(c, n, false, stats + (size_t)stats_row0 * kTickRow, st);
+  };
   Sequence seq(c->v, Sequence::kRollout);
   if (int rc = refresh_if_dirty(c, st)) return rc;
   if (int rc = stage_ticks(c, n, ticks, st)) return rc;
@@ -3541,8 +3782,9 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
                                   buf(t + 1), buf(t + 2), 0, st))
         return rc;
       c->v.step_issued(false, false, /*keep_ring=*/true);  // (d_c5's own ring of 3)
+      if (int rc = part_row(t)) return rc;
     }
-    return seq.ok();
+    return seq.end(rows_done());
   }
   HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
   c->v.slabs_zeroed();
@@ -3590,8 +3832,9 @@ static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, 
     if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
                              reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, st))
       return rc;
+    if (int rc = part_row(t)) return rc;
   }
-  return seq.ok();
+  return seq.end(rows_done());
 }
 
 int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -3599,7 +3842,7 @@ int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const md
                               int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                               void* stream) {
   return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
-                                    p_dev, nullptr, nullptr, 0, stream, "mdr_actor_rollout_sharded");
+                                    p_dev, nullptr, nullptr, 0, nullptr, 0, 0, stream, "mdr_actor_rollout_sharded");
 }
 
 int mdr_actor_rollout_sharded_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -3607,8 +3850,20 @@ int mdr_actor_rollout_sharded_snap(mdr_ctx* c, int n, const mdr_tick* ticks, con
                                    int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                                    const mdr_snap* snap, const mdr_snap_halo* halo, int row0, void* stream) {
   return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
-                                    p_dev, snap, halo, row0, stream,
+                                    p_dev, snap, halo, row0, nullptr, 0, 0, stream,
                                     snap ? "mdr_actor_rollout_sharded_snap" : "mdr_actor_rollout_sharded");
+}
+
+int mdr_actor_rollout_sharded_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
+                                    const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
+                                    int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
+                                    const mdr_snap* snap, const mdr_snap_halo* halo, int row0, double* stats,
+                                    int64_t stats_rows, int64_t stats_row0, void* stream) {
+  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
+                                    p_dev, snap, halo, row0, stats, stats_rows, stats_row0, stream,
+                                    stats  ? "mdr_actor_rollout_sharded_stats"
+                                    : snap ? "mdr_actor_rollout_sharded_snap"
+                                           : "mdr_actor_rollout_sharded");
 }
 
 }  // extern "C"

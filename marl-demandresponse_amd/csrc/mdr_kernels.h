@@ -278,6 +278,16 @@ __global__ void k_tick_rows_finish(const double* part, int nblk, const double* p
 // the stats rows of a closed-loop window (mdr_rollout_stats): one block of kTickBlock threads per
 // tick, from k_step_closed<..., true>'s block partials and the window slot's counts and records
 __global__ void k_closed_stats(KParams p, const double* wstat, int nblk, unsigned long long* slot, double* rows);
+// stats rows of a house-sharded cluster: a rank's partial rows of a STATS window (grid K, kTickBlock
+// threads; red: the slot's class totals of THIS rank, before their allreduce) ...
+__global__ void k_closed_stats_part(KParams p, const double* wstat, int nblk, const unsigned long long* red,
+                                    double* rows);
+// ... and the rank-order combine of the allreduced exchange slab X[world][m][kTickRow] into the
+// caller's rows (grid m, 64 threads; CLOSED: k_closed_stats_part's partial rows, tkp the call's m
+// staged ticks), which zeroes the slab again
+template <bool CLOSED>
+__global__ void k_stats_rows_combine(KParams p, double* X, int world, int rank, int m, const TickArgs* tkp,
+                                     double* rows);
 __global__ void k_obs(KParams p, ObsArgs o, const double* p_dev, float* obs);
 __global__ void k_halo_pack(KParams p, ObsArgs o, int lo, int hi, float* out);
 __global__ void k_halo_step_pack(KParams p, ObsArgs o, const uint8_t* action, const TickArgs* tkp, int lo, int hi,

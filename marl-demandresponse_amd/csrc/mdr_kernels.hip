@@ -2859,6 +2859,97 @@ __global__ void __launch_bounds__(kTickBlock) k_closed_stats(KParams p, const do
   }
 }
 
+// ---- stats rows of a house-sharded cluster ------------------------------------
+// A rank's partial row of a STATS window on a sharded context (behind k_step_closed<..., true> and
+// k_win_shard_sum, BEFORE the allreduce that rewrites `red` in place with the cluster's totals): block
+// j reduces tick j's block partials in k_closed_stats' order and writes, into this rank's part of the
+// exchange slab, [0..11] raw (slot 4 = S = sum_i pen_i of the rank) and [12..15] the rank's ON totals
+// per capacity class as doubles (exact integers; a class past n_cap: 0).
+__global__ void __launch_bounds__(kTickBlock) k_closed_stats_part(KParams p, const double* __restrict__ wstat, int nblk,
+                                                                  const unsigned long long* __restrict__ red,
+                                                                  double* __restrict__ rows) {
+  __shared__ double sh[kStats][4];
+  const int j = blockIdx.x, ncap = p.n_cap;
+  double a[kStats];
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+  const double* part = wstat + (size_t)j * nblk * kStats;
+  for (int b = threadIdx.x; b < nblk; b += kTickBlock)
+#pragma unroll
+    for (int k = 0; k < kStats; ++k) {
+      const double o = part[(size_t)b * kStats + k];
+      a[k] = k == 2 ? fmax(a[k], o) : a[k] + o;
+    }
+  const double v = tick_block_reduce(a, sh);
+  double* row = rows + (size_t)j * kTickRow;
+  const int k = threadIdx.x;
+  if (k < kStats) {
+    row[k] = v;
+  } else if (k < kTickRow) {
+    const int c = k - kStats;
+    row[k] = c < ncap ? (double)red[j * ncap + c] : 0.0;
+  }
+}
+
+// The ranks' partial rows of a call of m ticks, X[world][m][kTickRow], after ONE in-place double
+// sum-allreduce of the whole slab: rank r wrote only X[r] and the rest was zero, so every element had
+// one non-zero addend and the sum is exact whatever the collective's order.  Block t combines row t in
+// RANK order — slot 2 by fmax, the other eleven by + — so every rank and every communicator forms the
+// same bits; then it zeroes every rank's slot of the row, which restores the slab's invariant (all
+// zero between calls) without a memset.  CLOSED = false (per-tick partial rows, k_tick_stats_finish's):
+// [12] = P from this rank's own slot (the device scalar is global already).  CLOSED = true
+// (k_closed_stats_part's): [12..15] are the ranks' class totals; their sums are exact integers, P is
+// win_power over them, the signal term k_closed_reward_sharded's -win_nsig(P, s_prev of the staged
+// tick), and [4] k_closed_stats' expression over S = the ranks' S in rank order with N = n_global.
+template <bool CLOSED>
+__global__ void __launch_bounds__(64) k_stats_rows_combine(KParams p, double* __restrict__ X, int world, int rank, int m,
+                                                           const TickArgs* __restrict__ tkp, double* __restrict__ rows) {
+  const int t = blockIdx.x, k = threadIdx.x;
+  const size_t rs = (size_t)m * kTickRow;  // doubles between two ranks' rows of a tick
+  double* const x = X + (size_t)t * kTickRow;
+  double out = 0.0;
+  if (k < kStats) {
+    double v = x[k];
+    for (int r = 1; r < world; ++r) {
+      const double o = x[(size_t)r * rs + k];
+      v = k == 2 ? fmax(v, o) : v + o;
+    }
+    out = v;
+  }
+  if (CLOSED) {
+    if (k == 4 || k == kStats) {
+      const int ncap = p.n_cap;
+      unsigned long long cnt[kWinCap];
+      double p_on[kWinCap];
+#pragma unroll
+      for (int c = 0; c < kWinCap; ++c) {
+        double tot = 0.0;
+        if (c < ncap)
+          for (int r = 0; r < world; ++r) tot += x[(size_t)r * rs + kStats + c];
+        cnt[c] = (unsigned long long)tot;
+        p_on[c] = p.p_on[c < ncap ? c : 0];
+      }
+      const double P = win_power(p, cnt, p_on);
+      if (k == 4) {
+        const double sig = -win_nsig(p, P, tkp[t].s_prev);
+        const double tp = p.alpha_temp * out;
+        out = -(((p.norm_temp == 1.0 ? tp : tp / p.norm_temp) + (double)p.n_global * sig) / (double)p.n_global);
+      } else {
+        out = P;
+      }
+    }
+    __syncthreads();  // (threads 4 and 12 have read the class totals that threads 12..15 zero below)
+  } else if (k == kStats) {
+    out = x[(size_t)rank * rs + k];
+  }
+  if (k < kTickRow) {
+    rows[(size_t)t * kTickRow + k] = out;
+    for (int r = 0; r < world; ++r) x[(size_t)r * rs + k] = 0.0;
+  }
+}
+template __global__ void k_stats_rows_combine<false>(KParams, double*, int, int, int, const TickArgs*, double*);
+template __global__ void k_stats_rows_combine<true>(KParams, double*, int, int, int, const TickArgs*, double*);
+
 // --------------------------------------------------------------------------------------- population
 // Synthetic population: the reference noise model (building.py:224-267, hvac.py:66-70) drawn
 // from Philox4x32-10 keyed by (seed, global house id) — identical for any sharding.

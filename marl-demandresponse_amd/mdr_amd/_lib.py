@@ -219,6 +219,16 @@ SIGNATURES = {
     "mdr_comm_host": (I, [VP, I, I, VP, VP, VP]),
     "mdr_rollout_sharded": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP]),
     "mdr_rollout_sharded_mode": (I, [VP, P(I), P(I)]),
+    "mdr_stats_exchange_bytes": (C.c_size_t, [I, I]),
+    "mdr_stats_exchange_ranks": (I, [VP, I, I]),
+    "mdr_stats_exchange_buffer": (I, [VP, I, P(VP), P(I64)]),
+    "mdr_tick_stats_sharded": (I, [VP, VP, VP, D, I, I, VP]),
+    "mdr_stats_rows_combine": (I, [VP, I, VP, I64, I64, VP]),
+    "mdr_stats_rows_exchange": (I, [VP, I, VP, I64, I64, VP]),
+    "mdr_rollout_sharded_stats": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP, I64, I64, VP]),
+    "mdr_rollout_sharded_stats_path": (I, [VP, I]),
+    "mdr_actor_rollout_sharded_stats": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64, VP, I64, VP,
+                                            P(mdr_snap), P(mdr_snap_halo), I, VP, I64, I64, VP]),
     "mdr_probe_stream": (I, [VP, VP, VP]),
     "mdr_div_check": (I, [VP, VP, I64, VP, VP]),
     "mdr_event_record": (I, [VP, I, VP]),

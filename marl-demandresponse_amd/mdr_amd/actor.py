@@ -216,7 +216,11 @@ class DeviceActor:
         ``stats`` (mdr_amd.services.RolloutStats; combinable with ``store``): each tick's cluster
         statistics of the post-step state, its rewards and the cluster power are appended to it as one
         row, written by two more kernels after the tick's step inside the same graph
-        (mdr_actor_rollout_stats; the common penalty modes: mdr_tick_stats after each step_tensor)."""
+        (mdr_actor_rollout_stats; the common penalty modes: mdr_tick_stats after each step_tensor).
+        On a sharded environment ``stats`` is a ``services.ShardedRolloutStats``: a native comm writes
+        each tick's partial row inside the C loop and exchanges the call's rows once behind it
+        (mdr_actor_rollout_sharded_stats, with or without a sharded store); ``TorchComm`` and the common
+        penalty modes write them per tick (mdr_tick_stats_sharded) with one exchange at the end."""
         torch = _torch()
         env = self.env
         sh = env.shard
@@ -235,12 +239,14 @@ class DeviceActor:
             # (a store without probability rows, replay.ReplayStore: probs stays None)
             rewards, actions, probs = (None if x is None else x[row0:row0 + n_ticks]
                                        for x in (store.rewards, store.actions, store.probs))
-        if sh.penalty_mode != 0 or (env.world > 1 and not getattr(env._comm, "native", False)):
+        sharded_rows = bool(getattr(stats, "sharded", False))  # (services.ShardedRolloutStats)
+        if sh.penalty_mode != 0 or ((env.world > 1 or sharded_rows) and not getattr(env._comm, "native", False)):
             return self._rollout_stepwise(n_ticks, rewards, actions, probs, store, stats)
         # (a sharded store at world 1, RCCL to self: the C loop records its halo rows)
-        sharded = env.world > 1 or (store is not None and getattr(store, "sharded", False))
-        if sharded and stats is not None:
-            raise ValueError("stats rows are single-shard: a sharded environment has no stats= rollouts")
+        sharded = env.world > 1 or (store is not None and getattr(store, "sharded", False)) or sharded_rows
+        if sharded and stats is not None and not sharded_rows:
+            raise ValueError("stats rows are single-shard: a sharded environment takes "
+                             "services.ShardedRolloutStats (rollout_stats_for)")
         spec, _sc, keep = env.bound_obs_spec() if not sharded else (env.obs_spec(), None, [])
         self._check_obs(spec)
         n = env.n_local
@@ -264,7 +270,16 @@ class DeviceActor:
             osc[1:, 2] = ticks.solar[:-1]
             osc[:, 3] = ticks.t_od_prev
             sl = (lambda x, st: None if x is None else (x[done:done + k] if st else x))
-            if sharded and store is not None:  # ... and the tick's state, scalars and halo rows
+            if sharded and stats is not None:  # ... and the ranks' partial rows, one exchange behind the loop
+                if done == 0:
+                    stats.record_power(srow0)
+                st_sh = store is not None and getattr(store, "sharded", False)
+                sh.actor_rollout_sharded_stats(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
+                                               sl(rewards, rs), rs, store.snap if store is not None else None,
+                                               store.halo if st_sh else None, row0 + done, stats.stats, srow0 + done)
+                if store is not None:
+                    store.commit_rows(k)
+            elif sharded and store is not None:  # ... and the tick's state, scalars and halo rows
                 sh.actor_rollout_sharded_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
                                               sl(rewards, rs), rs, store.snap, store.halo, row0 + done)
                 store.commit_rows(k)
@@ -315,20 +330,33 @@ class DeviceActor:
             rewards = torch.empty((n_ticks, n), dtype=torch.float64, device=sh.device)
         a_tmp = torch.empty(n, dtype=torch.uint8, device=sh.device)
         p_tmp = torch.empty(n, dtype=torch.float32, device=sh.device)
-        for t in range(n_ticks):
-            a = a_tmp if actions is None else (actions[t] if actions.dim() == 2 else actions)
-            p = p_tmp if probs is None else (probs[t] if probs.dim() == 2 else probs)
-            if store is not None:
-                env.snapshot(store)
-            if stats is not None:
-                if t == 0:
-                    stats.record_power(stats.rows)
-                s_prev, od = env.power_grid.current_signal, env.current_od_temp
-            self.select_actions(action=a, prob=p, count_next=True)
-            r = env.step_tensor(a, rewards=rewards[t] if rewards.dim() == 2 else rewards)
-            if stats is not None:
-                sh.tick_stats(r, stats.stats[stats.begin_rows(1)])
-                stats.commit_rows([s_prev], [od], [env.power_grid.current_signal], first=(t == 0))
+        sharded_rows = bool(getattr(stats, "sharded", False))  # (services.ShardedRolloutStats)
+        if sharded_rows:  # this rank's partial rows tick by tick, one exchange behind the loop
+            stats.begin_partial(n_ticks)
+        try:
+            for t in range(n_ticks):
+                a = a_tmp if actions is None else (actions[t] if actions.dim() == 2 else actions)
+                p = p_tmp if probs is None else (probs[t] if probs.dim() == 2 else probs)
+                if store is not None:
+                    env.snapshot(store)
+                if stats is not None:
+                    if t == 0:
+                        stats.record_power(stats.rows)
+                    s_prev, od = env.power_grid.current_signal, env.current_od_temp
+                self.select_actions(action=a, prob=p, count_next=True)
+                r = env.step_tensor(a, rewards=rewards[t] if rewards.dim() == 2 else rewards)
+                if stats is not None:
+                    if sharded_rows:
+                        stats.partial_row(r, t)
+                    else:
+                        sh.tick_stats(r, stats.stats[stats.begin_rows(1)])
+                    stats.commit_rows([s_prev], [od], [env.power_grid.current_signal], first=(t == 0))
+        except BaseException:
+            if sharded_rows:
+                stats.abort()
+            raise
+        if sharded_rows:
+            stats.exchange()
         return rewards
 
 

@@ -88,8 +88,16 @@ class RcclComm:
                 "allgather")
         return out
 
-    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride) -> None:
+    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride, stats=None, row0: int = 0) -> None:
+        """``stats`` (services.ShardedRolloutStats): tick t's row into ``stats.stats[row0 + t]``, the
+        ranks' partial rows exchanged once behind the call (mdr_rollout_sharded_stats)."""
         n = shard.n
+        if stats is not None:
+            L.check(shard.lib.mdr_rollout_sharded_stats(
+                shard.ctx, len(ticks), ticks.ptr(), L.ptr(actions), n if actions is not None else 0, mode,
+                L.ptr(rewards), rew_stride, L.ptr(shard.p_dev), L.ptr(stats.stats), int(stats.stats.shape[0]),
+                int(row0), shard.stream()), "mdr_rollout_sharded_stats")
+            return
         L.check(shard.lib.mdr_rollout_sharded(shard.ctx, len(ticks), ticks.ptr(), L.ptr(actions),
                                               n if actions is not None else 0, mode, L.ptr(rewards),
                                               rew_stride, L.ptr(shard.p_dev), shard.stream()),
@@ -241,13 +249,29 @@ class TorchComm(RcclComm):
             r.wait()
         return recv.to(shard.device) if host else recv
 
-    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride) -> None:
-        for t in range(len(ticks)):
-            tk = ticks.struct(t)
-            a = actions[t] if actions is not None else None
-            shard.power_counts(a, mode, tk.tick)
-            self.allreduce_counts(shard)
-            shard.step(a, mode, tk, reward=rewards[t] if rew_stride else rewards)
+    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride, stats=None, row0: int = 0) -> None:
+        """``stats`` (services.ShardedRolloutStats): each tick's partial row behind its step, then one
+        ``allreduce_sum`` of the exchange slab and the combine into ``stats.stats[row0 ...]``."""
+        m = len(ticks)
+        if stats is not None:
+            shard.stats_exchange_ranks(self.world, self.rank)
+            slab = shard.stats_exchange_buffer(m)
+        try:
+            for t in range(m):
+                tk = ticks.struct(t)
+                a = actions[t] if actions is not None else None
+                shard.power_counts(a, mode, tk.tick)
+                self.allreduce_counts(shard)
+                r = shard.step(a, mode, tk, reward=rewards[t] if rew_stride else rewards)
+                if stats is not None:
+                    shard.tick_stats_sharded(r, m, t)
+        except BaseException:
+            if stats is not None:
+                slab.zero_()  # (the slab's invariant: all zero between calls)
+            raise
+        if stats is not None:
+            self.allreduce_sum(shard, slab)
+            shard.stats_rows_combine(m, stats.stats, row0)
 
 
 class HostComm(TorchComm):
@@ -304,14 +328,18 @@ class HostComm(TorchComm):
                 self.error = e
                 return -1
 
-        self._cbs = (L.HOST_ALLREDUCE_FN(allreduce), L.HOST_SENDRECV_FN(sendrecv))  # (kept alive)
+        # The callbacks live as long as the context that holds their addresses: on the SHARD.  (Their
+        # closures capture that shard's device.  Kept on the comm, a second shard attached to it — an
+        # env's deep copy shares its comm — replaced them and freed the first shard's while its context
+        # still called them.)
+        cbs = (L.HOST_ALLREDUCE_FN(allreduce), L.HOST_SENDRECV_FN(sendrecv))
         self.error = None
-        L.check(shard.lib.mdr_comm_host(shard.ctx, self.world, self.rank, self._cbs[0], self._cbs[1], None),
-                "mdr_comm_host")
+        L.check(shard.lib.mdr_comm_host(shard.ctx, self.world, self.rank, cbs[0], cbs[1], None), "mdr_comm_host")
+        shard._host_cbs = cbs
         shard._host_comm = self
 
-    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride) -> None:
-        RcclComm.rollout(self, shard, ticks, actions, mode, rewards, rew_stride)
+    def rollout(self, shard, ticks, actions, mode, rewards, rew_stride, stats=None, row0: int = 0) -> None:
+        RcclComm.rollout(self, shard, ticks, actions, mode, rewards, rew_stride, stats, row0)
 
     def pipeline(self, shard) -> dict:
         return RcclComm.pipeline(self, shard)

@@ -618,7 +618,11 @@ class Environment:
         (k_step_closed<..., STATS> + k_closed_stats; individual_L2 only), or by mdr_tick_stats' kernels
         behind every tick where the call runs one launch per tick.  The open-loop window rollout (random / always_on /
         buffer with the window on) writes no rows: ``NotImplementedError``.  ``ValueError``: rows of
-        another env, or more ticks than the rows left."""
+        another env, or more ticks than the rows left.  Sharded: ``stats`` is a
+        ``services.ShardedRolloutStats`` — every rank's partial rows of a driver window are exchanged
+        once behind it (native comms: mdr_rollout_sharded_stats, the closed-loop windows or one launch
+        per tick as mdr_rollout_sharded_stats_path says; ``TorchComm``: mdr_tick_stats_sharded per
+        tick, one ``allreduce_sum`` of the slab, mdr_stats_rows_combine)."""
         import torch
 
         sh = self._shard
@@ -627,12 +631,18 @@ class Environment:
             raise NotImplementedError("sharded rollout supports individual_L2; use step_tensor for common penalties")
         mode = ACTION_MODES[action_mode]
         srow0 = 0
+        sharded_rows = bool(getattr(stats, "sharded", False))  # (services.ShardedRolloutStats)
         if stats is not None:
             if stats.env is not self:
                 raise ValueError("the stats rows belong to another environment")
+            if sharded_rows and self._comm is None:
+                raise ValueError("ShardedRolloutStats rows on an environment without a communicator")
             srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
             try:  # which launch sequence would write the rows; nothing is launched
-                sh.rollout_stats_path(mode)
+                if not sharded_rows:
+                    sh.rollout_stats_path(mode)
+                elif getattr(self._comm, "native", False):
+                    sh.rollout_sharded_stats_path(mode)
             except L.MdrError as e:
                 if "MDR_EARG" in str(e):
                     raise NotImplementedError(str(e)) from None
@@ -671,7 +681,13 @@ class Environment:
             whole = done == 0 and k == n_ticks  # one window: the caller's buffers as they are
             a = None if actions is None else (actions if whole and actions.shape[0] == k else actions[done:done + k])
             r = rewards[done:done + k] if rew_stride and not (whole and rewards.shape[0] == k) else rewards
-            if self._comm is not None:
+            if self._comm is not None and sharded_rows:
+                # the ranks' partial rows of this driver window, one exchange behind it (native comms:
+                # mdr_rollout_sharded_stats; TorchComm: per tick, then allreduce_sum + the combine)
+                if done == 0:
+                    stats.record_power(srow0)
+                self._comm.rollout(sh, ticks, a, mode, r, rew_stride, stats=stats, row0=srow0 + done)
+            elif self._comm is not None:
                 self._comm.rollout(sh, ticks, a, mode, r, rew_stride)
             else:
                 # graphs are cached per (length, buffers): shorter windows only reuse them on 1-D rewards
@@ -705,17 +721,25 @@ class Environment:
         finish launch per 32 ticks), bit for bit ``shard.tick_stats`` after every tick of the
         per-tick loop, which is what the per-tick fallback here does.  ``ValueError``: rows of
         another env, or more ticks than the rows left; a context with a communicator is refused
-        (MdrError) before the drivers advance."""
+        (MdrError) before the drivers advance, unless ``stats`` is a ``services.ShardedRolloutStats``:
+        then the per-tick loop writes each rank's partial rows and one exchange behind it combines them
+        (mdr_greedy_rollout at world > 1 stays out)."""
         import torch
 
         sh = self._shard
         n = self._n_local
         srow0 = 0
+        sharded_rows = bool(getattr(stats, "sharded", False))  # (services.ShardedRolloutStats)
         if stats is not None:
             if stats.env is not self:
                 raise ValueError("the stats rows belong to another environment")
-            srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
-            sh.greedy_rollout_stats_check()  # (MdrError: a communicator; nothing is launched)
+            if sharded_rows:
+                if self._comm is None:
+                    raise ValueError("ShardedRolloutStats rows on an environment without a communicator")
+                srow0 = stats.begin_partial(n_ticks)  # (ValueError: overflow)
+            else:
+                srow0 = stats.begin_rows(n_ticks)  # (ValueError: overflow)
+                sh.greedy_rollout_stats_check()  # (MdrError: a communicator; nothing is launched)
         if actions is None:
             actions = torch.empty(n, dtype=torch.uint8, device=sh.device)
         if rewards is None:
@@ -727,18 +751,28 @@ class Environment:
         a_st = n if actions.dim() == 2 else 0
         r_st = n if rewards.dim() == 2 else 0
         if (self.world > 1 or (self._gq_force_sharded and self._comm is not None) or self._links is None
-                or self._grid_pending):
-            for t in range(n_ticks):
-                a = actions[t] if a_st else actions
-                if stats is not None:
-                    if t == 0:
-                        stats.record_power(srow0)
-                    s_prev, od = self.power_grid.current_signal, self.current_od_temp
-                self.greedy_actions(out=a)
-                r = self.step_tensor(a, rewards=rewards[t] if r_st else rewards, ctrl="greedy_keys")
-                if stats is not None:
-                    sh.tick_stats(r, stats.stats[srow0 + t])
-                    stats.commit_rows([s_prev], [od], [self.power_grid.current_signal], first=(t == 0))
+                or self._grid_pending or sharded_rows):
+            try:
+                for t in range(n_ticks):
+                    a = actions[t] if a_st else actions
+                    if stats is not None:
+                        if t == 0:
+                            stats.record_power(srow0)
+                        s_prev, od = self.power_grid.current_signal, self.current_od_temp
+                    self.greedy_actions(out=a)
+                    r = self.step_tensor(a, rewards=rewards[t] if r_st else rewards, ctrl="greedy_keys")
+                    if stats is not None:
+                        if sharded_rows:  # this rank's partial row; one exchange behind the loop
+                            stats.partial_row(r, t)
+                        else:
+                            sh.tick_stats(r, stats.stats[srow0 + t])
+                        stats.commit_rows([s_prev], [od], [self.power_grid.current_signal], first=(t == 0))
+            except BaseException:
+                if sharded_rows:
+                    stats.abort()
+                raise
+            if sharded_rows:
+                stats.exchange()
             return actions, rewards
         done = 0
         while done < n_ticks:  # one window unless interpolation ends it early (driver_window)

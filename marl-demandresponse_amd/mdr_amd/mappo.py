@@ -26,8 +26,9 @@ Categorical RNG.
 On a house-sharded ``neighbours`` environment ``collect`` / ``update`` train one policy from the
 cluster's buffer: every rank builds the agent with the same seed, stores its own houses' transitions
 and ring halos, and per minibatch contributes the rows it owns to one integer allreduce, after which
-every rank takes the identical optimiser step (``DeviceMAPPO.update``; ``evaluate`` and
-``collect(metrics=...)`` stay single-shard).
+every rank takes the identical optimiser step (``DeviceMAPPO.update``).  ``evaluate`` and
+``collect(metrics=...)`` are collective calls there: their stats rows are
+``services.ShardedRolloutStats``', combined over the ranks once per call.
 """
 from __future__ import annotations
 
@@ -253,7 +254,7 @@ class DeviceMAPPO:
 
         ``metrics`` (mdr_amd.services.DeviceMetrics): the ticks also feed it as
         ``metrics_service.update`` does every step (training_manager.py:242-245) — their stats rows
-        are written inside the same graph (``self.stats``, a RolloutStats of the store's capacity)
+        are written inside the same graph (``self.stats``, ``rollout_stats_for`` the store's capacity)
         and accumulated by one ``update_rollout`` as time steps ``time_step0`` .. (default: the
         ticks collected so far)."""
         if self.store is None:
@@ -263,9 +264,9 @@ class DeviceMAPPO:
         stats = None
         if metrics is not None:
             if self.stats is None:
-                from .services import RolloutStats
+                from .services import rollout_stats_for
 
-                self.stats = RolloutStats(self.env, self.store.capacity)
+                self.stats = rollout_stats_for(self.env, self.store.capacity)
             stats = self.stats
             stats.clear()
         r = self.device_actor.rollout(n_ticks, store=self.store, stats=stats)
@@ -292,10 +293,11 @@ class DeviceMAPPO:
           "Test mean signal error"       sum_t N |s_post - P_post| / N^2 / T
 
         The training env's device state, tick, date, P, graphs and packed weights are not touched.
+        On a sharded env the call is collective and every rank returns the same means.
         ``return_actions``: also the ticks' actions, uint8 [n_ticks, n_local]."""
         import copy
 
-        from .services import RolloutStats, evaluation_means
+        from .services import evaluation_means, rollout_stats_for
 
         torch = _torch()
         if n_ticks < 1:
@@ -307,7 +309,7 @@ class DeviceMAPPO:
         kept = self._eval.get(id(ev)) if env is not None else None
         if kept is None or kept["env"] is not ev or kept["stats"].capacity < n_ticks:
             kept = {"env": ev, "actor": DeviceActor(ev, self.actor_net, precision=self.device_actor.precision),
-                    "stats": RolloutStats(ev, n_ticks),
+                    "stats": rollout_stats_for(ev, n_ticks),
                     "rewards": torch.empty(ev.n_local, dtype=torch.float64, device=ev.shard.device), "actions": None}
             if env is not None:
                 self._eval[id(ev)] = kept

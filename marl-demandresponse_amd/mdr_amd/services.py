@@ -10,6 +10,8 @@ per-house UI list is materialised only when read.
   DeviceMetrics  Metrics               server/app/services/metrics_service.py:71-257
   RolloutStats   (the obs dicts Metrics.update and TrainingManager.test read, as one device row per
                  tick written inside a rollout: ``mdr_tick_stats``)  training_manager.py:242-245,265-295
+  ShardedRolloutStats  the same rows on a house-sharded env: the ranks' partial rows of a call, combined by one
+                 exact exchange behind it (``rollout_stats_for(env, cap)`` picks the class)
   UISummary      ClientManagerService  server/app/services/client_manager_service.py:12-245
   ServerLoop     ControllerManager     server/app/services/controller_manager.py:93-260
   evaluate_controller  TrainingManager.test for the bang-bang and greedy-myopic baselines
@@ -81,7 +83,7 @@ class RolloutStats:
     already knows — the pre-step ``reg_signal`` and ``OD_temp`` — and the post-step signal.  The
     pre-step cluster power of a call's first tick is copied on the device, without a
     synchronisation, from the env's ``P`` scalar; every later tick's is the previous row's slot 12.
-    One shard only (a row sums the shard's own houses)."""
+    One shard only (a row sums the shard's own houses); a sharded environment: ``ShardedRolloutStats``."""
 
     def __init__(self, env, capacity_ticks: int):
         import torch
@@ -91,6 +93,11 @@ class RolloutStats:
         if env.world > 1:
             raise ValueError("RolloutStats: sharded environments are not supported (a row sums this "
                              "shard's houses only)")
+        self._alloc(env, capacity_ticks)
+
+    def _alloc(self, env, capacity_ticks: int) -> None:
+        import torch
+
         self.env = env
         cap = self.capacity = int(capacity_ticks)
         # one allocation, one download: [cap, 16] rows, then the cap pre-step powers
@@ -150,6 +157,75 @@ class RolloutStats:
         self.host()
         return {"reg_signal": np.asarray(self.reg_signal, np.float64), "OD_temp": np.asarray(self.od_temp, np.float64),
                 "cluster_hvac_power": self._host[1], "signal_post": np.asarray(self.signal_post, np.float64)}
+
+
+class ShardedRolloutStats(RolloutStats):
+    """``RolloutStats`` of a house-sharded environment (``world > 1``, or any env with a communicator):
+    the same ``[capacity, 16]`` tensor and host scalars, on every rank.  During a call of m ticks each
+    rank writes PARTIAL rows — its own houses' sums with N = the cluster's size — into its part of the
+    context's exchange slab X[world][m][16]; behind the call ONE double sum-allreduce of the slab (every
+    element has exactly one non-zero contributor: exact whatever the collective does) and one combine
+    kernel, adding the ranks in rank order (slot 2: max), write the rows.  They are bit-identical on
+    every rank and between communicators, equal to ``RolloutStats``' at world 1, and differ from the
+    single process at world > 1 only by that regrouping of the sum slots.
+
+    Rollouts that take it: ``Environment.rollout`` / ``greedy_rollout``, ``DeviceActor.rollout``; every
+    such call is collective.  ``rollout_stats_for(env, capacity)`` picks this class or ``RolloutStats``."""
+
+    sharded = True  # (what the rollouts ask: partial rows and one exchange, not mdr_tick_stats' rows)
+
+    def __init__(self, env, capacity_ticks: int):
+        if capacity_ticks < 1:
+            raise ValueError("capacity_ticks must be at least 1")
+        comm = getattr(env, "_comm", None)
+        if comm is None or not callable(getattr(comm, "allreduce_sum", None)):
+            raise ValueError("ShardedRolloutStats: the rows of a sharded environment are summed over its ranks; "
+                             "its communicator needs a callable allreduce_sum (mdr_amd.distributed.make_comm)")
+        self._alloc(env, capacity_ticks)
+        self._call = None  # (m, first row) of the per-tick call whose partial rows are being written
+
+    # ---- calls stepped from Python: partial rows tick by tick, then one exchange
+    def _native(self) -> bool:
+        return bool(getattr(self.env._comm, "native", False))
+
+    def begin_partial(self, m: int) -> int:
+        """Start a call of ``m`` ticks whose partial rows ``partial_row`` writes one by one; returns the
+        first row (``begin_rows``: ValueError before anything advances)."""
+        row0 = self.begin_rows(m)
+        sh, comm = self.env.shard, self.env._comm
+        if not self._native():  # the context has no communicator of its own: tell it the slab's layout
+            sh.stats_exchange_ranks(comm.world, comm.rank)
+        self._call = (int(m), row0)
+        return row0
+
+    def partial_row(self, rewards, t: int) -> None:
+        """This rank's partial row ``t`` of the call from the current (post-step) state, ``rewards``
+        and the device P (mdr_tick_stats_sharded)."""
+        self.env.shard.tick_stats_sharded(rewards, self._call[0], t)
+
+    def exchange(self) -> None:
+        """The call's one exchange and combine: the library's communicator (RCCL, host callbacks), or
+        ``comm.allreduce_sum`` of the slab and mdr_stats_rows_combine."""
+        (m, row0), self._call = self._call, None
+        sh = self.env.shard
+        if self._native():
+            sh.stats_rows_exchange(m, self.stats, row0)
+        else:
+            self.env._comm.allreduce_sum(sh, sh.stats_exchange_buffer(m))
+            sh.stats_rows_combine(m, self.stats, row0)
+
+    def abort(self) -> None:
+        """A call that failed between ``begin_partial`` and ``exchange``: the slab back to all zero."""
+        if self._call is not None:
+            m, self._call = self._call[0], None
+            self.env.shard.stats_exchange_buffer(m).zero_()
+
+
+def rollout_stats_for(env, capacity_ticks: int):
+    """The stats rows class for ``env``: ``ShardedRolloutStats`` for a sharded environment or one with
+    a communicator, ``RolloutStats`` otherwise."""
+    sharded = env.world > 1 or getattr(env, "_comm", None) is not None
+    return (ShardedRolloutStats if sharded else RolloutStats)(env, capacity_ticks)
 
 
 class DeviceMetrics:
@@ -286,7 +362,9 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
     and one reward row every tick overwrites.  ``twin`` None: ``copy.deepcopy(env)`` as the
     reference does; a caller-kept twin may be passed instead, whose context, row and reward buffers
     and rollout graph are then reused by later calls.  The copy is ``reset`` (which advances the
-    shared RNG, as in the reference); ``env``'s device state, tick, date and P are not touched."""
+    shared RNG, as in the reference); ``env``'s device state, tick, date and P are not touched.
+    On a sharded environment the call is collective (every rank makes it) and the rows are
+    ``ShardedRolloutStats``': the same means on every rank."""
     import copy
 
     import torch
@@ -301,7 +379,7 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
     ev.reset(return_obs=False)
     kept = getattr(ev, "_eval_kept", None) if twin is not None else None
     if kept is None or kept["stats"].capacity != n_ticks:  # (a graph is cached per rollout length anyway)
-        kept = {"stats": RolloutStats(ev, n_ticks),
+        kept = {"stats": rollout_stats_for(ev, n_ticks),
                 "rewards": torch.empty(ev.n_local, dtype=torch.float64, device=ev.shard.device)}
         if twin is not None:
             ev._eval_kept = kept  # (Environment.__deepcopy__ leaves it behind)
@@ -495,7 +573,7 @@ class ServerLoop:
 
         env = self.env
         if self._rows is None:
-            self._rows = (RolloutStats(env, self.rollout_ticks),
+            self._rows = (rollout_stats_for(env, self.rollout_ticks),
                           torch.empty(env.n_local, dtype=torch.float64, device=env.shard.device),
                           torch.empty(env.n_local, dtype=torch.uint8, device=env.shard.device)
                           if self.controller == "greedy" else None)

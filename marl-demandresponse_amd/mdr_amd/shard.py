@@ -468,6 +468,63 @@ class HipShard:
                                                  L.ptr(stats), int(stats.shape[0]), int(stats_row0), self.stream()),
                 "mdr_actor_rollout_stats")
 
+    # ------------------------------------------------------------------ stats rows of a sharded cluster
+    def stats_exchange_ranks(self, world: int, rank: int) -> None:
+        """mdr_stats_exchange_ranks: the exchange slab's world and rank on a shard whose context has
+        no communicator of its own (the caller drives the exchange)."""
+        L.check(self.lib.mdr_stats_exchange_ranks(self.ctx, int(world), int(rank)), "mdr_stats_exchange_ranks")
+
+    def stats_exchange_buffer(self, m: int):
+        """Zero-copy float64 view of the context's exchange slab X[world][m][16] for an ``m``-row call
+        (mdr_stats_exchange_buffer): what a Python-driven exchange sum-allreduces."""
+        from .distributed import device_view
+
+        p, n = C.c_void_p(), C.c_int64()
+        L.check(self.lib.mdr_stats_exchange_buffer(self.ctx, int(m), C.byref(p), C.byref(n)),
+                "mdr_stats_exchange_buffer")
+        return device_view(p.value, n.value, "<f8", self.device)
+
+    def tick_stats_sharded(self, reward, m: int, row: int, use_p_dev=True, p_host: float = 0.0):
+        """This rank's partial row ``row`` of an ``m``-row call from the current (post-step) state
+        (mdr_tick_stats_sharded).  Asynchronous."""
+        L.check(self.lib.mdr_tick_stats_sharded(self.ctx, L.ptr(reward), L.ptr(self.p_dev) if use_p_dev else 0,
+                                                float(p_host), int(m), int(row), self.stream()),
+                "mdr_tick_stats_sharded")
+
+    def stats_rows_combine(self, m: int, stats, row0: int):
+        """``stats[row0 : row0 + m]`` <- the rank-order combine of the allreduced slab, which it zeroes
+        (mdr_stats_rows_combine)."""
+        L.check(self.lib.mdr_stats_rows_combine(self.ctx, int(m), L.ptr(stats), int(stats.shape[0]), int(row0),
+                                                self.stream()), "mdr_stats_rows_combine")
+
+    def stats_rows_exchange(self, m: int, stats, row0: int):
+        """The slab's allreduce over the context's communicator, then ``stats_rows_combine``
+        (mdr_stats_rows_exchange)."""
+        L.check(self.lib.mdr_stats_rows_exchange(self.ctx, int(m), L.ptr(stats), int(stats.shape[0]), int(row0),
+                                                 self.stream()), "mdr_stats_rows_exchange")
+
+    def rollout_sharded_stats_path(self, mode) -> int:
+        """mdr_rollout_sharded_stats_path: 1 (the closed-loop windows' partial rows) or 2 (partial rows
+        per tick); MdrError where mdr_rollout_sharded_stats would refuse.  Nothing is launched."""
+        rc = self.lib.mdr_rollout_sharded_stats_path(self.ctx, mode)
+        if rc < 0:
+            L.check(rc, "mdr_rollout_sharded_stats")
+        return rc
+
+    def actor_rollout_sharded_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
+                                    rew_stride, snap, halo, row0: int, stats, stats_row0: int):
+        """``actor_rollout_sharded_snap`` (``snap`` may be None) that also writes tick t's stats row
+        into ``stats[stats_row0 + t]`` — partial rows per tick, one exchange behind the loop
+        (mdr_actor_rollout_sharded_stats)."""
+        n = len(ticks)
+        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
+        assert obs_sc.shape == (n, 4)
+        L.check(self.lib.mdr_actor_rollout_sharded_stats(
+            self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec), L.ptr(action), act_stride, L.ptr(prob),
+            prob_stride, L.ptr(reward), rew_stride, L.ptr(self.p_dev), C.byref(snap) if snap is not None else None,
+            C.byref(halo) if halo is not None else None, int(row0), L.ptr(stats), int(stats.shape[0]),
+            int(stats_row0), self.stream()), "mdr_actor_rollout_sharded_stats")
+
     def obs_gather(self, spec, snap, rows: int, idx, out):
         """out float32 [len(idx), n_feat] <- the obs rows of transitions ``idx`` (device int64:
         tick * n_local + house) over the first ``rows`` snapshot rows (mdr_obs_gather)."""
