@@ -117,6 +117,36 @@ struct GraphKey {
   bool operator<(const GraphKey& o) const { return fields() < o.fields(); }
 };
 
+// what the six actor rollout entry points hand to the single-GPU or the sharded function
+struct ActorRolloutArgs {
+  int n; const mdr_tick* ticks;
+  const mdr_obs_scalars* osc; const mdr_obs_spec* sp;
+  uint8_t* action; int64_t act_stride;
+  float* prob; int64_t prob_stride;
+  double* reward; int64_t rew_stride; double* p_dev;
+  const mdr_snap* snap; const mdr_snap_halo* shalo; int row0;  // optional: snapshot (and ring halo) row row0 + t
+  double* stats; int64_t stats_rows, stats_row0;               // optional: stats row stats_row0 + t
+  uint8_t* act_row(int t, uint8_t* fallback) const { return action ? action + (int64_t)t * act_stride : fallback; }
+  float* prob_row(int t) const { return prob ? prob + (int64_t)t * prob_stride : nullptr; }
+  double* rew_row(int t) const { return reward + (int64_t)t * rew_stride; }
+  double* stats_row(int t) const { return stats + (stats_row0 + t) * kTickRow; }
+};
+
+// Everything a captured actor rollout bakes into its launches (the head is, its epsilon is not: the kernels
+// load it).  a.row0 is zero without a snapshot (it is ignored then), a.stats_row0 without stats rows; snap: the
+// caller's by value, zero without one.  A call with a snapshot or stats rows never shares a graph with one without.
+struct ActorGraphKey {
+  ActorRolloutArgs a;
+  mdr_snap snap;
+  const void *comm_table, *halo_msg, *weights; int n_feat, head;  // (weights: the packed image)
+  auto fields() const {
+    return std::tie(a.n, a.action, a.act_stride, a.prob, a.prob_stride, a.reward, a.rew_stride, a.p_dev, comm_table,
+                    halo_msg, n_feat, head, weights, snap.t_air, snap.t_mass, snap.hvac, snap.scalars, snap.row_stride,
+                    a.row0, a.stats, a.stats_row0);
+  }
+  bool operator<(const ActorGraphKey& o) const { return fields() < o.fields(); }
+};
+
 }  // namespace
 
 struct mdr_ctx {
@@ -228,7 +258,7 @@ struct mdr_ctx {
   Dev<double> d_rows_p;        //   and the batch's [kTickRowsBatch] cluster powers
   Dev<double> d_xstat;         // sharded stats rows: the exchange slab X[world][m][kTickRow], all zero between calls
   int x_world = 0, x_rank = 0; // mdr_stats_exchange_ranks: the slab's world / rank on a shard without a communicator
-  std::map<std::vector<int64_t>, std::pair<hipGraphExec_t, int>> actor_graphs;  // (as graphs)
+  std::map<ActorGraphKey, std::pair<hipGraphExec_t, int>> actor_graphs;  // (as graphs)
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
   int64_t graphs_guarded = 0;            // captured graphs the memset guard walked (graph_memset_guard)
   int64_t graph_nodes_checked = 0;       //   and their nodes
@@ -901,6 +931,23 @@ static int capture_graph(mdr_ctx* c, F&& launches, hipGraphExec_t* out) {
   // upload the executable graph now (capture time), not on its first replay
   e = hipGraphUpload(*out, c->cap_stream);
   if (e != hipSuccess) return fail(MDR_EHIP, std::string("graph upload: ") + hipGetErrorString(e));
+  return MDR_OK;
+}
+
+// The graph of `launches` cached under `key` (captured on first use, with the ring its capture ends
+// on) replayed on st.  counter: its slot of graph_launches (mdr_graph_info).
+extern "C++" template <class Map, class F>
+static int replay_graph(mdr_ctx* c, Map& graphs, int counter, const typename Map::key_type& key, F&& launches,
+                        hipStream_t st) {
+  auto it = graphs.find(key);
+  if (it == graphs.end()) {
+    hipGraphExec_t ex;
+    if (int rc = capture_graph(c, launches, &ex)) return rc;
+    it = graphs.emplace(key, std::make_pair(ex, c->v.ring())).first;
+  }
+  HIP_TRY(hipGraphLaunch(it->second.first, st));
+  ++c->graph_launches[counter];
+  c->v.graph_replayed(it->second.second);
   return MDR_OK;
 }
 
@@ -1714,18 +1761,8 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
   if (!rc && stats) rc = rollout_stats_scratch(c, a.mode, !a.p_out);
   if (rc) return rc;
   if (!use_graph) return seq.end(rollout_launches(c, a, st, srow));
-  const GraphKey key{a, stats, stats ? row0 : 0};
-  auto it = c->graphs.find(key);
-  if (it == c->graphs.end()) {
-    hipGraphExec_t ex;
-    rc = capture_graph(c, [&](hipStream_t cs) { return rollout_launches(c, a, cs, srow); }, &ex);
-    if (rc) return rc;
-    it = c->graphs.emplace(key, std::make_pair(ex, c->v.ring())).first;
-  }
-  if (hipGraphLaunch(it->second.first, st) != hipSuccess) return fail(MDR_EHIP, std::string(who) + ": hipGraphLaunch");
-  ++c->graph_launches[0];
-  c->v.graph_replayed(it->second.second);
-  return seq.ok();
+  return seq.end(replay_graph(c, c->graphs, 0, GraphKey{a, stats, stats ? row0 : 0},
+                              [&](hipStream_t cs) { return rollout_launches(c, a, cs, srow); }, st));
 }
 
 int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
@@ -3550,106 +3587,283 @@ int mdr_obs_gather_sharded(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* s
   return MDR_OK;
 }
 
-// mdr_actor_rollout (snap == NULL: its launches and graph keys) / mdr_actor_rollout_snap
-static int actor_rollout_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                              const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
-                              const mdr_snap* snap, int row0, double* stats, int64_t stats_rows, int64_t stats_row0,
-                              void* stream, const char* who) {
-  enter_writer(c);
-  if (snap)
-    if (int rc = check_snap_struct(snap, who)) return rc;
-  if (stats && (stats_rows < 0 || stats_row0 < 0 || n < 0 || stats_row0 > stats_rows - n))
-    return fail(MDR_EARG, std::string(who) + ": stats_row0 .. stats_row0 + n_ticks outside [0, stats_rows)");
-  if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
-  if (snap)
-    if (int rc = check_snap(c, snap, row0, n, who)) return rc;
-  if (stats)
-    if (int rc = check_tick_stats_ctx(c, who)) return rc;
-  if (int rc = check_actor_obs(c, sp, who, S(stream))) return rc;
-  if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
-  hipStream_t st = S(stream);
-  Sequence seq(c->v, Sequence::kRollout);
-  if (int rc = refresh_if_dirty(c, st)) return rc;
-  if (int rc = stage_ticks(c, n, ticks, st)) return rc;
-  // per-tick obs scalars [s, solar, t_od, -] next to the tick drivers (same capacity)
-  if (int rc = stage_recs(osc, n, c->d_obs_sc, st)) return rc;
+// ---- the actor rollouts: mdr_actor_rollout[_snap|_stats] on one GPU, mdr_actor_rollout_sharded[...]
 
-  ObsArgs o = obs_args(c, sp, &osc[0]);
-  auto launches = [&](hipStream_t ls) -> int {
-    if (int rc = zero_slabs(c, ls)) return rc;
-    c->v.slabs_zeroed();
-    for (int t = 0; t < n; ++t) {
-      // the current slab is zero here: the memset above (t = 0), then the previous two steps
-      // (each zeroes the slab two ahead and a BUFFER step writes no lookahead)
-      ObsArgs ot = o;
-      ot.sc_dev = c->d_obs_sc + 4 * t;
-      ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act, prob ? prob + (int64_t)t * prob_stride : nullptr,
-                   nullptr, nullptr, slab_at(c, c->v.ring()), nullptr};
-      // the state and scalars this tick's actor reads, into snapshot row row0 + t
-      if (snap)
-        if (int rc = launch_snap(c, snap, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{}, ls)) return rc;
-      if (int rc = launch_actor(c, sp, ot, p_dev, 0, c->d_ticks + t, out, ls)) return rc;
-      if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
-                               reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, ls))
-        return rc;
-      // the post-step state, this tick's reward row and P into stats row stats_row0 + t
-      if (stats)
-        if (int rc = launch_tick_stats(c, reward + (int64_t)t * rew_stride, p_dev, 0.0,
-                                       stats + (stats_row0 + t) * kTickRow, ls))
-          return rc;
-    }
+// a ring halo is exchanged between the shards.  MDR_FORCE_HALO=1 (test hook): even at world 1 (send/recv to self),
+// which must reproduce the local ring wrap-around — the 1-GPU check of the multi-GPU exchange
+static bool actor_halo(const mdr_ctx* c, const mdr_obs_spec* sp) {
+  return (c->world > 1 || c->force_halo) && sp->n_comm > 0;
+}
+
+// The argument checks of the six entry points, in the order a call with several faults reports them
+// (the single-GPU and the sharded order differ), before anything is staged or launched.
+enum { kActorSharded = 1 };
+static int actor_rollout_preamble(mdr_ctx* c, const ActorRolloutArgs& a, int flags, hipStream_t st, const char* who) {
+  const bool shd = flags & kActorSharded;
+  // (deliberate compatibility: these sharded answers name mdr_actor_rollout_sharded whichever of its three was called)
+  const std::string base = shd ? "mdr_actor_rollout_sharded" : who;
+  int rc;
+  if (shd && a.stats && (rc = check_stats_rows(who, a.n, a.stats_rows, a.stats_row0))) return rc;
+  if (a.snap && (rc = check_snap_struct(a.snap, who))) return rc;
+  if (shd && a.snap && a.shalo && (rc = check_snap_halo_struct(a.shalo, who))) return rc;
+  if (!shd && a.stats && (rc = check_stats_rows(who, a.n, a.stats_rows, a.stats_row0))) return rc;
+  const bool ptrs = a.ticks && a.osc && a.sp && a.reward && a.p_dev;
+  if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, base + ": bad argument");
+  if (!c->bound) return fail(MDR_ESTATE, base + ": context not bound");
+  if (shd && !has_comm(c)) return fail(MDR_ESTATE, base + ": no communicator (mdr_rccl_init / mdr_comm_host)");
+  const bool halo = shd && actor_halo(c, a.sp);
+  if (a.snap && !shd && (rc = check_snap(c, a.snap, a.row0, a.n, who))) return rc;
+  if (a.snap && shd) {
+    if ((rc = check_snap_slabs(c, a.snap, a.row0, a.n, who))) return rc;
+    if (halo && !a.shalo) return fail(MDR_EARG, std::string(who) + ": a ring halo is exchanged: halo must be given");
+    const int64_t need = (int64_t)a.sp->n_comm * mdr_msg_width(a.sp);
+    if (halo && (rc = check_snap_halo(a.shalo, need, a.row0, a.n, who))) return rc;
+  }
+  if (!shd && a.stats && (rc = check_tick_stats_ctx(c, who))) return rc;
+  if ((rc = check_actor_obs(c, a.sp, base.c_str(), st))) return rc;
+  if (win_common(c)) return fail(MDR_EARG, base + ": common penalty modes need the per-step API");
+  if (halo && a.sp->comm_mode != MDR_COMM_RING)
+    return fail(MDR_EARG, base + ": across shards only the 'neighbours' ring obs is supported");
+  if (halo && c->kp.n < (a.sp->n_comm + 1) / 2) return fail(MDR_EARG, base + ": shard smaller than the ring half-width");
+  return MDR_OK;
+}
+
+// ahead of either sequence: the tick drivers, the per-tick obs scalars [s, solar, t_od, -] next to them, d_act
+static int actor_stage(mdr_ctx* c, const ActorRolloutArgs& a, hipStream_t st) {
+  int rc = refresh_if_dirty(c, st);
+  if (!rc) rc = stage_ticks(c, a.n, a.ticks, st);
+  if (!rc) rc = stage_recs(a.osc, a.n, c->d_obs_sc, st);
+  if (!rc && !a.action) rc = dev_reserve(c->d_act, c->kp.n, "d_act");
+  return rc;
+}
+
+// The per-tick pieces the three sequences below share.  sp: the obs spec the actor runs (sharded: halo_msg = recv),
+// o: its tick-invariant ObsArgs; the ring halo: lo / hi houses before / after the shard, M floats each,
+// mine = [hi first | lo last] of this shard, recv = [lo before | hi after]
+struct ActorSeq {
+  mdr_ctx* c; const ActorRolloutArgs& a; hipStream_t st;
+  const mdr_obs_spec* sp; ObsArgs o;
+  int lo = 0, hi = 0, M = 0;
+  bool halo = false;
+  float *mine = nullptr, *recv = nullptr;
+  const double* sc(int t) const { return c->d_obs_sc + 4 * t; }  // tick t's staged obs scalars
+  ObsArgs obs(int t) const { ObsArgs ot = o; ot.sc_dev = sc(t); return ot; }
+  // tick t's outputs (the context-owned action row without the caller's), its ON counts into `counts`
+  ActorOut out(int t, unsigned long long* counts) const {
+    return ActorOut{a.act_row(t, c->d_act), a.prob_row(t), nullptr, nullptr, counts, nullptr};
+  }
+  int actor(int t, const ObsArgs& ot, const ActorOut& out) const {
+    return launch_actor(c, sp, ot, a.p_dev, 0, c->d_ticks + t, out, st);
+  }
+  // the state and scalars tick t's actor reads, into snapshot row row0 + t ...
+  int snapshot(int t) const {
+    return a.snap ? launch_snap(c, a.snap, a.row0 + t, sc(t), a.p_dev, mdr_obs_scalars{}, st) : MDR_OK;
+  }
+  // ... and the halo it reads, lo rows at halo_lo and hi at halo_hi (none exchanged: an empty halo row)
+  int snapshot(int t, const float* halo_lo, const float* halo_hi) const {
+    if (!a.snap) return MDR_OK;
+    return launch_snap_halo(c, a.snap, halo ? a.shalo : nullptr, a.row0 + t, sc(t), a.p_dev,
+                            mdr_obs_scalars{}, halo_lo, halo_hi, lo * M, hi * M, st);
+  }
+  // this shard's edge rows into mine; their exchange into recv: rank r-1's last lo houses, then rank r+1's first hi
+  int pack(hipStream_t on) const {
+    hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, on, c->kp, o, lo, hi, mine);
+    LAUNCH_CHECK("k_halo_pack");
     return MDR_OK;
-  };
-  if (!action)  // context-owned action row
-    if (int rc = dev_reserve(c->d_act, c->kp.n, "d_act")) return rc;
-  if (stats)
+  }
+  int exchange(hipStream_t on) const { return comm_halo(c, mine, recv, lo, hi, M, on); }
+  // tick t's step of its BUFFER actions, from the context's ring of slabs or from explicit ones
+  int step(int t) const {
+    return launch_step(c, a.act_row(t, c->d_act), MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t, a.rew_row(t), 0,
+                       MDR_CTRL_NONE, nullptr, a.p_dev, st);
+  }
+  int step(int t, const unsigned long long* cur, unsigned long long* nxt, unsigned long long* zer) const {
+    return launch_step_on(c, a.act_row(t, c->d_act), MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t, a.rew_row(t), 0,
+                          MDR_CTRL_NONE, nullptr, a.p_dev, cur, nxt, zer, 0, st);
+  }
+  // tick t's stats row — the state after its step, its reward row (read before a stride-0 buffer is
+  // overwritten by tick t + 1) and P — behind the step, before tick t + 1's snapshot and actor: into the
+  // caller's row stats_row0 + t, or (part, sharded) this rank's partial row of the exchange slab
+  int row(int t, bool part = false) const {
+    if (!a.stats) return MDR_OK;
+    return launch_tick_stats(c, a.rew_row(t), a.p_dev, 0.0, part ? stats_part_rows(c, a.n, t) : a.stats_row(t), st);
+  }
+};
+
+// The single-GPU sequence.  Kernels only, so a graph may capture it.
+static int actor_ticks(mdr_ctx* c, const ActorRolloutArgs& a, hipStream_t st) {
+  const ActorSeq s{c, a, st, a.sp, obs_args(c, a.sp, &a.osc[0])};
+  if (int rc = zero_slabs(c, st)) return rc;
+  c->v.slabs_zeroed();
+  for (int t = 0; t < a.n; ++t) {
+    // the current slab is zero here: the memset above (t = 0), then the previous two steps
+    // (each zeroes the slab two ahead and a BUFFER step writes no lookahead)
+    if (int rc = s.snapshot(t)) return rc;
+    if (int rc = s.actor(t, s.obs(t), s.out(t, slab_at(c, c->v.ring())))) return rc;
+    if (int rc = s.step(t)) return rc;
+    if (int rc = s.row(t)) return rc;
+  }
+  return MDR_OK;
+}
+
+// The sharded sequence with the halo in the counts (MDR_OPT_HALO_IN_COUNTS): ONE collective per
+// tick, the count slab and every rank's post-step edge rows of tick t (the halo of tick t + 1) in one
+// integer sum-allreduce (k_halo_step_pack); tick 0's halo (of the current state) is exchanged once
+// before the loop.  Tick t counts into slot t % 3 of d_c5, the step kernel's own ring of three.
+static int actor_ticks_halo_in_counts(const ActorSeq& s) {
+  mdr_ctx* const c = s.c;
+  const int lo = s.lo, hi = s.hi, M = s.M, W = lo + hi;
+  const size_t rows_words = ((size_t)c->world * W * M + 1) / 2;  // floats, two per u64 word
+  const size_t words = c->slab_len + rows_words;
+  if (3 * words > c->d_c5.capacity()) {
+    HIP_TRY(hipStreamSynchronize(s.st));
+    if (int rc = dev_reserve(c->d_c5, 3 * words, "d_c5")) return rc;
+  }
+  auto buf = [&](int t) { return c->d_c5 + (size_t)(t % 3) * words; };
+  auto rows = [&](int t) { return reinterpret_cast<float*>(buf(t) + c->slab_len); };
+  hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, s.st, c->d_c5, (int64_t)(3 * words));
+  LAUNCH_CHECK("k_zero_u64");
+  if (int rc = s.pack(s.st)) return rc;
+  if (int rc = s.exchange(s.st)) return rc;
+  const int prev = (c->rank + c->world - 1) % c->world, next = (c->rank + 1) % c->world;
+  for (int t = 0; t < s.a.n; ++t) {
+    // the halo this tick's actor reads: tick 0's from the exchange above, later ticks' the two parts
+    // of tick t - 1's allreduced rows, rank prev's last lo and rank next's first hi (stream-ordered
+    // after that allreduce, and before this tick's step and the pack of tick t + 2 that next write
+    // buf((t - 1) % 3))
+    ObsArgs ot = s.obs(t);
+    if (t > 0) {
+      ot.halo_msg = rows(t - 1) + (size_t)prev * W * M + (size_t)hi * M;
+      ot.halo_next = rows(t - 1) + (size_t)next * W * M;
+    }
+    const ActorOut out = s.out(t, buf(t));
+    if (int rc = s.snapshot(t, ot.halo_msg, t > 0 ? ot.halo_next : ot.halo_msg + (size_t)lo * M)) return rc;
+    if (int rc = s.actor(t, ot, out)) return rc;
+    hipLaunchKernelGGL(k_halo_step_pack, dim3(1), dim3(256), 0, s.st, c->kp, ot, (const uint8_t*)out.action,
+                       (const TickArgs*)(c->d_ticks + t), lo, hi, c->rank, c->world, rows(t));
+    LAUNCH_CHECK("k_halo_step_pack");
+    if (int rc = comm_allreduce(c, buf(t), words, 0, s.st)) return rc;
+    if (int rc = s.step(t, buf(t), buf(t + 1), buf(t + 2))) return rc;
+    c->v.step_issued(false, false, /*keep_ring=*/true);  // (d_c5's own ring of 3)
+    if (int rc = s.row(t, true)) return rc;
+  }
+  return MDR_OK;
+}
+
+// The sharded serial / overlap sequence (config C5): per tick
+//   [ring obs across shards] k_halo_pack -> grouped RCCL send/recv of the edge houses' message
+//   features with ranks r-1 / r+1 -> k_actor (obs on chip, actions, ON counts of those actions)
+//   -> RCCL sum-allreduce of the count slab -> k_step (BUFFER actions, global P)
+// Actions are sampled from Philox keyed by (seed, GLOBAL house id, tick) and the counts are exact
+// integers, so the sharded run is bit-identical to the single-shard one.
+// overlap (fused actor, >= 4 tiles, a comm stream): per tick the halo is packed and exchanged on the
+// comm stream while the interior tiles' actor runs on the compute stream; the first and last
+// tile follow once it has landed.  They are the only readers of the halo when lo, hi <= 32 and
+// the last tile holds no house whose ring reaches past it: tile ntile-2 reads houses up to
+// 32 (ntile-1) + hi - 1, beyond the shard when the last tile is short, n % 32 in 1 .. hi-1
+static int actor_ticks_sharded(const ActorSeq& s) {
+  mdr_ctx* const c = s.c;
+  const hipStream_t st = s.st, cs = c->comm_stream;
+  HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
+  c->v.slabs_zeroed();
+  const int64_t rag = c->kp.n % 32;
+  const bool overlap = s.halo && c->halo_overlap && cs && actor_fused_ok(c, s.sp) && (c->kp.n + 31) / 32 >= 4 &&
+                       s.lo <= 32 && s.hi <= 32 && (rag == 0 || rag >= s.hi);
+  for (int t = 0; t < s.a.n; ++t) {
+    const ObsArgs ot = s.obs(t);
+    ActorOut out = s.out(t, slab_at(c, c->v.ring()));
+    if (overlap) {
+      HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state after the previous step
+      HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
+      if (int rc = s.pack(cs)) return rc;
+      ActorOut in = out;
+      in.tiles = 1;  // (issued before the exchange: host collectives block in comm_halo)
+      if (int rc = s.actor(t, ot, in)) return rc;
+      if (int rc = s.exchange(cs)) return rc;
+      HIP_TRY(hipEventRecord(c->ev_ar[0], cs));
+      HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[0], 0));
+      out.tiles = 2;
+      // (recv has landed for the compute stream; the next tick's exchange waits on ev_pc, recorded
+      // after the snapshot launch below)
+    } else if (s.halo) {
+      if (int rc = s.pack(st)) return rc;
+      if (int rc = s.exchange(st)) return rc;
+    }
+    // the pre-step state and the halo in recv, before this tick's step
+    if (int rc = s.snapshot(t, s.recv, s.recv ? s.recv + (size_t)s.lo * s.M : nullptr)) return rc;
+    if (int rc = s.actor(t, ot, out)) return rc;
+    if (int rc = comm_allreduce(c, slab_at(c, c->v.ring()), c->slab_len, 0, st)) return rc;
+    if (int rc = s.step(t)) return rc;
+    if (int rc = s.row(t, true)) return rc;
+  }
+  return MDR_OK;
+}
+
+static ActorGraphKey actor_graph_key(const mdr_ctx* c, ActorRolloutArgs a) {
+  if (!a.snap) a.row0 = 0;
+  if (!a.stats) a.stats_row0 = 0;
+  return ActorGraphKey{a, a.snap ? *a.snap : mdr_snap{}, a.sp->comm_table, a.sp->halo_msg, c->d_actor.get(),
+                       a.sp->n_feat, c->actor_head};
+}
+
+// mdr_actor_rollout / _snap / _stats: the single-GPU sequence, replayed as a cached graph (the ring at
+// the end of its capture: n steps from slab 0, n % 3) unless the caller declines
+static int actor_rollout(mdr_ctx* c, const ActorRolloutArgs& a, int use_graph, void* stream, const char* who) {
+  enter_writer(c);
+  hipStream_t st = S(stream);
+  if (int rc = actor_rollout_preamble(c, a, 0, st, who)) return rc;
+  Sequence seq(c->v, Sequence::kRollout);
+  if (int rc = actor_stage(c, a, st)) return rc;
+  if (a.stats)
     if (int rc = tick_scratch(c)) return rc;  // (before any capture)
+  auto launches = [&](hipStream_t ls) { return actor_ticks(c, a, ls); };
   if (!use_graph) return seq.end(launches(st));
-  std::vector<int64_t> key{n, (int64_t)(uintptr_t)action, act_stride, (int64_t)(uintptr_t)prob, prob_stride,
-                           (int64_t)(uintptr_t)reward, rew_stride, (int64_t)(uintptr_t)p_dev,
-                           (int64_t)(uintptr_t)sp->comm_table,
-                           (int64_t)(uintptr_t)sp->halo_msg, sp->n_feat | ((int64_t)c->actor_head << 32),
-                           (int64_t)(uintptr_t)c->d_actor.get()};
-  // (the head, mdr_actor_set_head, is baked into the captured launches, so it is part of the key above
-  // n_feat — MDR_HEAD_SOFTMAX = 0 leaves the softmax keys as they were; epsilon is not: the kernels load it)
-  if (snap)  // (longer keys: never equal to a rollout's without snapshots)
-    key.insert(key.end(), {(int64_t)(uintptr_t)snap->t_air, (int64_t)(uintptr_t)snap->t_mass,
-                           (int64_t)(uintptr_t)snap->hvac, (int64_t)(uintptr_t)snap->scalars, snap->row_stride,
-                           (int64_t)row0});
-  if (stats) {  // (20 entries: the snapshot fields, zero without one, then the stats rows)
-    if (!snap) key.insert(key.end(), {0, 0, 0, 0, 0, 0});
-    key.insert(key.end(), {(int64_t)(uintptr_t)stats, stats_row0});
-  }
-  auto it = c->actor_graphs.find(key);
-  if (it == c->actor_graphs.end()) {
-    hipGraphExec_t ex;
-    if (int rc = capture_graph(c, launches, &ex)) return rc;
-    // (the ring at the end of the capture: n steps from slab 0, n % 3)
-    it = c->actor_graphs.emplace(key, std::make_pair(ex, c->v.ring())).first;
-  }
-  HIP_TRY(hipGraphLaunch(it->second.first, st));
-  ++c->graph_launches[1];
-  c->v.graph_replayed(it->second.second);
-  return seq.ok();
+  return seq.end(replay_graph(c, c->actor_graphs, 1, actor_graph_key(c, a), launches, st));
 }
 
-int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                      const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                      int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
-                      void* stream) {
-  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
-                            use_graph, nullptr, 0, nullptr, 0, 0, stream, "mdr_actor_rollout");
+// mdr_actor_rollout_sharded / _snap / _stats.  With a snapshot one k_snap_halo per tick records the
+// state, scalars and halo the tick's actor reads; with stats rows each tick leaves this rank's partial
+// row and one exchange + combine follows the loop.
+static int actor_rollout_sharded(mdr_ctx* c, const ActorRolloutArgs& a, void* stream, const char* who) {
+  enter_writer(c);
+  hipStream_t st = S(stream);
+  if (int rc = actor_rollout_preamble(c, a, kActorSharded, st, who)) return rc;
+  if (a.stats) {  // the exchange slab and k_tick_stats' partials, outside the launch sequence
+    if (int rc = stats_exchange_reserve(c, a.n, who)) return rc;
+    if (int rc = tick_scratch(c)) return rc;
+  }
+  Sequence seq(c->v, Sequence::kRollout);
+  if (int rc = actor_stage(c, a, st)) return rc;
+  const int K = a.sp->n_comm, M = mdr_msg_width(a.sp), lo = K / 2, hi = (K + 1) / 2;
+  const bool halo = actor_halo(c, a.sp);
+  const size_t hrows = (size_t)2 * (lo + hi) * M;
+  if (halo && hrows > c->d_halo.capacity()) {
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = dev_reserve(c->d_halo, hrows, "d_halo")) return rc;
+  }
+  float* const recv = c->d_halo ? c->d_halo + (size_t)(lo + hi) * M : nullptr;
+  mdr_obs_spec spec = *a.sp;
+  spec.halo_msg = halo ? recv : nullptr;
+  const ActorSeq s{c, a, st, &spec, obs_args(c, &spec, &a.osc[0]), lo, hi, M, halo, c->d_halo, recv};
+  int rc = halo && c->halo_in_counts ? actor_ticks_halo_in_counts(s) : actor_ticks_sharded(s);
+  if (!rc && a.stats) rc = stats_rows_exchange(c, a.n, false, a.stats_row(0), st);
+  return seq.end(rc);
 }
 
-int mdr_actor_rollout_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                           const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                           int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
-                           const mdr_snap* snap, int row0, void* stream) {
-  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
-                            use_graph, snap, row0, nullptr, 0, 0, stream, "mdr_actor_rollout_snap");
+int mdr_actor_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc, const mdr_obs_spec* sp,
+                      uint8_t* action, int64_t act_stride, float* prob, int64_t prob_stride, double* reward,
+                      int64_t rew_stride, double* p_dev, int use_graph, void* stream) {
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev};
+  return actor_rollout(c, a, use_graph, stream, "mdr_actor_rollout");
+}
+
+int mdr_actor_rollout_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc, const mdr_obs_spec* sp,
+                           uint8_t* action, int64_t act_stride, float* prob, int64_t prob_stride, double* reward,
+                           int64_t rew_stride, double* p_dev, int use_graph, const mdr_snap* snap, int row0,
+                           void* stream) {
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                           snap, nullptr, row0};
+  return actor_rollout(c, a, use_graph, stream, "mdr_actor_rollout_snap");
 }
 
 int mdr_actor_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -3657,201 +3871,26 @@ int mdr_actor_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_
                             int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, int use_graph,
                             const mdr_snap* snap, int row0, double* stats, int64_t stats_rows, int64_t stats_row0,
                             void* stream) {
-  return actor_rollout_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
-                            use_graph, snap, row0, stats, stats_rows, stats_row0, stream,
-                            stats ? "mdr_actor_rollout_stats" : snap ? "mdr_actor_rollout_snap" : "mdr_actor_rollout");
-}
-
-// Sharded MA-PPO rollout (config C5): per tick
-//   [ring obs across shards] k_halo_pack -> grouped RCCL send/recv of the edge houses' message
-//   features with ranks r-1 / r+1 -> k_actor (obs on chip, actions, ON counts of those actions)
-//   -> RCCL sum-allreduce of the count slab -> k_step (BUFFER actions, global P)
-// Actions are sampled from Philox keyed by (seed, GLOBAL house id, tick) and the counts are exact
-// integers, so the sharded run is bit-identical to the single-shard one.
-// snap != NULL (mdr_actor_rollout_sharded_snap): one k_snap_halo per tick records the state, scalars
-// and halo the tick's actor reads; snap == NULL: mdr_actor_rollout_sharded's launches
-static int actor_rollout_sharded_impl(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
-                                      const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                                      int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
-                                      const mdr_snap* snap, const mdr_snap_halo* shalo, int row0, double* stats,
-                                      int64_t stats_rows, int64_t stats_row0, void* stream, const char* who) {
-  enter_writer(c);
-  if (stats)  // (before anything is staged or launched, and before any other answer)
-    if (int rc = check_stats_rows(who, n, stats_rows, stats_row0)) return rc;
-  if (snap)
-    if (int rc = check_snap_struct(snap, who)) return rc;
-  if (snap && shalo)
-    if (int rc = check_snap_halo_struct(shalo, who)) return rc;
-  if (!c || !ticks || !osc || !sp || !reward || !p_dev || n < 1)
-    return fail(MDR_EARG, "mdr_actor_rollout_sharded: bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_rollout_sharded: context not bound");
-  if (!has_comm(c)) return fail(MDR_ESTATE, "mdr_actor_rollout_sharded: no communicator (mdr_rccl_init / mdr_comm_host)");
-  if (snap) {  // (before anything is launched or staged)
-    if (int rc = check_snap_slabs(c, snap, row0, n, who)) return rc;
-    if ((c->world > 1 || c->force_halo) && sp->n_comm > 0) {
-      if (!shalo) return fail(MDR_EARG, std::string(who) + ": a ring halo is exchanged: halo must be given");
-      if (int rc = check_snap_halo(shalo, (int64_t)sp->n_comm * mdr_msg_width(sp), row0, n, who)) return rc;
-    }
-  }
-  if (int rc = check_actor_obs(c, sp, "mdr_actor_rollout_sharded", S(stream))) return rc;
-  if (c->kp.penalty_mode != MDR_PEN_INDIVIDUAL_L2)
-    return fail(MDR_EARG, "mdr_actor_rollout_sharded: common penalty modes need the per-step API");
-  const int K = sp->n_comm, M = mdr_msg_width(sp);
-  const int lo = K / 2, hi = (K + 1) / 2;
-  // MDR_FORCE_HALO=1 (test hook): exchange the halo even at world 1 (send/recv to self), which
-  // must reproduce the local ring wrap-around — the 1-GPU check of the multi-GPU exchange
-  const bool halo = (c->world > 1 || c->force_halo) && K > 0;
-  if (halo && sp->comm_mode != MDR_COMM_RING)
-    return fail(MDR_EARG, "mdr_actor_rollout_sharded: across shards only the 'neighbours' ring obs is supported");
-  if (halo && c->kp.n < (lo > hi ? lo : hi))
-    return fail(MDR_EARG, "mdr_actor_rollout_sharded: shard smaller than the ring half-width");
-  hipStream_t st = S(stream);
-  if (stats) {  // the exchange slab and k_tick_stats' partials, outside the launch sequence
-    if (int rc = stats_exchange_reserve(c, n, who)) return rc;
-    if (int rc = tick_scratch(c)) return rc;
-  }
-  // tick t's partial row — the state after its step, its reward row (read before a stride-0 buffer is
-  // overwritten by tick t + 1) and P — behind the step on the compute stream, before tick t + 1's
-  // snapshot and actor; one exchange + combine behind the loop (rows_done)
-  auto part_row = [&](int t) -> int {
-    if (!stats) return MDR_OK;
-    return launch_tick_stats(c, reward + (int64_t)t * rew_stride, p_dev, 0.0, stats_part_rows(c, n, t), st);
-  };
-  auto rows_done = [&]() -> int {
-    if (!stats) return MDR_OK;
-    return stats_rows_exchange(c, n, false, stats + (size_t)stats_row0 * kTickRow, st);
-  };
-  Sequence seq(c->v, Sequence::kRollout);
-  if (int rc = refresh_if_dirty(c, st)) return rc;
-  if (int rc = stage_ticks(c, n, ticks, st)) return rc;
-  if (int rc = stage_recs(osc, n, c->d_obs_sc, st)) return rc;
-  if (!action)
-    if (int rc = dev_reserve(c->d_act, c->kp.n, "d_act")) return rc;
-  const size_t hrows = (size_t)2 * (lo + hi) * M;
-  if (halo && hrows > c->d_halo.capacity()) {
-    HIP_TRY(hipStreamSynchronize(st));
-    if (int rc = dev_reserve(c->d_halo, hrows, "d_halo")) return rc;
-  }
-  float* mine = c->d_halo;                                    // [hi first | lo last] of this shard
-  float* recv = c->d_halo ? c->d_halo + (size_t)(lo + hi) * M : nullptr;  // [lo before | hi after]
-  mdr_obs_spec spec = *sp;
-  spec.halo_msg = halo ? recv : nullptr;
-  const ObsArgs o = obs_args(c, &spec, &osc[0]);
-  if (halo && c->halo_in_counts) {
-    // ONE collective per tick: the count slab and every rank's post-step edge rows of tick t (the
-    // halo of tick t + 1) in one integer sum-allreduce (k_halo_step_pack); tick 0's halo (of the
-    // current state) is exchanged once before the loop
-    const int W = lo + hi;
-    const size_t rows_words = ((size_t)c->world * W * M + 1) / 2;  // floats, two per u64 word
-    const size_t words = c->slab_len + rows_words;
-    if (3 * words > c->d_c5.capacity()) {
-      HIP_TRY(hipStreamSynchronize(st));
-      if (int rc = dev_reserve(c->d_c5, 3 * words, "d_c5")) return rc;
-    }
-    auto buf = [&](int t) { return c->d_c5 + (size_t)(t % 3) * words; };
-    auto rows = [&](int t) { return reinterpret_cast<float*>(buf(t) + c->slab_len); };
-    hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(256), 0, st, c->d_c5, (int64_t)(3 * words));
-    LAUNCH_CHECK("k_zero_u64");
-    hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, st, c->kp, o, lo, hi, mine);
-    LAUNCH_CHECK("k_halo_pack");
-    if (int rc = comm_halo(c, mine, recv, lo, hi, M, st)) return rc;
-    const int prev = (c->rank + c->world - 1) % c->world, next = (c->rank + 1) % c->world;
-    for (int t = 0; t < n; ++t) {
-      ObsArgs ot = o;
-      ot.sc_dev = c->d_obs_sc + 4 * t;
-      if (t > 0) {  // the previous tick's allreduced rows: rank prev's last lo, rank next's first hi
-        ot.halo_msg = rows(t - 1) + (size_t)prev * W * M + (size_t)hi * M;
-        ot.halo_next = rows(t - 1) + (size_t)next * W * M;
-      }
-      ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act,
-                   prob ? prob + (int64_t)t * prob_stride : nullptr, nullptr, nullptr, buf(t), nullptr};
-      // the halo this tick's actor reads: tick 0's from the exchange above, later ticks' the two parts
-      // of tick t - 1's allreduced rows (stream-ordered after that allreduce, and before this tick's
-      // step and the pack of tick t + 2 that next write buf((t - 1) % 3))
-      if (snap)
-        if (int rc = launch_snap_halo(c, snap, shalo, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{}, ot.halo_msg,
-                                      t > 0 ? ot.halo_next : ot.halo_msg + (size_t)lo * M, lo * M, hi * M, st))
-          return rc;
-      if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, out, st)) return rc;
-      hipLaunchKernelGGL(k_halo_step_pack, dim3(1), dim3(256), 0, st, c->kp, ot, (const uint8_t*)out.action,
-                         (const TickArgs*)(c->d_ticks + t), lo, hi, c->rank, c->world, rows(t));
-      LAUNCH_CHECK("k_halo_step_pack");
-      if (int rc = comm_allreduce(c, buf(t), words, 0, st)) return rc;
-      if (int rc = launch_step_on(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
-                                  reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, buf(t),
-                                  buf(t + 1), buf(t + 2), 0, st))
-        return rc;
-      c->v.step_issued(false, false, /*keep_ring=*/true);  // (d_c5's own ring of 3)
-      if (int rc = part_row(t)) return rc;
-    }
-    return seq.end(rows_done());
-  }
-  HIP_TRY(hipMemsetAsync(c->d_slab, 0, kSlabs * c->slab_len * sizeof(unsigned long long), st));
-  c->v.slabs_zeroed();
-  // overlap (fused actor, >= 4 tiles, a comm stream): per tick the halo is packed and exchanged on the
-  // comm stream while the interior tiles' actor runs on the compute stream; the first and last
-  // tile follow once it has landed.  They are the only readers of the halo when lo, hi <= 32 and
-  // the last tile holds no house whose ring reaches past it: tile ntile-2 reads houses up to
-  // 32 (ntile-1) + hi - 1, beyond the shard when the last tile is short, n % 32 in 1 .. hi-1
-  const int64_t rag = c->kp.n % 32;
-  const bool overlap = halo && c->halo_overlap && c->comm_stream && actor_fused_ok(c, &spec) &&
-                       (c->kp.n + 31) / 32 >= 4 && lo <= 32 && hi <= 32 && (rag == 0 || rag >= hi);
-  hipStream_t cs = c->comm_stream;
-  for (int t = 0; t < n; ++t) {
-    ObsArgs ot = o;
-    ot.sc_dev = c->d_obs_sc + 4 * t;
-    ActorOut out{action ? action + (int64_t)t * act_stride : c->d_act,
-                 prob ? prob + (int64_t)t * prob_stride : nullptr, nullptr, nullptr, slab_at(c, c->v.ring()), nullptr};
-    if (overlap) {
-      HIP_TRY(hipEventRecord(c->ev_pc, st));  // the state after the previous step
-      HIP_TRY(hipStreamWaitEvent(cs, c->ev_pc, 0));
-      hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, cs, c->kp, o, lo, hi, mine);
-      LAUNCH_CHECK("k_halo_pack");
-      ActorOut in = out;
-      in.tiles = 1;  // (issued before the exchange: host collectives block in comm_halo)
-      if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, in, st)) return rc;
-      if (int rc = comm_halo(c, mine, recv, lo, hi, M, cs)) return rc;
-      HIP_TRY(hipEventRecord(c->ev_ar[0], cs));
-      HIP_TRY(hipStreamWaitEvent(st, c->ev_ar[0], 0));
-      out.tiles = 2;
-      // (recv has landed for the compute stream; the next tick's exchange waits on ev_pc, recorded
-      // after the snapshot launch below)
-    } else if (halo) {
-      hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, st, c->kp, o, lo, hi, mine);
-      LAUNCH_CHECK("k_halo_pack");
-      // the previous rank's last lo houses come first in the halo, the next rank's first hi after
-      if (int rc = comm_halo(c, mine, recv, lo, hi, M, st)) return rc;
-    }
-    // the pre-step state and the halo in recv (none: an empty halo row), before this tick's step
-    if (snap)
-      if (int rc = launch_snap_halo(c, snap, halo ? shalo : nullptr, row0 + t, ot.sc_dev, p_dev, mdr_obs_scalars{},
-                                    recv, recv ? recv + (size_t)lo * M : nullptr, lo * M, hi * M, st))
-        return rc;
-    if (int rc = launch_actor(c, &spec, ot, p_dev, 0, c->d_ticks + t, out, st)) return rc;
-    if (int rc = comm_allreduce(c, slab_at(c, c->v.ring()), c->slab_len, 0, st)) return rc;
-    if (int rc = launch_step(c, out.action, MDR_ACT_BUFFER, TickArgs{}, c->d_ticks + t,
-                             reward + (int64_t)t * rew_stride, 0, MDR_CTRL_NONE, nullptr, p_dev, st))
-      return rc;
-    if (int rc = part_row(t)) return rc;
-  }
-  return seq.end(rows_done());
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                           snap, nullptr, row0, stats, stats_rows, stats_row0};
+  return actor_rollout(c, a, use_graph, stream,
+                       stats ? "mdr_actor_rollout_stats" : snap ? "mdr_actor_rollout_snap" : "mdr_actor_rollout");
 }
 
 int mdr_actor_rollout_sharded(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
                               const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
-                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
-                              void* stream) {
-  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
-                                    p_dev, nullptr, nullptr, 0, nullptr, 0, 0, stream, "mdr_actor_rollout_sharded");
+                              int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev, void* stream) {
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev};
+  return actor_rollout_sharded(c, a, stream, "mdr_actor_rollout_sharded");
 }
 
 int mdr_actor_rollout_sharded_snap(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
                                    const mdr_obs_spec* sp, uint8_t* action, int64_t act_stride, float* prob,
                                    int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                                    const mdr_snap* snap, const mdr_snap_halo* halo, int row0, void* stream) {
-  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
-                                    p_dev, snap, halo, row0, nullptr, 0, 0, stream,
-                                    snap ? "mdr_actor_rollout_sharded_snap" : "mdr_actor_rollout_sharded");
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                           snap, halo, row0};
+  return actor_rollout_sharded(c, a, stream, snap ? "mdr_actor_rollout_sharded_snap" : "mdr_actor_rollout_sharded");
 }
 
 int mdr_actor_rollout_sharded_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const mdr_obs_scalars* osc,
@@ -3859,11 +3898,10 @@ int mdr_actor_rollout_sharded_stats(mdr_ctx* c, int n, const mdr_tick* ticks, co
                                     int64_t prob_stride, double* reward, int64_t rew_stride, double* p_dev,
                                     const mdr_snap* snap, const mdr_snap_halo* halo, int row0, double* stats,
                                     int64_t stats_rows, int64_t stats_row0, void* stream) {
-  return actor_rollout_sharded_impl(c, n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride,
-                                    p_dev, snap, halo, row0, stats, stats_rows, stats_row0, stream,
-                                    stats  ? "mdr_actor_rollout_sharded_stats"
-                                    : snap ? "mdr_actor_rollout_sharded_snap"
-                                           : "mdr_actor_rollout_sharded");
+  const ActorRolloutArgs a{n, ticks, osc, sp, action, act_stride, prob, prob_stride, reward, rew_stride, p_dev,
+                           snap, halo, row0, stats, stats_rows, stats_row0};
+  return actor_rollout_sharded(c, a, stream, stats  ? "mdr_actor_rollout_sharded_stats"
+                                             : snap ? "mdr_actor_rollout_sharded_snap" : "mdr_actor_rollout_sharded");
 }
 
 }  // extern "C"

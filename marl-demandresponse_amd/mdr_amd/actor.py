@@ -270,38 +270,18 @@ class DeviceActor:
             osc[1:, 2] = ticks.solar[:-1]
             osc[:, 3] = ticks.t_od_prev
             sl = (lambda x, st: None if x is None else (x[done:done + k] if st else x))
-            if sharded and stats is not None:  # ... and the ranks' partial rows, one exchange behind the loop
-                if done == 0:
-                    stats.record_power(srow0)
-                st_sh = store is not None and getattr(store, "sharded", False)
-                sh.actor_rollout_sharded_stats(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
-                                               sl(rewards, rs), rs, store.snap if store is not None else None,
-                                               store.halo if st_sh else None, row0 + done, stats.stats, srow0 + done)
-                if store is not None:
-                    store.commit_rows(k)
-            elif sharded and store is not None:  # ... and the tick's state, scalars and halo rows
-                sh.actor_rollout_sharded_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
-                                              sl(rewards, rs), rs, store.snap, store.halo, row0 + done)
-                store.commit_rows(k)
-            elif sharded:  # C loop: ring halo + actor + count allreduce + step per tick (RCCL)
-                sh.actor_rollout_sharded(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
-                                         sl(rewards, rs), rs)
+            if stats is not None and done == 0:
+                stats.record_power(srow0)
+            # optional, inside the launch sequence: the store's snapshot rows (after the earlier windows'), stats rows
+            rows = dict(snap=store.snap if store is not None else None, row0=row0 + done,
+                        stats=stats.stats if stats is not None else None, stats_row0=srow0 + done)
+            a = (ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps, sl(rewards, rs), rs)
+            if sharded:  # C loop: ring halo + actor + count allreduce + step per tick (a sharded store: + halo rows)
+                sh.actor_rollout_sharded(*a, halo=getattr(store, "halo", None), **rows)
             else:
-                g = use_graph and (k == n_ticks or not (rs or as_ or ps))
-                if stats is not None:  # (and the store's snapshot rows, when both are given)
-                    if done == 0:
-                        stats.record_power(srow0)
-                    sh.actor_rollout_stats(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
-                                           sl(rewards, rs), rs, store.snap if store is not None else None,
-                                           row0 + done, stats.stats, srow0 + done, g)
-                    if store is not None:
-                        store.commit_rows(k)
-                elif store is not None:  # this window's snapshot rows follow the previous windows'
-                    sh.actor_rollout_snap(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps,
-                                          sl(rewards, rs), rs, store.snap, row0 + done, g)
-                    store.commit_rows(k)
-                else:
-                    sh.actor_rollout(ticks, osc, spec, sl(actions, as_), as_, sl(probs, ps), ps, sl(rewards, rs), rs, g)
+                sh.actor_rollout(*a, use_graph=use_graph and (k == n_ticks or not (rs or as_ or ps)), **rows)
+            if store is not None:
+                store.commit_rows(k)
             env._P_dev_valid = True
             env.finish_grid_step()
             if stats is not None:  # tick t's post-step signal is tick t + 1's s_prev; the last one's is the grid's

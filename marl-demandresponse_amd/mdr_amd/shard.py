@@ -402,29 +402,64 @@ class HipShard:
                                        L.ptr(prob), L.ptr(probs), L.ptr(obs_out), int(count_next),
                                        self.stream()), "mdr_actor_act")
 
-    def actor_rollout(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
-                      use_graph=True):
-        """n ticks of actor -> step in one C call (graph-captured, replayed on the current stream).
-        ``ticks``: TickWindow; ``obs_sc``: float64 [n, 4] array in the mdr_obs_scalars layout."""
+    @staticmethod
+    def _rollout_rows(ticks, obs_sc, snap, stats):
+        """(n, obs_sc as float64 [n, 4], snap / stats / its row count or NULL / NULL / 0, the answering entry point's suffix)"""
         n = len(ticks)
         obs_sc = np.ascontiguousarray(obs_sc, np.float64)
         assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
-                                           L.ptr(action), act_stride, L.ptr(prob), prob_stride, L.ptr(reward),
-                                           rew_stride, L.ptr(self.p_dev), int(use_graph), self.stream()),
-                "mdr_actor_rollout")
+        return (n, obs_sc, C.byref(snap) if snap is not None else None, L.ptr(stats),
+                int(stats.shape[0]) if stats is not None else 0,
+                "_stats" if stats is not None else "_snap" if snap is not None else "")
 
-    def actor_rollout_sharded(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
-                              rew_stride):
-        """n ticks of ring halo -> actor -> count allreduce -> step over the RCCL communicator
-        (mdr_actor_rollout_sharded), on the caller's current stream."""
-        n = len(ticks)
-        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
-        assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout_sharded(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
-                                                   L.ptr(action), act_stride, L.ptr(prob), prob_stride,
-                                                   L.ptr(reward), rew_stride, L.ptr(self.p_dev), self.stream()),
-                "mdr_actor_rollout_sharded")
+    def actor_rollout(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride, *,
+                      snap=None, row0: int = 0, stats=None, stats_row0: int = 0, use_graph=True):
+        """n ticks of actor -> step in one C call (graph-captured, replayed on the current stream).
+        ``ticks``: TickWindow; ``obs_sc``: float64 [n, 4] array in the mdr_obs_scalars layout.
+        ``snap`` (an ``mdr_snap``): tick t's pre-step state also goes into its row ``row0 + t``;
+        ``stats`` (device float64 [rows, 16]): tick t's stats row into ``stats[stats_row0 + t]``.  One entry point,
+        mdr_actor_rollout_stats: without rows mdr_actor_rollout_snap, without a snapshot mdr_actor_rollout."""
+        n, osc, snap_p, stats_p, stats_rows, sfx = self._rollout_rows(ticks, obs_sc, snap, stats)
+        rc = self.lib.mdr_actor_rollout_stats(self.ctx, n, ticks.ptr(), osc.ctypes.data, C.byref(spec), L.ptr(action),
+                                              act_stride, L.ptr(prob), prob_stride, L.ptr(reward), rew_stride,
+                                              L.ptr(self.p_dev), int(use_graph), snap_p, int(row0), stats_p,
+                                              stats_rows, int(stats_row0), self.stream())
+        L.check(rc, "mdr_actor_rollout" + sfx)
+
+    def actor_rollout_sharded(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                              *, snap=None, halo=None, row0: int = 0, stats=None, stats_row0: int = 0):
+        """n ticks of ring halo -> actor -> count allreduce -> step over the context's communicator, on
+        the caller's current stream.  ``snap`` / ``halo`` (``mdr_snap`` / ``mdr_snap_halo``): tick t's
+        pre-step state, obs scalars and ring halo into their row ``row0 + t``; ``stats``: tick t's stats
+        row into ``stats[stats_row0 + t]`` — partial rows per tick, one exchange behind the loop.  One entry
+        point, mdr_actor_rollout_sharded_stats, which reduces to the plainer two as ``actor_rollout``'s does."""
+        n, osc, snap_p, stats_p, stats_rows, sfx = self._rollout_rows(ticks, obs_sc, snap, stats)
+        rc = self.lib.mdr_actor_rollout_sharded_stats(
+            self.ctx, n, ticks.ptr(), osc.ctypes.data, C.byref(spec), L.ptr(action), act_stride, L.ptr(prob),
+            prob_stride, L.ptr(reward), rew_stride, L.ptr(self.p_dev), snap_p,
+            C.byref(halo) if halo is not None else None, int(row0), stats_p, stats_rows, int(stats_row0), self.stream())
+        L.check(rc, "mdr_actor_rollout_sharded" + sfx)
+
+    # (the four names tests and tools call positionally)
+    def actor_rollout_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                           snap, row0: int, use_graph=True):
+        self.actor_rollout(ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                           snap=snap, row0=row0, use_graph=use_graph)
+
+    def actor_rollout_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                            snap, row0: int, stats, stats_row0: int, use_graph=True):
+        self.actor_rollout(ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                           snap=snap, row0=row0, stats=stats, stats_row0=stats_row0, use_graph=use_graph)
+
+    def actor_rollout_sharded_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
+                                   rew_stride, snap, halo, row0: int):
+        self.actor_rollout_sharded(ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                                   snap=snap, halo=halo, row0=row0)
+
+    def actor_rollout_sharded_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
+                                    rew_stride, snap, halo, row0: int, stats, stats_row0: int):
+        self.actor_rollout_sharded(ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
+                                   snap=snap, halo=halo, row0=row0, stats=stats, stats_row0=stats_row0)
 
     # ------------------------------------------------------------------ replay snapshots
     def snapshot(self, snap, row: int, scalars, use_p_dev=True):
@@ -433,18 +468,6 @@ class HipShard:
         L.check(self.lib.mdr_snapshot(self.ctx, C.byref(snap), int(row), C.byref(scalars),
                                       L.ptr(self.p_dev) if use_p_dev else 0, self.stream()), "mdr_snapshot")
 
-    def actor_rollout_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
-                           snap, row0: int, use_graph=True):
-        """``actor_rollout`` that also records tick t's pre-step state into row ``row0 + t`` of ``snap``
-        (mdr_actor_rollout_snap)."""
-        n = len(ticks)
-        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
-        assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout_snap(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
-                                                L.ptr(action), act_stride, L.ptr(prob), prob_stride, L.ptr(reward),
-                                                rew_stride, L.ptr(self.p_dev), int(use_graph), C.byref(snap),
-                                                int(row0), self.stream()), "mdr_actor_rollout_snap")
-
     # ------------------------------------------------------------------ per-tick stats rows
     def tick_stats(self, reward, out, use_p_dev=True, p_host: float = 0.0):
         """out (device float64 [16]) <- mdr_tick_stats of the current (post-step) state: the 12
@@ -452,21 +475,6 @@ class HipShard:
         ``p_host``), three zeros.  Asynchronous."""
         L.check(self.lib.mdr_tick_stats(self.ctx, L.ptr(reward), L.ptr(self.p_dev) if use_p_dev else 0,
                                         float(p_host), L.ptr(out), self.stream()), "mdr_tick_stats")
-
-    def actor_rollout_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward, rew_stride,
-                            snap, row0: int, stats, stats_row0: int, use_graph=True):
-        """``actor_rollout_snap`` (``snap`` may be None) that also writes tick t's stats row into
-        ``stats[stats_row0 + t]`` (device float64 [rows, 16]) inside the same launch sequence
-        (mdr_actor_rollout_stats)."""
-        n = len(ticks)
-        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
-        assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout_stats(self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec),
-                                                 L.ptr(action), act_stride, L.ptr(prob), prob_stride, L.ptr(reward),
-                                                 rew_stride, L.ptr(self.p_dev), int(use_graph),
-                                                 C.byref(snap) if snap is not None else None, int(row0),
-                                                 L.ptr(stats), int(stats.shape[0]), int(stats_row0), self.stream()),
-                "mdr_actor_rollout_stats")
 
     # ------------------------------------------------------------------ stats rows of a sharded cluster
     def stats_exchange_ranks(self, world: int, rank: int) -> None:
@@ -511,20 +519,6 @@ class HipShard:
             L.check(rc, "mdr_rollout_sharded_stats")
         return rc
 
-    def actor_rollout_sharded_stats(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
-                                    rew_stride, snap, halo, row0: int, stats, stats_row0: int):
-        """``actor_rollout_sharded_snap`` (``snap`` may be None) that also writes tick t's stats row
-        into ``stats[stats_row0 + t]`` — partial rows per tick, one exchange behind the loop
-        (mdr_actor_rollout_sharded_stats)."""
-        n = len(ticks)
-        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
-        assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout_sharded_stats(
-            self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec), L.ptr(action), act_stride, L.ptr(prob),
-            prob_stride, L.ptr(reward), rew_stride, L.ptr(self.p_dev), C.byref(snap) if snap is not None else None,
-            C.byref(halo) if halo is not None else None, int(row0), L.ptr(stats), int(stats.shape[0]),
-            int(stats_row0), self.stream()), "mdr_actor_rollout_sharded_stats")
-
     def obs_gather(self, spec, snap, rows: int, idx, out):
         """out float32 [len(idx), n_feat] <- the obs rows of transitions ``idx`` (device int64:
         tick * n_local + house) over the first ``rows`` snapshot rows (mdr_obs_gather)."""
@@ -540,19 +534,6 @@ class HipShard:
                                               C.byref(halo) if halo is not None else None, int(row),
                                               C.byref(scalars), L.ptr(self.p_dev) if use_p_dev else 0,
                                               L.ptr(halo_src), self.stream()), "mdr_snapshot_sharded")
-
-    def actor_rollout_sharded_snap(self, ticks, obs_sc, spec, action, act_stride, prob, prob_stride, reward,
-                                   rew_stride, snap, halo, row0: int):
-        """``actor_rollout_sharded`` that also records tick t's pre-step state, obs scalars and ring
-        halo into row ``row0 + t`` of ``snap`` / ``halo`` (mdr_actor_rollout_sharded_snap; ``snap`` None:
-        ``actor_rollout_sharded``)."""
-        n = len(ticks)
-        obs_sc = np.ascontiguousarray(obs_sc, np.float64)
-        assert obs_sc.shape == (n, 4)
-        L.check(self.lib.mdr_actor_rollout_sharded_snap(
-            self.ctx, n, ticks.ptr(), obs_sc.ctypes.data, C.byref(spec), L.ptr(action), act_stride, L.ptr(prob),
-            prob_stride, L.ptr(reward), rew_stride, L.ptr(self.p_dev), C.byref(snap) if snap is not None else None,
-            C.byref(halo) if halo is not None else None, int(row0), self.stream()), "mdr_actor_rollout_sharded_snap")
 
     def obs_gather_sharded(self, spec, snap, halo, rows: int, idx, out):
         """``obs_gather`` on a shard: ``idx`` local (tick * n_local + local house), the ring sources

@@ -420,3 +420,90 @@ def test_refusals(torch_gpu):
         other.shard.actor_rollout_stats(other.driver_window(1), np.zeros((1, 4)), spec_o, None, 0, None, 0, rew, n,
                                         None, 0, torch.zeros((4, 16), dtype=torch.float64, device="cuda"), 0)
     assert float(out.min()) == -7.0
+
+
+# ------------------------------------------------------------------ 7. actor graph keys partition the calls
+def test_actor_graph_keys_partition_the_calls(torch_gpu):
+    """One graph per (snapshot rows?, stats rows?) form of the same call, each replayed by its repeat:
+    a snapshot and a stats buffer are part of the key, ``row0`` only with a snapshot.  96 houses: three
+    full 32-house actor tiles."""
+    import ctypes as C
+
+    from mdr_amd import _lib as L
+    from mdr_amd.actor import DeviceActor, make_actor
+    from mdr_amd.replay import RolloutStore
+    from mdr_amd.services import RolloutStats
+
+    torch = torch_gpu
+    n, T = 96, 2
+    env = make_env(n, seed=8)
+    sh = env.shard
+    da = DeviceActor(env, make_actor(env.obs_spec().n_feat, 2, [100, 100], seed=3).to("cuda"))
+    assert da.fused()
+    da.rollout(1)  # (off the reset state; its own graph is cached before the counts below)
+    store, stats = RolloutStore(env, 8), RolloutStats(env, 8)
+    spec, _sc, _keep = env.bound_obs_spec()
+    sh.p_dev.fill_(float(env._P_host))
+    solar0 = float(env._solar)
+    ticks = env.driver_window(T)
+    osc = np.zeros((T, 4), np.float64)
+    osc[:, 1], osc[0, 2], osc[1:, 2], osc[:, 3] = ticks.s_prev, solar0, ticks.solar[:-1], ticks.t_od_prev
+    rew = torch.empty((T, n), dtype=torch.float64, device="cuda")
+    act = torch.empty((T, n), dtype=torch.uint8, device="cuda")
+    state = {k: getattr(sh, k).clone() for k in ("t_air", "t_mass", "hvac", "p_dev")}
+    snap_bufs = (store.t_air, store.t_mass, store.hvac, store.scalars)
+
+    def call(form, row0=0):
+        """The same two ticks from the same state; returns what the call wrote."""
+        for k, v in state.items():
+            getattr(sh, k).copy_(v)
+        for b in (rew, act, stats.stats) + snap_bufs:
+            b.zero_()
+        a = (ticks, osc, spec, act, n, None, 0, rew, n)
+        if form == "plain":
+            sh.actor_rollout(*a)
+        elif form == "plain_by_snap":  # (the C entry point itself: snap == NULL, row0 ignored)
+            L.check(sh.lib.mdr_actor_rollout_snap(sh.ctx, T, ticks.ptr(), osc.ctypes.data, C.byref(spec), L.ptr(act), n,
+                                                  0, 0, L.ptr(rew), n, L.ptr(sh.p_dev), 1, None, row0, sh.stream()),
+                    "mdr_actor_rollout_snap")
+        elif form == "snap":
+            sh.actor_rollout_snap(*a, store.snap, row0)
+        elif form == "stats":
+            sh.actor_rollout_stats(*a, None, 0, stats.stats, 0)
+        else:
+            sh.actor_rollout_stats(*a, store.snap, row0, stats.stats, 0)
+        return [x.clone() for x in (rew, act, stats.stats) + snap_bufs] + [getattr(sh, k).clone() for k in state]
+
+    forms = ("plain", "snap", "stats", "both")
+    g0 = sh.graph_info()
+    first = {f: call(f) for f in forms}
+    g1 = sh.graph_info()
+    assert g1["actor_graphs"] == g0["actor_graphs"] + 4 and g1["actor_launches"] == g0["actor_launches"] + 4
+    again = {f: call(f) for f in forms}
+    g2 = sh.graph_info()
+    assert g2["actor_graphs"] == g1["actor_graphs"] and g2["actor_launches"] == g1["actor_launches"] + 4
+    for f in forms:
+        for i, (x, y) in enumerate(zip(first[f], again[f])):
+            assert torch.equal(x, y), (f, i)
+    # the forms ran the same ticks, and each wrote exactly its own rows
+    for f in forms[1:]:
+        assert torch.equal(first[f][0], first["plain"][0]) and torch.equal(first[f][1], first["plain"][1]), f
+    assert float(first["plain"][0].abs().max()) > 0
+    for f in forms:
+        assert bool(first[f][2][:T].any()) == (f in ("stats", "both")), f
+        assert bool(first[f][3][:T].any()) == (f in ("snap", "both")), f
+    assert torch.equal(first["both"][2], first["stats"][2])
+    for i in range(3, 7):
+        assert torch.equal(first["both"][i], first["snap"][i]), i
+
+    # without a snapshot row0 is no part of the key; with one it is
+    out = call("plain_by_snap", row0=5)
+    g3 = sh.graph_info()
+    assert g3["actor_graphs"] == g2["actor_graphs"] and g3["actor_launches"] == g2["actor_launches"] + 1
+    for i, (x, y) in enumerate(zip(first["plain"], out)):
+        assert torch.equal(x, y), i
+    out = call("snap", row0=5)
+    g4 = sh.graph_info()
+    assert g4["actor_graphs"] == g3["actor_graphs"] + 1 and g4["actor_launches"] == g3["actor_launches"] + 1
+    assert torch.equal(out[0], first["snap"][0]) and torch.equal(out[3][5:5 + T], first["snap"][3][:T])
+    assert not bool(out[3][:T].any())
