@@ -162,7 +162,8 @@ struct WinDrv {
 };
 // SIMPLE: deadband 0 and norm_temp 1 (reward without branches / division); FORM: the per-tick
 // thermal update, MDR_THERMAL_EXACT (the reference's expression) or MDR_THERMAL_AFFINE (its
-// per-window transition coefficients, mdr_kernels.hip K1W)
+// per-window transition coefficients, mdr_kernels.hip K1W).  The per-house body of k_step_window,
+// k_step_group and k_step_closed (load, form, tick loop, store) is one struct there, WinHouses.
 // COMMON (common_L2 / common_max_error / mixture, SIMPLE = false only): every tick each wave also
 // writes {sum pen_i / N, max pen_i} over its tile to pen.part[tick][tile] (tiles padded to whole
 // blocks: gridDim.x * 4 per tick) and block 0 the tick's signal term to pen.sig[tick]; the reward

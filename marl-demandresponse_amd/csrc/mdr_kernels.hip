@@ -355,6 +355,13 @@ __device__ __forceinline__ bool pick_action(int mode, const uint8_t* action, uin
   return ctrl_deadband(T, tgt, deadband, hv_on(w0));
 }
 
+// the individual_L2 reward of a house from its temperature penalty and the tick's signal term
+// (rewards_calculator.py:135-203); x / 1.0 == x exactly: the default normaliser costs no division
+__device__ __forceinline__ double reward_individual(const KParams& p, double pen, double sig_term) {
+  const double tpen = p.alpha_temp * pen;
+  return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term);
+}
+
 // Loads/stores at an SGPR base + 32-bit VGPR byte offset (computed in 32 bits, so the compiler
 // emits the saddr form instead of a 64-bit address add per array).
 template <typename V>
@@ -487,11 +494,8 @@ __global__ void __launch_bounds__(256) k_step_t(KParams p, const uint8_t* __rest
       rc_apply_t<false>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
     }
     pen[h] = deadband_l2(tg[h], p.deadband, reward_lag ? T[h] : Tn[h]);
-    // x / 1.0 == x exactly: the default normaliser (integer target) costs no division
-    const double tpen = p.alpha_temp * pen[h];
-    rw[h] = p.penalty_mode == MDR_PEN_INDIVIDUAL_L2
-                ? -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term)
-                : pen[h];  // finalised by k_reward_finalize
+    rw[h] = p.penalty_mode == MDR_PEN_INDIVIDUAL_L2 ? reward_individual(p, pen[h], sig_term)
+                                                    : pen[h];  // finalised by k_reward_finalize
     on1[h] = false;
     if (lookahead) {
       bool an;
@@ -778,8 +782,7 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
         kc = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
         rc_apply_t<false>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
       }
-      const double tpen = p.alpha_temp * deadband_l2(tg[h], p.deadband, Tn[h]);
-      rw[h] = -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term);
+      rw[h] = reward_individual(p, deadband_l2(tg[h], p.deadband, Tn[h]), sig_term);
       on1[h] = false;
       if (LA) {
         bool an;
@@ -955,6 +958,18 @@ __device__ __forceinline__ RcWin rc_window(double ua, double ca, double cm, doub
   w.rCa = recip(ca);
   w.rc = recip(ua);
   w.rd = recip(w.k.r2 - w.k.r1);
+  w.UaHm = ua + hm;
+  return w;
+}
+
+// The same for parameters outside the fast-division range: IEEE division (identical bits).  The slow
+// path of rc_apply_win reads only k, the three nb and UaHm; the rest is a constant, never undefined.
+__device__ __forceinline__ RcWin rc_window_ieee(double ua, double ca, double cm, double hm, double dt) {
+  RcWin w;
+  w.k = rc_coeffs_t<false>(ua, ca, cm, hm, dt);
+  w.rCa = Recip{0.0, -ca, 0.0};
+  w.rc = Recip{0.0, -ua, 0.0};
+  w.rd = Recip{0.0, -(w.k.r2 - w.k.r1), 0.0};
   w.UaHm = ua + hm;
   return w;
 }
@@ -1446,6 +1461,236 @@ __device__ __forceinline__ AffWin aff_window(double ua, double ca, double cm, do
   return w;
 }
 
+// The houses of a wave tile, in registers over a launch: the one per-house body of k_step_window,
+// k_step_group and k_step_closed, run as load, form, { begin_window, ticks, end_window } per window,
+// store (k_step_closed: load, form, its own tick loop on T / Tm / w, store).  The kernels agree bit
+// for bit because these statements are the only copy.  FORM: MDR_THERMAL_EXACT runs the reference's
+// expression per tick (rc_apply_win: bit-identical to the one-tick kernels); MDR_THERMAL_AFFINE the
+// per-window transition above, the state in Kelvin between begin_window and end_window.  Two windows
+// of one launch take the round trip two launches take: end_window leaves Celsius (tk - 273.0),
+// begin_window reloads it (+ 273.0) and forms win_finite again from the coefficients and tk, tmk, hk.
+template <int HPT, int FORM>
+struct WinHouses {
+  static constexpr bool AFF = FORM == MDR_THERMAL_AFFINE;
+  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
+  uint32_t w[HPT];  // the FSM word (open-loop sources: the one at the end of the stepped windows)
+  int cls[HPT];
+  bool params_ok;                         // the parameters are in the fast-division ranges
+  double qc[HPT], lo_tg[HPT], hi_tg[HPT];  // heat when ON; deadbandL2 thresholds (utils.py:4-23)
+  RcWin rw[AFF ? 1 : HPT];                // per-house constants of the form
+  AffWin aw[AFF ? HPT : 1];
+  double tk[HPT], tmk[HPT], hk[HPT];  // AFFINE: Kelvin state, Kelvin penalty threshold
+  bool win_finite;                    // AFFINE: every coefficient and temperature finite
+
+  // ---- state + parameters, once per launch (fsm: where the caller keeps the houses' FSM words)
+  __device__ __forceinline__ void load(const KParams& p, const WinTile<HPT>& t, const uint32_t* fsm) {
+    params_ok = !*p.params_bad && p.fast_tick_ok;
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) {
+      const uint32_t i = t.idx[h];
+      T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
+      ca[h] = p.ca[i]; cm[h] = p.cm[i];
+      w[h] = fsm[i];
+      cls[h] = p.cap_idx[i];
+    }
+  }
+
+  // ---- what depends on the parameters alone, once per launch
+  __device__ __forceinline__ void form(const KParams& p) {
+    double q_on[kWinCap];
+#pragma unroll
+    for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) {
+      qc[h] = q_on[0];
+#pragma unroll
+      for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
+      hi_tg[h] = tg[h] + p.deadband / 2.0;
+      lo_tg[h] = tg[h] - p.deadband / 2.0;
+    }
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) {
+      if constexpr (AFF) {
+        aw[h] = aff_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt, qc[h], params_ok);
+        hk[h] = hi_tg[h] + 273.0;
+      } else {
+        rw[h] = params_ok ? rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt)
+                          : rc_window_ieee(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
+      }
+    }
+  }
+
+  // ---- what a window forms from the Celsius state it finds
+  __device__ __forceinline__ void begin_window() {
+    win_finite = true;
+    if constexpr (AFF) {
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        tk[h] = T[h] + 273.0;
+        tmk[h] = Tm[h] + 273.0;
+        const AffWin& a = aw[h];
+        const double s = a.tt + a.tm + a.tq + a.to + a.qt + a.mt + a.mm + a.mq + a.mo + a.qm + tk[h] + tmk[h] + hk[h];
+        win_finite = win_finite && (s - s == 0.0);
+      }
+      win_finite = __all(win_finite);
+    }
+  }
+
+  // ---- the K ticks of a window: heat source from the stored ON masks, thermal update, reward
+  // rec: the window's tick records; onb_w: the wave's mask rows of the window, [tick][HPT]; reward
+  // row j0 + j is tick j's.  KA: the drivers come from dv, lane j of {ns_lo, ns_hi} holds tick j's
+  // negated signal penalty (read with v_readlane) and rec is not read here.
+  // COMMON (the common penalty modes, rewards_calculator.py:46-181): the cluster's mean and max of the
+  // per-house temperature penalty couple the houses once per tick.  Each tick the wave reduces its
+  // tile's {sum pen_i / N, max pen_i} with a fixed xor butterfly (no atomics, no block barrier: the
+  // order never depends on scheduling) and lane 0 stores the pair to wp.part[tick][tile]; every wave
+  // stores all K pairs (an empty tile: zeros), so the buffer is never cleared.  The reward row gets
+  // the raw pen_i (mixture) or nothing.
+  template <bool SIMPLE, bool KA, bool COMMON>
+  __device__ __forceinline__ void ticks(const KParams& p, const WinTile<HPT>& t, int K, const double* __restrict__ rec,
+                                        const uint64_t* onb_w, double* reward, int j0, int64_t rew_stride, const WinDrv& dv,
+                                        uint32_t ns_lo, uint32_t ns_hi, const WinPen& wp) {
+    static_assert(!(COMMON && SIMPLE), "the common penalty modes use the general dead-band penalty");
+    // the tick's scalars (record, ON masks) are loaded one tick ahead (scalar loads, no vector work)
+    auto lane_nsig = [&](int j) { return __longlong_as_double((long long)readlane_u64(ns_lo, ns_hi, j)); };
+    double r_od = KA ? dv.od_k[0] : rec[0], r_sol = KA ? dv.solar[0] : rec[1], r_sig = KA ? lane_nsig(0) : rec[2];
+    uint64_t r_ok = KA ? (uint64_t)(dv.ok & 1u) : __double_as_longlong(rec[3]);  // 1.0 or 0.0: compared as bits (scalar unit)
+    uint64_t r_on[HPT];
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[h];
+    const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
+    const double nalpha = -p.alpha_temp;
+    const bool mix = COMMON && p.penalty_mode == MDR_PEN_MIXTURE;  // COMMON: the raw pen_i goes to the reward row
+    for (int j = 0; j < K; ++j) {
+      [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
+      const double od_k = r_od, solar = r_sol, nsig = r_sig;
+      const bool tick_ok = r_ok != 0;
+      uint64_t on_m[HPT];
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) on_m[h] = r_on[h];
+      const int jn = j + 1 < K ? j + 1 : j;
+      if (KA) {
+        r_od = dv.od_k[jn];
+        r_sol = dv.solar[jn];
+        r_sig = lane_nsig(jn);
+        r_ok = (dv.ok >> jn) & 1u;
+      } else {
+        r_od = rec[jn * kWinRec + 0];
+        r_sol = rec[jn * kWinRec + 1];
+        r_sig = rec[jn * kWinRec + 2];
+        r_ok = __double_as_longlong(rec[jn * kWinRec + 3]);
+      }
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[jn * HPT + h];
+      char* rrow = reinterpret_cast<char*>(reward + (int64_t)(j0 + j) * rew_stride);
+      // the reward from the new Celsius temperature Tn (Kelvin tkn on the affine path)
+      auto reward_of = [&](int h, double Tn, double tkn, auto fast_c) {
+        constexpr bool F = decltype(fast_c)::value;
+        if (SIMPLE) {  // deadband 0, norm_temp 1 (the defaults): no branches, no division
+          // on the fast path Tn is finite, so the reference's two comparisons reduce to x * x (x = 0
+          // gives +0 either way); off it a NaN gives 0.  -(a * pen + s) == (-a) * pen + (-s) bit for
+          // bit: negation is exact and rounding is symmetric, and with a, s >= +0 (mdr_capi checks
+          // the signs for SIMPLE) the only zero sum is +0 + +0, whose negation is -0 either way
+          if (AFF && F) {
+            const double x = tkn - hk[h];
+            return __builtin_fma(nalpha, x * x, nsig);
+          }
+          const double x = Tn - hi_tg[h];
+          const double pen = F ? x * x : deadband_l2_0(hi_tg[h], Tn);
+          return nalpha * pen + nsig;
+        }
+        double pen = 0.0;
+        if (hi_tg[h] < Tn) { const double x = Tn - hi_tg[h]; pen = x * x; }
+        else if (lo_tg[h] > Tn) { const double x = lo_tg[h] - Tn; pen = x * x; }
+        if constexpr (COMMON) return pen;  // (deadband_l2's bits; finalised by k_win_reward_common)
+        return reward_individual(p, pen, -nsig);
+      };
+      if constexpr (AFF) {
+        auto houses = [&](auto fast_c) {
+#pragma unroll
+          for (int h = 0; h < HPT; ++h) {
+            const AffWin& a = aw[h];
+            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
+            const double ut = __builtin_fma(a.to, od_k, __builtin_fma(a.tq, solar, on ? a.qt : 0.0));
+            const double um = __builtin_fma(a.mo, od_k, __builtin_fma(a.mq, solar, on ? a.qm : 0.0));
+            const double tkn = __builtin_fma(a.tt, tk[h], __builtin_fma(a.tm, tmk[h], ut));
+            const double tmkn = __builtin_fma(a.mt, tk[h], __builtin_fma(a.mm, tmk[h], um));
+            tk[h] = tkn;
+            tmk[h] = tmkn;
+            const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
+            if constexpr (COMMON) pen_t[h] = r;
+            if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          }
+        };
+        if (win_finite && tick_ok) houses(std::true_type());
+        else houses(std::false_type());
+      } else {
+        // all lanes in range: the comparison masks themselves (v_cmp writes a lane mask) against exec
+        uint64_t ok_m = ~0ull;
+#pragma unroll
+        for (int h = 0; h < HPT; ++h)
+          ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
+        const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
+        auto houses = [&](auto fast_c) {
+          constexpr bool F = decltype(fast_c)::value;
+#pragma unroll
+          for (int h = 0; h < HPT; ++h) {
+            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
+            const double q = on ? qc[h] : 0.0;
+            double Tn, Tmn;
+            rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, solar, od_k, Tn, Tmn);
+            T[h] = Tn;
+            Tm[h] = Tmn;
+            const double r = reward_of(h, Tn, 0.0, fast_c);
+            if constexpr (COMMON) pen_t[h] = r;
+            if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+          }
+        };
+        if (fast) houses(std::true_type());
+        else houses(std::false_type());
+      }
+      if constexpr (COMMON) {
+        // the tile's {sum pen_i / N, max pen_i} (the terms of k_step_t: divided one by one), reduced
+        // over the wave in a fixed butterfly; row j of the partials is [gridDim.x * 4 tiles][2]
+        double sacc = 0.0, macc = 0.0;
+#pragma unroll
+        for (int h = 0; h < HPT; ++h)
+          if (t.v[h]) { sacc += pen_t[h] / (double)p.n_global; macc = fmax(macc, pen_t[h]); }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          sacc += __shfl_xor(sacc, off);
+          macc = fmax(macc, __shfl_xor(macc, off));
+        }
+        if ((threadIdx.x & 63) == 0) {
+          const size_t ntile = (size_t)gridDim.x * (blockDim.x >> 6);
+          *reinterpret_cast<double2*>(wp.part + ((size_t)j * ntile + t.tile) * 2) = make_double2(sacc, macc);
+        }
+      }
+    }
+  }
+
+  // ---- the Celsius a window leaves (what a launch stores and the next window reloads)
+  __device__ __forceinline__ void end_window() {
+    if constexpr (AFF) {
+#pragma unroll
+      for (int h = 0; h < HPT; ++h) {
+        T[h] = tk[h] - 273.0;
+        Tm[h] = tmk[h] - 273.0;
+      }
+    }
+  }
+
+  // ---- state back, once per launch
+  __device__ __forceinline__ void store(const KParams& p, const WinTile<HPT>& t) const {
+#pragma unroll
+    for (int h = 0; h < HPT; ++h)
+      if (t.v[h]) {
+        const uint32_t i = t.i0 + 64u * h;
+        p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w[h];
+      }
+  }
+};
+
 // One window of K ticks.  slot: this window's slot (red counts are folded into its tick records);
 // onb / wah: the window's ON lane masks and end-of-window FSM words (from k_count_window or the
 // previous launch's lookahead), replaced by the next window's when la_K > 0: then the FSM runs on
@@ -1453,16 +1698,9 @@ __device__ __forceinline__ AffWin aff_window(double ua, double ca, double cm, do
 // KA (the first window of a directly launched rollout): the tick drivers come as kernel arguments
 // (dv) and rec holds only each tick's P (the P-only k_win_reduce); lane j derives tick j's signal
 // penalty once (win_nsig, the reduce's expression) and the thermal loop reads it with v_readlane.
-// FORM: MDR_THERMAL_EXACT runs the reference's expression per tick (rc_apply_win: bit-identical to
-// the one-tick kernels); MDR_THERMAL_AFFINE the per-window transition above (Kelvin state kept in
-// registers for the window).
-// COMMON (the common penalty modes, rewards_calculator.py:46-181): the cluster's mean and max of the
-// per-house temperature penalty couple the houses once per tick.  Each tick the wave reduces its
-// tile's {sum pen_i / N, max pen_i} with a fixed xor butterfly (no atomics, no block barrier: the
-// order never depends on scheduling) and lane 0 stores the pair to pen.part[tick][tile]; every wave
-// of the grid stores all K pairs (an empty tile: zeros), so the buffer is never cleared.  Block 0
-// publishes the tick's signal term to pen.sig.  The reward row gets the raw pen_i (mixture) or
-// nothing; k_win_pen_reduce and k_win_reward_common, launched behind this kernel, finish it.
+// The houses' body is WinHouses (FORM, COMMON: see there).  COMMON: block 0 also publishes the
+// tick's signal term to pen.sig; k_win_pen_reduce and k_win_reward_common, launched behind this
+// kernel, finish the reward rows.
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool COMMON>
 __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* __restrict__ action,
                                                      int64_t act_stride, const TickArgs* __restrict__ tkp, int K,
@@ -1471,8 +1709,6 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
                                                      uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
                                                      unsigned long long* __restrict__ next_slot, WinDrv dv,
                                                      WinPen wp) {
-  static_assert(!(COMMON && SIMPLE), "the common penalty modes use the general dead-band penalty");
-  constexpr bool AFF = FORM == MDR_THERMAL_AFFINE;
   __shared__ unsigned s_cnt[4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6;
   const WinTile<HPT> t(p);
@@ -1503,203 +1739,25 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
     ns_hi = (uint32_t)((uint64_t)__double_as_longlong(ns) >> 32);
   }
 
-  // ---- state + parameters, once per window
-  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
-  uint32_t w_end[HPT];
-  int cls[HPT];
-  const bool params_ok = !*p.params_bad && p.fast_tick_ok;
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    const uint32_t i = t.idx[h];
-    T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
-    ca[h] = p.ca[i]; cm[h] = p.cm[i];
-    w_end[h] = wah[i];
-    cls[h] = p.cap_idx[i];
-  }
-  double q_on[kWinCap];
-#pragma unroll
-  for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
-  double qc[HPT], lo_tg[HPT], hi_tg[HPT];  // heat when ON; deadbandL2 thresholds (utils.py:4-23)
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    qc[h] = q_on[0];
-#pragma unroll
-    for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
-    hi_tg[h] = tg[h] + p.deadband / 2.0;
-    lo_tg[h] = tg[h] - p.deadband / 2.0;
-  }
-  // per-house constants of the form
-  RcWin rw[AFF ? 1 : HPT];
-  AffWin aw[AFF ? HPT : 1];
-  double tk[HPT], tmk[HPT], hk[HPT];  // AFFINE: Kelvin state, Kelvin penalty threshold
-  bool win_finite = true;             // AFFINE: every coefficient and temperature finite
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    if constexpr (AFF) {
-      aw[h] = aff_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt, qc[h], params_ok);
-      tk[h] = T[h] + 273.0;
-      tmk[h] = Tm[h] + 273.0;
-      hk[h] = hi_tg[h] + 273.0;
-      const AffWin& a = aw[h];
-      const double s = a.tt + a.tm + a.tq + a.to + a.qt + a.mt + a.mm + a.mq + a.mo + a.qm + tk[h] + tmk[h] + hk[h];
-      win_finite = win_finite && (s - s == 0.0);
-    } else if (params_ok) {
-      rw[h] = rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-    } else {  // IEEE division (identical bits; parameters outside the fast-division range)
-      rw[h].k = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-      rw[h].rCa.nb = -ca[h];
-      rw[h].rc.nb = -ua[h];
-      rw[h].rd.nb = -(rw[h].k.r2 - rw[h].k.r1);
-      rw[h].UaHm = ua[h] + hm[h];
-    }
-  }
-  if constexpr (AFF) win_finite = __all(win_finite);
-
-  // ---- the K ticks: heat source from the stored ON masks, thermal update, reward
-  // the tick's scalars (record, ON masks) are loaded one tick ahead (scalar loads, no vector work)
-  auto lane_nsig = [&](int j) { return __longlong_as_double((long long)readlane_u64(ns_lo, ns_hi, j)); };
-  double r_od = KA ? dv.od_k[0] : rec[0], r_sol = KA ? dv.solar[0] : rec[1], r_sig = KA ? lane_nsig(0) : rec[2];
-  uint64_t r_ok = KA ? (uint64_t)(dv.ok & 1u) : __double_as_longlong(rec[3]);  // 1.0 or 0.0: compared as bits (scalar unit)
-  uint64_t r_on[HPT];
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[h];
-  const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
-  const double nalpha = -p.alpha_temp;
-  const bool mix = COMMON && p.penalty_mode == MDR_PEN_MIXTURE;  // COMMON: the raw pen_i goes to the reward row
-  for (int j = 0; j < K; ++j) {
-    [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
-    const double od_k = r_od, solar = r_sol, nsig = r_sig;
-    const bool tick_ok = r_ok != 0;
-    uint64_t on_m[HPT];
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) on_m[h] = r_on[h];
-    const int jn = j + 1 < K ? j + 1 : j;
-    if (KA) {
-      r_od = dv.od_k[jn];
-      r_sol = dv.solar[jn];
-      r_sig = lane_nsig(jn);
-      r_ok = (dv.ok >> jn) & 1u;
-    } else {
-      r_od = rec[jn * kWinRec + 0];
-      r_sol = rec[jn * kWinRec + 1];
-      r_sig = rec[jn * kWinRec + 2];
-      r_ok = __double_as_longlong(rec[jn * kWinRec + 3]);
-    }
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[jn * HPT + h];
-    char* rrow = reinterpret_cast<char*>(reward + (int64_t)j * rew_stride);
-    // the reward from the new Celsius temperature Tn (Kelvin tkn on the affine path)
-    auto reward_of = [&](int h, double Tn, double tkn, auto fast_c) {
-      constexpr bool F = decltype(fast_c)::value;
-      if (SIMPLE) {  // deadband 0, norm_temp 1 (the defaults): no branches, no division
-        // on the fast path Tn is finite, so the reference's two comparisons reduce to x * x (x = 0
-        // gives +0 either way); off it a NaN gives 0.  -(a * pen + s) == (-a) * pen + (-s) bit for
-        // bit: negation is exact and rounding is symmetric, and with a, s >= +0 (mdr_capi checks
-        // the signs for SIMPLE) the only zero sum is +0 + +0, whose negation is -0 either way
-        if (AFF && F) {
-          const double x = tkn - hk[h];
-          return __builtin_fma(nalpha, x * x, nsig);
-        }
-        const double x = Tn - hi_tg[h];
-        const double pen = F ? x * x : deadband_l2_0(hi_tg[h], Tn);
-        return nalpha * pen + nsig;
-      }
-      double pen = 0.0;
-      if (hi_tg[h] < Tn) { const double x = Tn - hi_tg[h]; pen = x * x; }
-      else if (lo_tg[h] > Tn) { const double x = lo_tg[h] - Tn; pen = x * x; }
-      if constexpr (COMMON) return pen;  // (deadband_l2's bits; finalised by k_win_reward_common)
-      const double tpen = p.alpha_temp * pen;
-      return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + -nsig);
-    };
-    if constexpr (AFF) {
-      auto houses = [&](auto fast_c) {
-        constexpr bool F = decltype(fast_c)::value;
-#pragma unroll
-        for (int h = 0; h < HPT; ++h) {
-          const AffWin& a = aw[h];
-          const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
-          const double ut = __builtin_fma(a.to, od_k, __builtin_fma(a.tq, solar, on ? a.qt : 0.0));
-          const double um = __builtin_fma(a.mo, od_k, __builtin_fma(a.mq, solar, on ? a.qm : 0.0));
-          const double tkn = __builtin_fma(a.tt, tk[h], __builtin_fma(a.tm, tmk[h], ut));
-          const double tmkn = __builtin_fma(a.mt, tk[h], __builtin_fma(a.mm, tmk[h], um));
-          tk[h] = tkn;
-          tmk[h] = tmkn;
-          const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
-          if constexpr (COMMON) pen_t[h] = r;
-          if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
-        }
-      };
-      if (win_finite && tick_ok) houses(std::true_type());
-      else houses(std::false_type());
-    } else {
-      // all lanes in range: the comparison masks themselves (v_cmp writes a lane mask) against exec
-      uint64_t ok_m = ~0ull;
-#pragma unroll
-      for (int h = 0; h < HPT; ++h)
-        ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
-      const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
-      auto houses = [&](auto fast_c) {
-        constexpr bool F = decltype(fast_c)::value;
-#pragma unroll
-        for (int h = 0; h < HPT; ++h) {
-          const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
-          const double q = on ? qc[h] : 0.0;
-          double Tn, Tmn;
-          rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, solar, od_k, Tn, Tmn);
-          T[h] = Tn;
-          Tm[h] = Tmn;
-          const double r = reward_of(h, Tn, 0.0, fast_c);
-          if constexpr (COMMON) pen_t[h] = r;
-          if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
-        }
-      };
-      if (fast) houses(std::true_type());
-      else houses(std::false_type());
-    }
-    if constexpr (COMMON) {
-      // the tile's {sum pen_i / N, max pen_i} (the terms of k_step_t: divided one by one), reduced
-      // over the wave in a fixed butterfly; row j of the partials is [gridDim.x * 4 tiles][2]
-      double sacc = 0.0, macc = 0.0;
-#pragma unroll
-      for (int h = 0; h < HPT; ++h)
-        if (t.v[h]) { sacc += pen_t[h] / (double)p.n_global; macc = fmax(macc, pen_t[h]); }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        sacc += __shfl_xor(sacc, off);
-        macc = fmax(macc, __shfl_xor(macc, off));
-      }
-      if ((threadIdx.x & 63) == 0) {
-        const size_t ntile = (size_t)gridDim.x * (blockDim.x >> 6);
-        *reinterpret_cast<double2*>(wp.part + ((size_t)j * ntile + t.tile) * 2) = make_double2(sacc, macc);
-      }
-    }
-  }
-  if constexpr (AFF) {
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) {
-      T[h] = tk[h] - 273.0;
-      Tm[h] = tmk[h] - 273.0;
-    }
-  }
-
-  // ---- state back, once per window (the FSM word at the window's end came with the ON masks)
-#pragma unroll
-  for (int h = 0; h < HPT; ++h)
-    if (t.v[h]) {
-      const uint32_t i = t.i0 + 64u * h;
-      p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w_end[h];
-    }
+  // ---- the window (the FSM word at its end came with the ON masks)
+  WinHouses<HPT, FORM> hs;
+  hs.load(p, t, wah);
+  hs.form(p);
+  hs.begin_window();
+  hs.template ticks<SIMPLE, KA, COMMON>(p, t, K, rec, onb_w, reward, 0, rew_stride, dv, ns_lo, ns_hi, wp);
+  hs.end_window();
+  hs.store(p, t);
 
   // ---- lookahead: the next window's ON masks, FSM words and class counts
   if (la_K > 0) {
     uint64_t cmk[HPT][kWinCap];
-    win_classes<HPT>(t, cls, cmk);
-    win_run<ACT, HPT>(p, w_end, cmk, t, KA ? nullptr : tkp + K, KA ? dv.tick0 + (uint64_t)K : 0, la_K,
+    win_classes<HPT>(t, hs.cls, cmk);
+    win_run<ACT, HPT>(p, hs.w, cmk, t, KA ? nullptr : tkp + K, KA ? dv.tick0 + (uint64_t)K : 0, la_K,
                       ACT == MDR_ACT_BUFFER ? action + (int64_t)K * act_stride : nullptr, act_stride, s_cnt[wv],
                       onb_w);
 #pragma unroll
     for (int h = 0; h < HPT; ++h)
-      if (t.v[h]) wah[t.i0 + 64u * h] = w_end[h];
+      if (t.v[h]) wah[t.i0 + 64u * h] = hs.w[h];
     __syncthreads();
     win_flush(p, la_K, s_cnt, next_slot);
   }
@@ -1707,15 +1765,9 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
 
 // A group of g.nw <= kWinGroup consecutive windows of one rollout call, then the lookahead over the
 // g.la_nw windows of the next group (mdr_kernels.h WinGrp; individual_L2 only).  k_step_window's
-// pieces in k_step_window's order, with what it does once per window split in two:
-//   * once per launch: state, parameters, class, end word, thresholds, AffWin / RcWin, and at the end
-//     the state's write-back and the lookahead;
-//   * once per window: the tick loop, word for word (the same expressions in the same order), over
-//     that window's mask rows and tick records.
-// Between two windows of a group the values take the round trip they take between two k_step_window
-// launches, so no result moves by a bit: AFFINE stores Celsius (tk - 273.0) and reloads it
-// (+ 273.0), and win_finite is formed again from the coefficients and the new tk, tmk, hk; EXACT
-// carries T, Tm as they are.  params_ok is read once (nothing changes it inside a rollout call).
+// WinHouses pieces: load, form and store once per launch, { begin_window, ticks, end_window } once
+// per window over that window's mask rows, tick records and reward rows (the round trip between two
+// windows: see WinHouses).  params_ok is read once (nothing changes it inside a rollout call).
 // The group's last end word is the one in wah on entry: the producer of the group's masks left it
 // after its last window.  Each counted window has its own LDS count rows, so one barrier separates
 // the lookahead's runs from their flushes.  No wave waits for another wave's data.
@@ -1725,7 +1777,6 @@ __global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __
                                                     double* __restrict__ reward, int64_t rew_stride,
                                                     uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
                                                     WinDrv dv) {
-  constexpr bool AFF = FORM == MDR_THERMAL_AFFINE;
   __shared__ unsigned s_cnt[kWinGroup][4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6;
   const WinTile<HPT> t(p);
@@ -1745,194 +1796,34 @@ __global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __
     ns_hi = (uint32_t)((uint64_t)__double_as_longlong(ns) >> 32);
   }
 
-  // ---- state + parameters, once per launch
-  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
-  uint32_t w_end[HPT];
-  int cls[HPT];
-  const bool params_ok = !*p.params_bad && p.fast_tick_ok;
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    const uint32_t i = t.idx[h];
-    T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
-    ca[h] = p.ca[i]; cm[h] = p.cm[i];
-    w_end[h] = wah[i];
-    cls[h] = p.cap_idx[i];
-  }
-  double q_on[kWinCap];
-#pragma unroll
-  for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
-  double qc[HPT], lo_tg[HPT], hi_tg[HPT];  // heat when ON; deadbandL2 thresholds (utils.py:4-23)
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    qc[h] = q_on[0];
-#pragma unroll
-    for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
-    hi_tg[h] = tg[h] + p.deadband / 2.0;
-    lo_tg[h] = tg[h] - p.deadband / 2.0;
-  }
-  // per-house constants of the form
-  RcWin rw[AFF ? 1 : HPT];
-  AffWin aw[AFF ? HPT : 1];
-  double tk[HPT], tmk[HPT], hk[HPT];  // AFFINE: Kelvin state, Kelvin penalty threshold
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    if constexpr (AFF) {
-      aw[h] = aff_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt, qc[h], params_ok);
-      hk[h] = hi_tg[h] + 273.0;
-    } else if (params_ok) {
-      rw[h] = rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-    } else {  // IEEE division (identical bits; parameters outside the fast-division range)
-      rw[h].k = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-      rw[h].rCa.nb = -ca[h];
-      rw[h].rc.nb = -ua[h];
-      rw[h].rd.nb = -(rw[h].k.r2 - rw[h].k.r1);
-      rw[h].UaHm = ua[h] + hm[h];
-    }
-  }
-
-  const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
-  const double nalpha = -p.alpha_temp;
-  auto lane_nsig = [&](int j) { return __longlong_as_double((long long)readlane_u64(ns_lo, ns_hi, j)); };
+  // ---- the group's windows (the FSM word at the group's end came with the ON masks)
+  WinHouses<HPT, FORM> hs;
+  hs.load(p, t, wah);
+  hs.form(p);
   int tick_off = 0;  // the window's first tick, from the group's
   for (int gi = 0; gi < g.nw; ++gi) {
-    const int K = g.K[gi];
-    const double* __restrict__ rec = g.rec[gi];
-    const uint64_t* onb_g = onb_r + gi * (kWinMax * HPT);
-    // ---- what a k_step_window launch forms from the state it loads
-    bool win_finite = true;  // AFFINE: every coefficient and temperature finite
-    if constexpr (AFF) {
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) {
-        tk[h] = T[h] + 273.0;
-        tmk[h] = Tm[h] + 273.0;
-        const AffWin& a = aw[h];
-        const double s = a.tt + a.tm + a.tq + a.to + a.qt + a.mt + a.mm + a.mq + a.mo + a.qm + tk[h] + tmk[h] + hk[h];
-        win_finite = win_finite && (s - s == 0.0);
-      }
-      win_finite = __all(win_finite);
-    }
-
-    // ---- the K ticks: heat source from the stored ON masks, thermal update, reward
-    // the tick's scalars (record, ON masks) are loaded one tick ahead (scalar loads, no vector work)
-    double r_od = KA ? dv.od_k[0] : rec[0], r_sol = KA ? dv.solar[0] : rec[1], r_sig = KA ? lane_nsig(0) : rec[2];
-    uint64_t r_ok = KA ? (uint64_t)(dv.ok & 1u) : __double_as_longlong(rec[3]);  // 1.0 or 0.0: compared as bits (scalar unit)
-    uint64_t r_on[HPT];
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) r_on[h] = onb_g[h];
-    for (int j = 0; j < K; ++j) {
-      const double od_k = r_od, solar = r_sol, nsig = r_sig;
-      const bool tick_ok = r_ok != 0;
-      uint64_t on_m[HPT];
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) on_m[h] = r_on[h];
-      const int jn = j + 1 < K ? j + 1 : j;
-      if (KA) {
-        r_od = dv.od_k[jn];
-        r_sol = dv.solar[jn];
-        r_sig = lane_nsig(jn);
-        r_ok = (dv.ok >> jn) & 1u;
-      } else {
-        r_od = rec[jn * kWinRec + 0];
-        r_sol = rec[jn * kWinRec + 1];
-        r_sig = rec[jn * kWinRec + 2];
-        r_ok = __double_as_longlong(rec[jn * kWinRec + 3]);
-      }
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) r_on[h] = onb_g[jn * HPT + h];
-      char* rrow = reinterpret_cast<char*>(reward + (int64_t)(tick_off + j) * rew_stride);
-      // the reward from the new Celsius temperature Tn (Kelvin tkn on the affine path)
-      auto reward_of = [&](int h, double Tn, double tkn, auto fast_c) {
-        constexpr bool F = decltype(fast_c)::value;
-        if (SIMPLE) {  // (k_step_window's reward_of: see there)
-          if (AFF && F) {
-            const double x = tkn - hk[h];
-            return __builtin_fma(nalpha, x * x, nsig);
-          }
-          const double x = Tn - hi_tg[h];
-          const double pen = F ? x * x : deadband_l2_0(hi_tg[h], Tn);
-          return nalpha * pen + nsig;
-        }
-        double pen = 0.0;
-        if (hi_tg[h] < Tn) { const double x = Tn - hi_tg[h]; pen = x * x; }
-        else if (lo_tg[h] > Tn) { const double x = lo_tg[h] - Tn; pen = x * x; }
-        const double tpen = p.alpha_temp * pen;
-        return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + -nsig);
-      };
-      if constexpr (AFF) {
-        auto houses = [&](auto fast_c) {
-#pragma unroll
-          for (int h = 0; h < HPT; ++h) {
-            const AffWin& a = aw[h];
-            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
-            const double ut = __builtin_fma(a.to, od_k, __builtin_fma(a.tq, solar, on ? a.qt : 0.0));
-            const double um = __builtin_fma(a.mo, od_k, __builtin_fma(a.mq, solar, on ? a.qm : 0.0));
-            const double tkn = __builtin_fma(a.tt, tk[h], __builtin_fma(a.tm, tmk[h], ut));
-            const double tmkn = __builtin_fma(a.mt, tk[h], __builtin_fma(a.mm, tmk[h], um));
-            tk[h] = tkn;
-            tmk[h] = tmkn;
-            const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
-            if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
-          }
-        };
-        if (win_finite && tick_ok) houses(std::true_type());
-        else houses(std::false_type());
-      } else {
-        // all lanes in range: the comparison masks themselves (v_cmp writes a lane mask) against exec
-        uint64_t ok_m = ~0ull;
-#pragma unroll
-        for (int h = 0; h < HPT; ++h)
-          ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
-        const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
-        auto houses = [&](auto fast_c) {
-          constexpr bool F = decltype(fast_c)::value;
-#pragma unroll
-          for (int h = 0; h < HPT; ++h) {
-            const bool on = __builtin_amdgcn_inverse_ballot_w64(on_m[h]);
-            const double q = on ? qc[h] : 0.0;
-            double Tn, Tmn;
-            rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, solar, od_k, Tn, Tmn);
-            T[h] = Tn;
-            Tm[h] = Tmn;
-            const double r = reward_of(h, Tn, 0.0, fast_c);
-            if (t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
-          }
-        };
-        if (fast) houses(std::true_type());
-        else houses(std::false_type());
-      }
-    }
-    if constexpr (AFF) {  // (the Celsius a k_step_window launch stores; the next window reloads it)
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) {
-        T[h] = tk[h] - 273.0;
-        Tm[h] = tmk[h] - 273.0;
-      }
-    }
-    tick_off += K;
+    hs.begin_window();
+    hs.template ticks<SIMPLE, KA, false>(p, t, g.K[gi], g.rec[gi], onb_r + gi * (kWinMax * HPT), reward, tick_off,
+                                         rew_stride, dv, ns_lo, ns_hi, WinPen{});
+    hs.end_window();
+    tick_off += g.K[gi];
   }
-
-  // ---- state back, once per launch (the FSM word at the group's end came with the ON masks)
-#pragma unroll
-  for (int h = 0; h < HPT; ++h)
-    if (t.v[h]) {
-      const uint32_t i = t.i0 + 64u * h;
-      p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w_end[h];
-    }
+  hs.store(p, t);
 
   // ---- lookahead: the next group's ON masks, end word and class counts, window by window
   if (g.la_nw > 0) {
     uint64_t cmk[HPT][kWinCap];
-    win_classes<HPT>(t, cls, cmk);
+    win_classes<HPT>(t, hs.cls, cmk);
     for (int li = 0; li < g.la_nw; ++li) {
       const int la_K = g.la_K[li];
-      win_run<ACT, HPT>(p, w_end, cmk, t, KA ? nullptr : tkp + tick_off, KA ? dv.tick0 + (uint64_t)tick_off : 0, la_K,
+      win_run<ACT, HPT>(p, hs.w, cmk, t, KA ? nullptr : tkp + tick_off, KA ? dv.tick0 + (uint64_t)tick_off : 0, la_K,
                         ACT == MDR_ACT_BUFFER ? action + (int64_t)tick_off * act_stride : nullptr, act_stride,
                         s_cnt[li][wv], onb_w + li * (kWinMax * HPT));
       tick_off += la_K;
     }
 #pragma unroll
     for (int h = 0; h < HPT; ++h)
-      if (t.v[h]) wah[t.i0 + 64u * h] = w_end[h];
+      if (t.v[h]) wah[t.i0 + 64u * h] = hs.w[h];
     __syncthreads();
     for (int li = 0; li < g.la_nw; ++li) win_flush(p, g.la_K[li], s_cnt[li], g.la_slot[li]);
   }
@@ -2089,44 +1980,15 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const WinTile<HPT> t(p);
 
-  // ---- state + parameters, once per window
-  double T[HPT], Tm[HPT], ua[HPT], hm[HPT], tg[HPT], ca[HPT], cm[HPT];
-  uint32_t w[HPT];
-  int cls[HPT];
-  const bool params_ok = !*p.params_bad && p.fast_tick_ok;
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    const uint32_t i = t.idx[h];
-    T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
-    ca[h] = p.ca[i]; cm[h] = p.cm[i];
-    w[h] = p.hvac[i];
-    cls[h] = p.cap_idx[i];
-  }
-  double q_on[kWinCap];
-#pragma unroll
-  for (int c = 0; c < kWinCap; ++c) q_on[c] = p.q_on[c < p.n_cap ? c : 0];
-  double qc[HPT];  // heat when ON
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    qc[h] = q_on[0];
-#pragma unroll
-    for (int c = 1; c < kWinCap; ++c) qc[h] = cls[h] == c ? q_on[c] : qc[h];
-  }
+  // ---- state + parameters, once per window (WinHouses' EXACT form; the tick loop below is this
+  // kernel's own: controller, FSM, counts and stats)
+  WinHouses<HPT, MDR_THERMAL_EXACT> hs;
+  hs.load(p, t, p.hvac);
+  hs.form(p);
+  auto &T = hs.T, &Tm = hs.Tm, &ua = hs.ua, &hm = hs.hm, &tg = hs.tg, &qc = hs.qc;
+  auto& w = hs.w;
   uint64_t clm[HPT][kWinCap];  // class membership lane masks (houses of the shard only)
-  win_classes<HPT>(t, cls, clm);
-  RcWin rw[HPT];
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    if (params_ok) {
-      rw[h] = rc_window(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-    } else {  // IEEE division (identical bits; parameters outside the fast-division range)
-      rw[h].k = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-      rw[h].rCa.nb = -ca[h];
-      rw[h].rc.nb = -ua[h];
-      rw[h].rd.nb = -(rw[h].k.r2 - rw[h].k.r1);
-      rw[h].UaHm = ua[h] + hm[h];
-    }
-  }
+  win_classes<HPT>(t, hs.cls, clm);
 
   // ---- the K ticks; the tick's drivers are wave-uniform (scalar loads), read one tick ahead
   uint32_t cnt_v[kWinCap] = {0u, 0u, 0u, 0u};  // lane j: tick j's ON houses of the tile per class
@@ -2143,7 +2005,7 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
 #pragma unroll
     for (int h = 0; h < HPT; ++h)
       ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
-    const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
+    const bool fast = hs.params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
     // only the last row of a shared reward row (rew_stride == 0) is ever finalised
     const bool store = rew_stride != 0 || j == K - 1;
     char* rrow = reinterpret_cast<char*>(reward + (int64_t)j * rew_stride);
@@ -2166,7 +2028,7 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
         on_m[h] = __builtin_amdgcn_ballot_w64(on);
         const double q = on ? qc[h] : 0.0;
         double Tn, Tmn;
-        rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], rw[h], q, tk.solar, od_k, Tn, Tmn);
+        rc_apply_win<F>(T[h], Tm[h], ua[h], hm[h], hs.rw[h], q, tk.solar, od_k, Tn, Tmn);
         T[h] = Tn;
         Tm[h] = Tmn;
         const double pen = deadband_l2(tg[h], p.deadband, Tn);
@@ -2218,13 +2080,7 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
     }
   }
 
-  // ---- state back, once per window
-#pragma unroll
-  for (int h = 0; h < HPT; ++h)
-    if (t.v[h]) {
-      const uint32_t i = t.i0 + 64u * h;
-      p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w[h];
-    }
+  hs.store(p, t);
 
   // ---- the window's ON counts into its slot (the lookahead's tail of k_step_window)
   if (lane < K) {
@@ -2392,12 +2248,10 @@ __global__ void __launch_bounds__(256) k_probe_stream(KParams p, double* __restr
   *reinterpret_cast<double2*>(reward + i0) = make_double2(s0, s1);
 }
 
-// Fixed-order reduction of the per-block penalty partials -> partial2 = {sum pen/N, max pen}.
-__global__ void __launch_bounds__(256) k_pen_reduce(const double* __restrict__ pen_partial, int nblk,
-                                                    double* __restrict__ partial2) {
+// out[0], out[1] = {sum, max} of the block's 256 {s, m} in a fixed order: an LDS tree over stride-1
+// rows of doubles (lanes of a wave read consecutive 8-B words, no bank conflict)
+__device__ __forceinline__ void pen_tree(double s, double m, double* __restrict__ out) {
   __shared__ double ss[256], sm[256];
-  double s = 0.0, m = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += blockDim.x) { s += pen_partial[2 * b]; m = fmax(m, pen_partial[2 * b + 1]); }
   ss[threadIdx.x] = s;
   sm[threadIdx.x] = m;
   __syncthreads();
@@ -2408,7 +2262,15 @@ __global__ void __launch_bounds__(256) k_pen_reduce(const double* __restrict__ p
     }
     __syncthreads();
   }
-  if (threadIdx.x == 0) { partial2[0] = ss[0]; partial2[1] = sm[0]; }
+  if (threadIdx.x == 0) { out[0] = ss[0]; out[1] = sm[0]; }
+}
+
+// Fixed-order reduction of the per-block penalty partials -> partial2 = {sum pen/N, max pen}.
+__global__ void __launch_bounds__(256) k_pen_reduce(const double* __restrict__ pen_partial, int nblk,
+                                                    double* __restrict__ partial2) {
+  double s = 0.0, m = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += blockDim.x) { s += pen_partial[2 * b]; m = fmax(m, pen_partial[2 * b + 1]); }
+  pen_tree(s, m, partial2);
 }
 
 // the reward of a house under common_L2 / common_max_error / mixture from its own penalty, the
@@ -2455,12 +2317,10 @@ __global__ void __launch_bounds__(256) k_reward_finalize_dev(KParams p, const Ti
 // ---- finish of a common-penalty window (behind k_step_window<..., COMMON>: the kernel boundary
 // makes its plain-store partials visible)
 // One block per tick j: res[j] = {sum, max} of the tick's per-wave partials part[j][0 .. ntile),
-// thread t taking tiles t, t + 256, ... in index order, then k_pen_reduce's LDS tree (stride-1
-// rows of doubles: lanes of a wave read consecutive 8-B words, no bank conflict).  A fixed order:
-// the result is the same bits every run.
+// thread t taking tiles t, t + 256, ... in index order, then k_pen_reduce's LDS tree (pen_tree).  A
+// fixed order: the result is the same bits every run.
 __global__ void __launch_bounds__(256) k_win_pen_reduce(const double* __restrict__ part, int ntile,
                                                         double* __restrict__ res) {
-  __shared__ double ss[256], sm[256];
   const double2* row = reinterpret_cast<const double2*>(part) + (size_t)blockIdx.x * ntile;
   double s = 0.0, m = 0.0;
   for (int b = threadIdx.x; b < ntile; b += blockDim.x) {
@@ -2468,17 +2328,7 @@ __global__ void __launch_bounds__(256) k_win_pen_reduce(const double* __restrict
     s += v.x;
     m = fmax(m, v.y);
   }
-  ss[threadIdx.x] = s;
-  sm[threadIdx.x] = m;
-  __syncthreads();
-  for (int w = blockDim.x / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      ss[threadIdx.x] += ss[threadIdx.x + w];
-      sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + w]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { res[2 * blockIdx.x] = ss[0]; res[2 * blockIdx.x + 1] = sm[0]; }
+  pen_tree(s, m, res + 2 * blockIdx.x);
 }
 
 // Reward row of tick j = j0 + blockIdx.y of the window (blockIdx.x: 256 houses): k_reward_finalize's
@@ -2497,19 +2347,24 @@ __global__ void __launch_bounds__(256) k_win_reward_common(KParams p, const doub
   __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
 }
 
-// Finish of a closed-loop window (behind k_step_closed and k_win_reduce): reward row j = j0 +
-// blockIdx.y holds the raw pen_i and is rewritten in place with the one-tick kernels' individual_L2
-// expression; the signal term is the exact negation of the tick record's rec[2] (win_nsig), so the
-// sum has the bits of k_step_t's.  rew_stride == 0: the caller launches the last tick alone.
-__global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* __restrict__ rec, int j0,
-                                                       double* __restrict__ reward, int64_t rew_stride) {
-  const int j = j0 + (int)blockIdx.y;
-  const double sig_term = -rec[j * kWinRec + 2];
+// the thread's house of reward row j of a closed-loop window: the raw pen_i rewritten in place with
+// the one-tick kernels' individual_L2 expression
+__device__ __forceinline__ void closed_reward_row(const KParams& p, int j, double sig_term,
+                                                  double* __restrict__ reward, int64_t rew_stride) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
   double* r = reward + (int64_t)j * rew_stride + i;
-  const double tpen = p.alpha_temp * *r;
-  __builtin_nontemporal_store(-((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term), r);
+  __builtin_nontemporal_store(reward_individual(p, *r, sig_term), r);
+}
+
+// Finish of a closed-loop window (behind k_step_closed and k_win_reduce): reward row j = j0 +
+// blockIdx.y holds the raw pen_i and is rewritten in place (closed_reward_row); the signal term is
+// the exact negation of the tick record's rec[2] (win_nsig), so the sum has the bits of k_step_t's.
+// rew_stride == 0: the caller launches the last tick alone.
+__global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* __restrict__ rec, int j0,
+                                                       double* __restrict__ reward, int64_t rew_stride) {
+  const int j = j0 + (int)blockIdx.y;
+  closed_reward_row(p, j, -rec[j * kWinRec + 2], reward, rew_stride);
 }
 
 // Finish of a closed-loop window on a sharded context (behind k_step_closed, k_win_shard_sum and the
@@ -2531,11 +2386,7 @@ __global__ void __launch_bounds__(256) k_closed_reward_sharded(KParams p, const 
   const double P = win_power(p, red + j * ncap, p_on);
   const double sig_term = -win_nsig(p, P, tkp[j].s_prev);
   if (p_out && j == nt - 1 && blockIdx.x == 0 && threadIdx.x == 0) *p_out = P;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  double* r = reward + (int64_t)j * rew_stride + i;
-  const double tpen = p.alpha_temp * *r;
-  __builtin_nontemporal_store(-((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term), r);
+  closed_reward_row(p, j, sig_term, reward, rew_stride);
 }
 
 // Finish of a COMMON closed-loop window (behind k_step_closed<..., COMMON>, k_win_reduce and
@@ -2565,8 +2416,7 @@ __global__ void __launch_bounds__(256) k_reward_state(KParams p, const TickArgs*
   if (p_out && blockIdx.x == 0 && threadIdx.x == 0) *p_out = P;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
-  const double tpen = p.alpha_temp * deadband_l2(p.target[i], p.deadband, p.t_air[i]);
-  reward[i] = -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term);
+  reward[i] = reward_individual(p, deadband_l2(p.target[i], p.deadband, p.t_air[i]), sig_term);
 }
 
 // --------------------------------------------------------------------------------------- stats

@@ -5,6 +5,8 @@ import random
 import numpy as np
 import pytest
 
+import golden_util as gu
+
 pytestmark = pytest.mark.gpu
 
 
@@ -122,3 +124,78 @@ def test_fast_division_guard_fallback(tpw):
     s0, s1 = envs[0].shard.host_state(), envs[1].shard.host_state()
     np.testing.assert_array_equal(s0["T"], s1["T"])
     np.testing.assert_array_equal(s0["Tm"], s1["Tm"])
+
+
+# ---- the window kernels off the fast-division range (rc_window_ieee: params_ok false for the whole
+# context, and one house's temperature outside the range on top of it)
+FB_N, FB_TICKS, FB_WIN = 257, 40, 7
+
+
+def _fallback_env(window, group=0, thermal="exact", deadband=0.0, synthetic=True):
+    from mdr_amd import _lib as L
+    from mdr_amd.environment import Environment
+
+    props = gu.props_from_overrides({"cluster_prop.nb_agents": FB_N,
+                                     "power_grid_prop.signal_properties.mode": "sinusoidals",
+                                     "cluster_prop.house_prop.deadband": deadband})
+    e = Environment(props, rng=random.Random(2), **({"population": "synthetic", "seed": 3} if synthetic else {}))
+    e.shard.set_option("window_thermal", {"exact": L.THERMAL_EXACT, "affine": L.THERMAL_AFFINE}[thermal])
+    e.shard.set_option("window_group", group)
+    e.shard.set_rollout_window(window)
+    e.shard.ua[17] = 1e-9
+    e.shard.t_air[130] = 3.0e6
+    e.shard.params_changed()
+    return e
+
+
+def _fallback_result(torch, e, r):
+    """Rewards [ticks, n], T, Tm, the FSM state (on, lock, sso) and the last P."""
+    torch.cuda.synchronize()
+    out = dict(e.shard.host_state())
+    out["reward"] = r.cpu().numpy() if hasattr(r, "cpu") else r
+    out["P"] = np.float64(e._cluster_power())
+    return out
+
+
+def _assert_same_bits(a, b, what):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), (what, k)
+
+
+@pytest.mark.parametrize("deadband", [0.0, 0.5])
+@pytest.mark.parametrize("mode", ["random", "buffer"])
+@pytest.mark.parametrize("thermal", ["exact", "affine"])
+def test_window_rollouts_off_the_fast_range(thermal, mode, deadband):
+    """Ua = 1e-9 (params_ok false: the window kernels form their RcWin with IEEE division) and one
+    house at 3e6 degC, 257 houses x 40 ticks at window 7: groups of four windows == one launch per
+    window == the captured graph, and under the EXACT form all three == the one-tick path (rollout
+    window 0), bit for bit.  Random and buffer actions; dead-band 0 (SIMPLE reward) and 0.5."""
+    import torch
+
+    acts = None
+    if mode == "buffer":
+        g = torch.Generator(device="cuda").manual_seed(5)
+        acts = (torch.rand((FB_TICKS, FB_N), device="cuda", generator=g) < 0.5).to(torch.uint8)
+    forms = [("group 4", FB_WIN, 4, False), ("group 0", FB_WIN, 0, False), ("graph", FB_WIN, 4, True)]
+    if thermal == "exact":
+        forms.insert(0, ("one tick", 0, 0, False))
+    res = []
+    for what, window, group, graph in forms:
+        e = _fallback_env(window, group, thermal, deadband)
+        r = e.rollout(FB_TICKS, actions=acts, action_mode=mode, use_graph=graph)
+        res.append((what, _fallback_result(torch, e, r)))
+    for what, r in res[1:]:
+        _assert_same_bits(r, res[0][1], (what, "against", res[0][0]))
+
+
+@pytest.mark.parametrize("ctrl", ["bangbang", "deadband_bangbang"])
+def test_closed_window_off_the_fast_range(ctrl):
+    """The same inputs through k_step_closed: a bang-bang rollout of 40 ticks at window 7 == the loop
+    of one-tick steps, bit for bit."""
+    import torch
+
+    e1, e2 = (_fallback_env(FB_WIN, deadband=0.05, synthetic=False) for _ in range(2))
+    r1 = e1.rollout(FB_TICKS, action_mode=ctrl)
+    rows = [e2.step_tensor(None, action_mode=ctrl, lookahead=ctrl).cpu().numpy().copy() for _ in range(FB_TICKS)]
+    _assert_same_bits(_fallback_result(torch, e1, r1), _fallback_result(torch, e2, np.stack(rows)), ctrl)
