@@ -622,7 +622,7 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
   {
     // the fast division is provably exact for dt < 2^20 s and |q_on| < 2^40 W (mdr_device.h)
     bool ok = cfg->dt < (1 << 20);
-    for (int i = 0; i < cfg->n_cap; ++i) ok = ok && fabs(tab[i]) < 1099511627776.0;
+    for (int i = 0; i < cfg->n_cap; ++i) ok = ok && fabs(tab[i]) < kFastSolarAbs;
     k.fast_tick_ok = ok ? 1 : 0;
   }
   c->slab_len = kCountShards * cfg->n_cap;
@@ -1345,7 +1345,7 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
     dv.od_k[j] = h.t_od_prev + 273.0;  // (k_win_reduce's rec[0]: the same IEEE addition)
     dv.solar[j] = h.solar;
     dv.s_prev[j] = h.s_prev;
-    if (fabs(h.t_od_prev) < 1048576.0 && fabs(h.solar) < 1099511627776.0) dv.ok |= 1u << j;  // (win_tick_record)
+    if (fast_tick_ok(h.t_od_prev, h.solar)) dv.ok |= 1u << j;  // (win_tick_record's rec[3])
   }
   dv.tick0 = host_ticks[0].tick;
   if (nw == 1) dv.p_out = a.p_out;

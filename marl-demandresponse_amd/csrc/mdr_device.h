@@ -88,6 +88,29 @@ __device__ __forceinline__ bool div_safe(double x) {
   return e >= 1023 - 300 && e <= 1023 + 300;
 }
 
+// ---------------------------------------------------------------------------- fast-division ranges
+// The shared-reciprocal division (Recip above) is used only where every divisor and numerator of
+// the RC update provably stays within [2^-300, 2^300], so that it is the IEEE quotient bit for bit:
+// house parameters in k_refresh's ranges (params_bad), dt < 2^20 s and |q_on| < 2^40 W
+// (KParams::fast_tick_ok, checked once at mdr_create), and per tick the two predicates below — the
+// outdoor, air and mass temperatures within 2^20 and the solar gain within 2^40 (NaN and inf fail
+// both comparisons).  A tile that fails any of them takes the plain `/` operator, whose results the
+// fast path equals wherever it is allowed, so the choice never shows in the output.  Every kernel
+// that chooses between the two forms, and the host code that precomputes a window's tick flags,
+// asks these functions: the window path is only correct if its recorded flag and the one-tick
+// kernels' guard are the same predicate.
+constexpr double kFastTempAbs = 1048576.0;        // 2^20
+constexpr double kFastSolarAbs = 1099511627776.0;  // 2^40
+
+__host__ __device__ __forceinline__ bool fast_temp_ok(double t) { return fabs(t) < kFastTempAbs; }
+// the tick's drivers (wave-uniform)
+__host__ __device__ __forceinline__ bool fast_tick_ok(double t_od_prev, double solar) {
+  return fast_temp_ok(t_od_prev) && fabs(solar) < kFastSolarAbs;
+}
+// one house's state; the window kernels ballot its two halves (fast_temp_ok) separately, which
+// keeps each comparison's lane mask in SGPRs
+__host__ __device__ __forceinline__ bool fast_house_ok(double T, double Tm) { return fast_temp_ok(T) && fast_temp_ok(Tm); }
+
 // ---------------------------------------------------------------------------- RC coefficients
 struct RcCoef { double r1, r2, A3, A4, e1, e2; };
 

@@ -316,9 +316,10 @@ __device__ __forceinline__ void gqf_flush(const unsigned* s_sh, int ncopy, unsig
 }
 
 // --------------------------------------------------------------------------------------- K1
-// Phase 2: fused FSM + RC thermal + reward (environment.py:86-101) for one tick, HPT houses per
-// thread (HPT = 2: 16-B-per-lane loads/stores of the fp64 SoA arrays, two independent fp64
-// dependency chains per thread).
+// Phase 2: fused FSM + RC thermal + reward (environment.py:86-101) for one tick, two houses per
+// thread (16-B-per-lane loads/stores of the fp64 SoA arrays, two independent fp64 dependency chains
+// per thread).  k_step_t is the general form; its per-house statements are the pieces below
+// (Tile2 ... lookahead_flush), which the pipelined form K1' runs as well.
 //   counts    : the tick's GLOBAL per-class ON counts, slab [kCountShards][n_cap]; every wave
 //               reduces it itself (lane l reads shard l), so no block barrier precedes the work
 //   next_slab : when lookahead != 0, ON counts of tick+1 under the in-kernel action source
@@ -362,6 +363,13 @@ __device__ __forceinline__ double reward_individual(const KParams& p, double pen
   return -((p.norm_temp == 1.0 ? tpen : tpen / p.norm_temp) + sig_term);
 }
 
+// the signal term of a tick's reward from the cluster power P and the regulation signal
+// (rewards_calculator.py:183-203), uniform in the cluster; the window records hold its exact negation
+__device__ __forceinline__ double signal_term(const KParams& p, double P, double s_prev) {
+  const double x = (P - s_prev) / (double)p.n_global;
+  return p.alpha_sig * (x * x) / p.norm_sig;
+}
+
 // Loads/stores at an SGPR base + 32-bit VGPR byte offset (computed in 32 bits, so the compiler
 // emits the saddr form instead of a 64-bit address add per array).
 template <typename V>
@@ -379,200 +387,11 @@ __device__ __forceinline__ void sto_nt(void* base, uint32_t off, double2 v) {
   __builtin_nontemporal_store(d2{v.x, v.y}, reinterpret_cast<d2*>(reinterpret_cast<char*>(base) + off));
 }
 
-template <int HPT, bool FAST, int ACT, int LA>
-__global__ void __launch_bounds__(256) k_step_t(KParams p, const uint8_t* __restrict__ action,
-                                                int action_mode_rt, TickArgs tk0, const TickArgs* tkp,
-                                                const unsigned long long* __restrict__ counts,
-                                                double* __restrict__ reward, int ctrl,
-                                                uint8_t* __restrict__ ctrl_out, double* p_out,
-                                                int lookahead_rt, unsigned long long* next_slab,
-                                                unsigned long long* zero_slab,
-                                                double* __restrict__ pen_partial, int reward_lag) {
-  // ACT / LA >= 0: action source / lookahead fixed at compile time (the hot configurations);
-  // -1: taken from the runtime arguments
-  const int action_mode = ACT >= 0 ? ACT : action_mode_rt;
-  const int lookahead = LA >= 0 ? LA : lookahead_rt;
-  __shared__ unsigned hist[MDR_MAX_CAP];
-  __shared__ double s_red[2][4];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  if (tid < p.n_cap) hist[tid] = 0;
-  if (zero_slab && blockIdx.x == 0)
-    for (int j = tid; j < kCountShards * p.n_cap; j += blockDim.x) zero_slab[j] = 0ull;
+// ---- the pieces of a one-tick step (k_step_t, k_step_pipe; house_tick also k_halo_step_pack).
+// Bit-identity between the one-tick kernels, and of every window kernel with them, is the contract:
+// the statements that produce the bits are here once, and the kernels call them in order.
 
-  // one wave tile of 64*HPT consecutive houses per wave (no grid-stride loop: straight-line code
-  // keeps the kernel-argument SGPRs short-lived); 32-bit element indices (n_local < 2^29) so
-  // every access is an SGPR base + 32-bit VGPR offset
-  const uint32_t tile = blockIdx.x * (blockDim.x >> 6) + (tid >> 6);
-  const uint32_t n = (uint32_t)p.n;
-  const uint32_t i0 = tile * (64u * HPT) + (uint32_t)lane * HPT;
-  bool valid[HPT];
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) valid[h] = i0 + h < n;
-
-  // ---- all per-house loads first (one round trip)
-  uint32_t w0[HPT];
-  double T[HPT], Tm[HPT], ua[HPT], ca[HPT], hm[HPT], tg[HPT];
-  double cm[HPT];
-  int cls[HPT];
-  if (HPT == 2 && valid[HPT - 1]) {
-    const uint32_t o8 = i0 * 8u;
-    auto ld2 = [&](const double* a) { return ldo<double2>(a, o8); };
-    const double2 vT = ld2(p.t_air), vTm = ld2(p.t_mass), vua = ld2(p.ua), vca = ld2(p.ca);
-    const double2 vhm = ld2(p.hm), vtg = ld2(p.target);
-    const uint2 vw = ldo<uint2>(p.hvac, i0 * 4u);
-    const unsigned short vc = ldo<unsigned short>(p.cap_idx, i0);
-    T[0] = vT.x; T[HPT - 1] = vT.y; Tm[0] = vTm.x; Tm[HPT - 1] = vTm.y;
-    ua[0] = vua.x; ua[HPT - 1] = vua.y; ca[0] = vca.x; ca[HPT - 1] = vca.y;
-    hm[0] = vhm.x; hm[HPT - 1] = vhm.y;
-    tg[0] = vtg.x; tg[HPT - 1] = vtg.y; w0[0] = vw.x; w0[HPT - 1] = vw.y;
-    cls[0] = vc & 0xFF; cls[HPT - 1] = vc >> 8;
-    const double2 vcm = ld2(p.cm);
-    cm[0] = vcm.x; cm[HPT - 1] = vcm.y;
-  } else {
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) {
-      const uint32_t i = valid[h] ? i0 + h : 0u;
-      T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; ca[h] = p.ca[i];
-      hm[h] = p.hm[i]; tg[h] = p.target[i]; w0[h] = p.hvac[i]; cls[h] = p.cap_idx[i];
-      cm[h] = p.cm[i];
-    }
-  }
-  __syncthreads();  // hist zeroed (the loads above stay in flight across the barrier)
-
-  const TickArgs tk = tkp ? *tkp : tk0;
-  // per-tick signal penalty (rewards_calculator.py:183-203), uniform in the wave.
-  // reward_lag (overlapped multi-GPU pipeline, tkp required): this launch writes the reward of the
-  // PREVIOUS tick — its temperature penalty from the loaded state (= that tick's result) and its
-  // signal term from `counts` = that tick's allreduced slab — so the allreduce of tick t runs
-  // concurrently with the launch of tick t.  counts == nullptr there (first tick): no reward.
-  double sig_term = 0.0;
-  const bool write_rew = counts != nullptr;
-  if (counts) {
-    const double P = wave_power(counts, p.p_on, p.n_cap);
-    const double x = (P - (reward_lag ? tkp[-1].s_prev : tk.s_prev)) / (double)p.n_global;
-    sig_term = p.alpha_sig * (x * x) / p.norm_sig;
-    if (p_out && blockIdx.x == 0 && tid == 0) *p_out = P;
-  }
-
-  // random controller bits of this tick (and the next, for the lookahead) for the whole wave
-  bool rnd[HPT], rnd1[HPT];
-  if (action_mode == MDR_ACT_RANDOM || lookahead == MDR_ACT_RANDOM) {
-    const WaveRandom wr(p.seed, p.goff + (uint64_t)tile * (64u * HPT), tk.tick);
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) {
-      rnd[h] = wr.get(p.goff + i0 + h, false);
-      rnd1[h] = wr.get(p.goff + i0 + h, true);
-    }
-  } else {
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) rnd[h] = rnd1[h] = false;
-  }
-
-  // shared-reciprocal division only where it is provably the IEEE quotient (mdr_device.h)
-  bool house_ok = true;
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) house_ok = house_ok && fabs(T[h]) < 1048576.0 && fabs(Tm[h]) < 1048576.0;
-  const bool tile_fast = FAST && !*p.params_bad && p.fast_tick_ok && fabs(tk.t_od_prev) < 1048576.0 &&
-                         fabs(tk.solar) < 1099511627776.0 && __all(house_ok);
-
-  double Tn[HPT], Tmn[HPT], rw[HPT], pen[HPT];
-  uint32_t w[HPT];
-  bool on[HPT], on1[HPT];
-#pragma unroll
-  for (int h = 0; h < HPT; ++h) {
-    const uint32_t i = i0 + h;
-    const bool a = valid[h] && pick_action(action_mode, action, i, rnd[h], T[h], tg[h], p.deadband, w0[h]);
-    w[h] = hvac_fsm(w0[h], a, p.dt, p.L);
-    on[h] = hv_on(w[h]);
-    const double q = on[h] ? p.q_on[cls[h]] : 0.0;
-    if (tile_fast) {
-      const RcCoef kc = rc_coeffs_t<FAST>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-      rc_apply_t<FAST>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
-    } else {
-      const RcCoef kc = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-      rc_apply_t<false>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
-    }
-    pen[h] = deadband_l2(tg[h], p.deadband, reward_lag ? T[h] : Tn[h]);
-    rw[h] = p.penalty_mode == MDR_PEN_INDIVIDUAL_L2 ? reward_individual(p, pen[h], sig_term)
-                                                    : pen[h];  // finalised by k_reward_finalize
-    on1[h] = false;
-    if (lookahead) {
-      bool an;
-      if (lookahead == MDR_ACT_RANDOM) an = rnd1[h];
-      else if (lookahead == MDR_ACT_ALWAYS_ON) an = true;
-      else if (lookahead == kActBangBang) an = ctrl_bangbang(Tn[h], tg[h]);
-      else an = ctrl_deadband(Tn[h], tg[h], p.deadband, on[h]);
-      on1[h] = valid[h] && hv_on(hvac_fsm(w[h], an, p.dt, p.L));
-    }
-  }
-
-  // ---- stores
-  if (HPT == 2 && valid[HPT - 1]) {
-    const uint32_t o8 = i0 * 8u;
-    sto(p.t_air, o8, make_double2(Tn[0], Tn[HPT - 1]));
-    sto(p.t_mass, o8, make_double2(Tmn[0], Tmn[HPT - 1]));
-    sto(p.hvac, i0 * 4u, make_uint2(w[0], w[HPT - 1]));
-    if (write_rew) sto_nt(reward, o8, make_double2(rw[0], rw[HPT - 1]));
-  } else {
-#pragma unroll
-    for (int h = 0; h < HPT; ++h)
-      if (valid[h]) {
-        p.t_air[i0 + h] = Tn[h]; p.t_mass[i0 + h] = Tmn[h]; p.hvac[i0 + h] = w[h];
-        if (write_rew) __builtin_nontemporal_store(rw[h], reward + i0 + h);
-      }
-  }
-  if (ctrl != MDR_CTRL_NONE && ctrl_out) {
-#pragma unroll
-    for (int h = 0; h < HPT; ++h)
-      if (valid[h]) {
-        const bool a1 = ctrl == MDR_CTRL_BANGBANG ? ctrl_bangbang(Tn[h], tg[h])
-                                                   : ctrl_deadband(Tn[h], tg[h], p.deadband, on[h]);
-        ctrl_out[i0 + h] = a1 ? 1 : 0;
-      }
-  }
-
-  // ---- cluster reductions for the next launch / the common penalty modes
-  if (lookahead) {
-    for (int k = 0; k < p.n_cap; ++k) {
-      unsigned c = 0;
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) c += (unsigned)__popcll(__ballot(on1[h] && cls[h] == k));
-      if (lane == 0 && c) atomicAdd(&hist[k], c);
-    }
-    __syncthreads();
-    if (tid < p.n_cap && hist[tid])
-      atomicAdd(&next_slab[(blockIdx.x % kCountShards) * p.n_cap + tid], (unsigned long long)hist[tid]);
-  }
-  if (p.penalty_mode != MDR_PEN_INDIVIDUAL_L2) {
-    double sacc = 0.0, macc = 0.0;
-#pragma unroll
-    for (int h = 0; h < HPT; ++h)
-      if (valid[h]) { sacc += pen[h] / (double)p.n_global; macc = fmax(macc, pen[h]); }
-    for (int off = 32; off > 0; off >>= 1) {
-      sacc += __shfl_xor(sacc, off);
-      macc = fmax(macc, __shfl_xor(macc, off));
-    }
-    if (lane == 0) { s_red[0][tid >> 6] = sacc; s_red[1][tid >> 6] = macc; }
-    __syncthreads();
-    if (tid == 0) {
-      double bs = 0.0, bm = 0.0;
-      for (int w2 = 0; w2 < (int)(blockDim.x >> 6); ++w2) { bs += s_red[0][w2]; bm = fmax(bm, s_red[1][w2]); }
-      pen_partial[2 * blockIdx.x] = bs;
-      pen_partial[2 * blockIdx.x + 1] = bm;
-    }
-  }
-}
-
-// --------------------------------------------------------------------------------------- K1'
-// Software-pipelined form of the hot step configurations (HPT = 2, shared-reciprocal division,
-// individual_L2, <= kPipeCap capacity classes): a wave steps TPW tiles (strided over the grid),
-// issuing tile k+1's loads before computing tile k, so the memory stream of one tile overlaps the
-// fp64 arithmetic of the previous one.  Straight-line code (TPW and the class loops are unrolled
-// at compile time): a loop in the body would make the compiler drain the in-flight loads at its
-// header.  Results are bit-identical to k_step_t (same per-house expressions).
-constexpr int kPipeCap = 4;
-
+// The wave tile's two houses of a lane: house h of lane l = tile * 128 + 2 l + h.
 struct Tile2 {
   double2 T, Tm, ua, ca, cm, hm, tg;
   uint2 w;
@@ -582,7 +401,10 @@ struct Tile2 {
 
 // full: the whole wave tile is inside the shard (wave-uniform), so every lane takes the 16-B path;
 // otherwise (the last, ragged tile) each house is loaded on its own from a clamped index (a house
-// past the end is computed on a copy of house n-1 and never stored or counted)
+// past the end is computed on a copy of house n-1 and never stored or counted: every consumer of its
+// values is gated by the lane's valid[h])
+__device__ __forceinline__ bool tile2_full(uint32_t tile, uint32_t n) { return (tile + 1u) * 128u <= n; }
+
 template <bool ACT_BUF>
 __device__ __forceinline__ void load_tile2(const KParams& p, const uint8_t* action, uint32_t i0, uint32_t n,
                                            bool full, Tile2& t) {
@@ -605,6 +427,205 @@ __device__ __forceinline__ void load_tile2(const KParams& p, const uint8_t* acti
     t.act = ACT_BUF ? ((unsigned)action[a] | ((unsigned)action[b] << 8)) : 0u;
   }
 }
+
+// the new state of the lane's pair and, when write_rew, its rewards (16-B stores where both houses
+// are inside the shard, chosen per lane)
+__device__ __forceinline__ void store_tile2(const KParams& p, uint32_t i0, const bool (&valid)[2], const double (&Tn)[2],
+                                            const double (&Tmn)[2], const uint32_t (&w)[2], bool write_rew,
+                                            double* __restrict__ reward, const double (&rw)[2]) {
+  if (valid[1]) {
+    const uint32_t o8 = i0 * 8u;
+    sto(p.t_air, o8, make_double2(Tn[0], Tn[1]));
+    sto(p.t_mass, o8, make_double2(Tmn[0], Tmn[1]));
+    sto(p.hvac, i0 * 4u, make_uint2(w[0], w[1]));
+    if (write_rew) sto_nt(reward, o8, make_double2(rw[0], rw[1]));
+  } else if (valid[0]) {
+    p.t_air[i0] = Tn[0]; p.t_mass[i0] = Tmn[0]; p.hvac[i0] = w[0];
+    if (write_rew) __builtin_nontemporal_store(rw[0], reward + i0);
+  }
+}
+
+// every house of the wave's tile inside the fast-division range (mdr_device.h), wave-uniform
+__device__ __forceinline__ bool tile2_fast_ok(const double (&T)[2], const double (&Tm)[2]) {
+  return __all(fast_house_ok(T[0], Tm[0]) && fast_house_ok(T[1], Tm[1]));
+}
+
+// random controller bits of this tick (rnd) and the next (rnd1, for the lookahead) for the wave's tile
+__device__ __forceinline__ void tile_random(const KParams& p, uint32_t tile, uint32_t i0, uint64_t tick, bool (&rnd)[2],
+                                            bool (&rnd1)[2]) {
+  const WaveRandom wr(p.seed, p.goff + (uint64_t)tile * 128u, tick);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    rnd[h] = wr.get(p.goff + i0 + h, false);
+    rnd1[h] = wr.get(p.goff + i0 + h, true);
+  }
+}
+
+// One house, one tick: the lockout FSM under action a, the heat of its class while ON (q_cls: the
+// caller's lookup of q_on), and the RC update — with the shared-reciprocal division where the tile
+// is in its range (fast; mdr_device.h), the plain operator otherwise.
+__device__ __forceinline__ void house_tick(const KParams& p, const TickArgs& tk, bool fast, bool a, double q_cls,
+                                           uint32_t w0, double T, double Tm, double ua, double ca, double cm, double hm,
+                                           uint32_t& w, double& Tn, double& Tmn) {
+  w = hvac_fsm(w0, a, p.dt, p.L);
+  const double q = hv_on(w) ? q_cls : 0.0;
+  if (fast) {
+    const RcCoef kc = rc_coeffs_t<true>(ua, ca, cm, hm, (double)p.dt);
+    rc_apply_t<true>(T, Tm, ua, ca, hm, kc, q, tk.solar, tk.t_od_prev, Tn, Tmn);
+  } else {
+    const RcCoef kc = rc_coeffs_t<false>(ua, ca, cm, hm, (double)p.dt);
+    rc_apply_t<false>(T, Tm, ua, ca, hm, kc, q, tk.solar, tk.t_od_prev, Tn, Tmn);
+  }
+}
+
+// the next tick's action under the in-kernel source `la` (never the action buffer), on the new state
+__device__ __forceinline__ bool lookahead_action(int la, bool rnd1, double Tn, double tg, double deadband, bool on) {
+  if (la == MDR_ACT_RANDOM) return rnd1;
+  if (la == MDR_ACT_ALWAYS_ON) return true;
+  if (la == kActBangBang) return ctrl_bangbang(Tn, tg);
+  return ctrl_deadband(Tn, tg, deadband, on);
+}
+
+// all threads of one block clear a count slab
+__device__ __forceinline__ void slab_zero(unsigned long long* __restrict__ slab, int n_cap) {
+  for (int j = threadIdx.x; j < kCountShards * n_cap; j += blockDim.x) slab[j] = 0ull;
+}
+
+// the block's lookahead class counts (hist, in LDS, complete after the barrier here) into its shard
+// of the next tick's slab
+__device__ __forceinline__ void lookahead_flush(const unsigned* hist, unsigned long long* __restrict__ next_slab,
+                                                int n_cap) {
+  __syncthreads();
+  const int tid = threadIdx.x;
+  if (tid < n_cap && hist[tid])
+    atomicAdd(&next_slab[(blockIdx.x % kCountShards) * n_cap + tid], (unsigned long long)hist[tid]);
+}
+
+template <int HPT, bool FAST, int ACT, int LA>
+__global__ void __launch_bounds__(256) k_step_t(KParams p, const uint8_t* __restrict__ action,
+                                                int action_mode_rt, TickArgs tk0, const TickArgs* tkp,
+                                                const unsigned long long* __restrict__ counts,
+                                                double* __restrict__ reward, int ctrl,
+                                                uint8_t* __restrict__ ctrl_out, double* p_out,
+                                                int lookahead_rt, unsigned long long* next_slab,
+                                                unsigned long long* zero_slab,
+                                                double* __restrict__ pen_partial, int reward_lag) {
+  static_assert(HPT == 2, "the tile is Tile2: two houses per lane (HPT stays in the kernel's name)");
+  // ACT / LA >= 0: action source / lookahead fixed at compile time (the hot configurations);
+  // -1: taken from the runtime arguments
+  const int action_mode = ACT >= 0 ? ACT : action_mode_rt;
+  const int lookahead = LA >= 0 ? LA : lookahead_rt;
+  __shared__ unsigned hist[MDR_MAX_CAP];
+  __shared__ double s_red[2][4];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  if (tid < p.n_cap) hist[tid] = 0;
+  if (zero_slab && blockIdx.x == 0) slab_zero(zero_slab, p.n_cap);
+
+  // one wave tile of 128 consecutive houses per wave (no grid-stride loop: straight-line code
+  // keeps the kernel-argument SGPRs short-lived); 32-bit element indices (n_local < 2^29) so
+  // every access is an SGPR base + 32-bit VGPR offset
+  const uint32_t tile = blockIdx.x * (blockDim.x >> 6) + (tid >> 6);
+  const uint32_t n = (uint32_t)p.n;
+  const uint32_t i0 = tile * 128u + (uint32_t)lane * 2u;
+  const bool valid[2] = {i0 < n, i0 + 1 < n};
+
+  // ---- all per-house loads first (one round trip); the action buffer is read by pick_action
+  Tile2 in;
+  load_tile2<false>(p, action, i0, n, tile2_full(tile, n), in);
+  __syncthreads();  // hist zeroed (the loads above stay in flight across the barrier)
+  const double T[2] = {in.T.x, in.T.y}, Tm[2] = {in.Tm.x, in.Tm.y}, ua[2] = {in.ua.x, in.ua.y};
+  const double ca[2] = {in.ca.x, in.ca.y}, cm[2] = {in.cm.x, in.cm.y}, hm[2] = {in.hm.x, in.hm.y};
+  const double tg[2] = {in.tg.x, in.tg.y};
+  const uint32_t w0[2] = {in.w.x, in.w.y};
+  const int cls[2] = {(int)(in.cls & 0xFF), (int)((in.cls >> 8) & 0xFF)};
+
+  const TickArgs tk = tkp ? *tkp : tk0;
+  // per-tick signal penalty (rewards_calculator.py:183-203), uniform in the wave.
+  // reward_lag (overlapped multi-GPU pipeline, tkp required): this launch writes the reward of the
+  // PREVIOUS tick — its temperature penalty from the loaded state (= that tick's result) and its
+  // signal term from `counts` = that tick's allreduced slab — so the allreduce of tick t runs
+  // concurrently with the launch of tick t.  counts == nullptr there (first tick): no reward.
+  double sig_term = 0.0;
+  const bool write_rew = counts != nullptr;
+  if (counts) {
+    const double P = wave_power(counts, p.p_on, p.n_cap);
+    sig_term = signal_term(p, P, reward_lag ? tkp[-1].s_prev : tk.s_prev);
+    if (p_out && blockIdx.x == 0 && tid == 0) *p_out = P;
+  }
+
+  bool rnd[2] = {false, false}, rnd1[2] = {false, false};
+  if (action_mode == MDR_ACT_RANDOM || lookahead == MDR_ACT_RANDOM) tile_random(p, tile, i0, tk.tick, rnd, rnd1);
+
+  // shared-reciprocal division only where it is provably the IEEE quotient (mdr_device.h)
+  const bool tile_fast = FAST && !*p.params_bad && p.fast_tick_ok && fast_tick_ok(tk.t_od_prev, tk.solar) &&
+                         tile2_fast_ok(T, Tm);
+
+  double Tn[2], Tmn[2], rw[2], pen[2];
+  uint32_t w[2];
+  bool on[2], on1[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const bool a = valid[h] && pick_action(action_mode, action, i0 + h, rnd[h], T[h], tg[h], p.deadband, w0[h]);
+    house_tick(p, tk, tile_fast, a, p.q_on[cls[h]], w0[h], T[h], Tm[h], ua[h], ca[h], cm[h], hm[h], w[h], Tn[h], Tmn[h]);
+    on[h] = hv_on(w[h]);
+    pen[h] = deadband_l2(tg[h], p.deadband, reward_lag ? T[h] : Tn[h]);
+    rw[h] = p.penalty_mode == MDR_PEN_INDIVIDUAL_L2 ? reward_individual(p, pen[h], sig_term)
+                                                    : pen[h];  // finalised by k_reward_finalize
+    on1[h] = lookahead && valid[h] &&
+             hv_on(hvac_fsm(w[h], lookahead_action(lookahead, rnd1[h], Tn[h], tg[h], p.deadband, on[h]), p.dt, p.L));
+  }
+
+  store_tile2(p, i0, valid, Tn, Tmn, w, write_rew, reward, rw);
+  if (ctrl != MDR_CTRL_NONE && ctrl_out) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (valid[h]) {
+        const bool a1 = ctrl == MDR_CTRL_BANGBANG ? ctrl_bangbang(Tn[h], tg[h])
+                                                   : ctrl_deadband(Tn[h], tg[h], p.deadband, on[h]);
+        ctrl_out[i0 + h] = a1 ? 1 : 0;
+      }
+  }
+
+  // ---- cluster reductions for the next launch / the common penalty modes
+  if (lookahead) {
+    for (int k = 0; k < p.n_cap; ++k) {
+      const unsigned c = (unsigned)__popcll(__ballot(on1[0] && cls[0] == k)) +
+                         (unsigned)__popcll(__ballot(on1[1] && cls[1] == k));
+      if (lane == 0 && c) atomicAdd(&hist[k], c);
+    }
+    lookahead_flush(hist, next_slab, p.n_cap);
+  }
+  if (p.penalty_mode != MDR_PEN_INDIVIDUAL_L2) {
+    double sacc = 0.0, macc = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (valid[h]) { sacc += pen[h] / (double)p.n_global; macc = fmax(macc, pen[h]); }
+    for (int off = 32; off > 0; off >>= 1) {
+      sacc += __shfl_xor(sacc, off);
+      macc = fmax(macc, __shfl_xor(macc, off));
+    }
+    if (lane == 0) { s_red[0][tid >> 6] = sacc; s_red[1][tid >> 6] = macc; }
+    __syncthreads();
+    if (tid == 0) {
+      double bs = 0.0, bm = 0.0;
+      for (int w2 = 0; w2 < (int)(blockDim.x >> 6); ++w2) { bs += s_red[0][w2]; bm = fmax(bm, s_red[1][w2]); }
+      pen_partial[2 * blockIdx.x] = bs;
+      pen_partial[2 * blockIdx.x + 1] = bm;
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------- K1'
+// Software-pipelined form of the hot step configurations (shared-reciprocal division,
+// individual_L2, <= kPipeCap capacity classes): a wave steps TPW tiles (strided over the grid),
+// issuing tile k+1's loads before computing tile k, so the memory stream of one tile overlaps the
+// fp64 arithmetic of the previous one.  Straight-line code (TPW and the class loops are unrolled
+// at compile time): a loop in the body would make the compiler drain the in-flight loads at its
+// header.  Results are bit-identical to k_step_t: both run the pieces above (load_tile2, tile_random,
+// house_tick, lookahead_action, store_tile2, lookahead_flush); what differs is when the loads are
+// issued and where a class's q_on comes from.
+constexpr int kPipeCap = 4;
 
 // GQ = 1: the greedy controller's keys of the post-step state, their superbin histogram and the
 // block's key range (k_gq_keys' outputs, gq_flush) as an epilogue, so the next mdr_ctrl_greedy
@@ -675,12 +696,10 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
   GqfAcnt gq_a{0u, 0u, 0u, 0u};
   const double gq_kmin = GQ == 1 ? gq.sel->kmin : GQ == 2 ? fz.sel->fkmin[npar] : 0.0;
   const double gq_scale = GQ == 1 ? gq.sel->scale : GQ == 2 ? fz.sel->fscale[npar] : 0.0;
-  if (zero_slab && blockIdx.x == 0)
-    for (int j = tid; j < kCountShards * p.n_cap; j += blockDim.x) zero_slab[j] = 0ull;
+  if (zero_slab && blockIdx.x == 0) slab_zero(zero_slab, p.n_cap);
   // GQ (no lookahead): the greedy call that follows counts its decisions into next_slab, and its
   // one-pass form (k_gq_binsc) cannot zero it itself
-  if (GQ && !LA && next_slab && blockIdx.x == 0)
-    for (int j = tid; j < kCountShards * p.n_cap; j += blockDim.x) next_slab[j] = 0ull;
+  if (GQ && !LA && next_slab && blockIdx.x == 0) slab_zero(next_slab, p.n_cap);
   const uint32_t n = (uint32_t)p.n;
   const uint32_t ntiles = (n + 64u * HPT - 1u) / (64u * HPT);
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
@@ -696,9 +715,8 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
   double q_on[kPipeCap];
 #pragma unroll
   for (int k = 0; k < kPipeCap; ++k) q_on[k] = p.q_on[k < p.n_cap ? k : 0];
-  auto full_tile = [&](uint32_t t) { return (t + 1u) * (64u * HPT) <= n; };
   Tile2 buf[2];
-  if (gw < ntiles) load_tile2<AB>(p, action, gw * (64u * HPT) + (uint32_t)lane * HPT, n, full_tile(gw), buf[0]);
+  if (gw < ntiles) load_tile2<AB>(p, action, gw * (64u * HPT) + (uint32_t)lane * HPT, n, tile2_full(gw, n), buf[0]);
   if (LA || GQ) __syncthreads();  // hist zeroed (a bare s_barrier: the tile loads stay in flight)
   const TickArgs tk = tkp ? *tkp : tk0;
   double sig_term = 0.0;
@@ -707,12 +725,10 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
 #pragma unroll
     for (int k = 0; k < kPipeCap; ++k)
       if (k < p.n_cap) P += (double)wave_sum_counts(cnt[k]) * p.p_on[k];
-    const double x = (P - tk.s_prev) / (double)p.n_global;
-    sig_term = p.alpha_sig * (x * x) / p.norm_sig;
+    sig_term = signal_term(p, P, tk.s_prev);
     if (p_out && blockIdx.x == 0 && tid == 0) *p_out = P;
   }
-  const bool tick_fast = !*p.params_bad && p.fast_tick_ok && fabs(tk.t_od_prev) < 1048576.0 &&
-                         fabs(tk.solar) < 1099511627776.0;
+  const bool tick_fast = !*p.params_bad && p.fast_tick_ok && fast_tick_ok(tk.t_od_prev, tk.solar);
   unsigned la_cnt[kPipeCap] = {0u, 0u, 0u, 0u};
 
 #pragma unroll
@@ -721,7 +737,7 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
     if (tile >= ntiles) break;  // wave-uniform
     if (k + 1 < TPW && tile + nwaves < ntiles)
       load_tile2<AB>(p, action, (tile + nwaves) * (64u * HPT) + (uint32_t)lane * HPT, n,
-                     full_tile(tile + nwaves), buf[(k + 1) & 1]);
+                     tile2_full(tile + nwaves, n), buf[(k + 1) & 1]);
     const Tile2& in = buf[k & 1];
     const uint32_t i0 = tile * (64u * HPT) + (uint32_t)lane * HPT;
     const double T[2] = {in.T.x, in.T.y}, Tm[2] = {in.Tm.x, in.Tm.y}, ua[2] = {in.ua.x, in.ua.y};
@@ -729,21 +745,11 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
     const double tg[2] = {in.tg.x, in.tg.y};
     const uint32_t w0[2] = {in.w.x, in.w.y};
     const int cls[2] = {(int)(in.cls & 0xFF), (int)((in.cls >> 8) & 0xFF)};
-    bool valid[2] = {i0 < n, i0 + 1 < n};
+    const bool valid[2] = {i0 < n, i0 + 1 < n};
 
     bool rnd[2] = {false, false}, rnd1[2] = {false, false};
-    if (ACT == MDR_ACT_RANDOM || LA == MDR_ACT_RANDOM) {
-      const WaveRandom wr(p.seed, p.goff + (uint64_t)tile * (64u * HPT), tk.tick);
-#pragma unroll
-      for (int h = 0; h < HPT; ++h) {
-        rnd[h] = wr.get(p.goff + i0 + h, false);
-        rnd1[h] = wr.get(p.goff + i0 + h, true);
-      }
-    }
-    bool house_ok = true;
-#pragma unroll
-    for (int h = 0; h < HPT; ++h) house_ok = house_ok && fabs(T[h]) < 1048576.0 && fabs(Tm[h]) < 1048576.0;
-    const bool tile_fast = tick_fast && __all(house_ok);
+    if (ACT == MDR_ACT_RANDOM || LA == MDR_ACT_RANDOM) tile_random(p, tile, i0, tk.tick, rnd, rnd1);
+    const bool tile_fast = tick_fast && tile2_fast_ok(T, Tm);
 
     double Tn[2], Tmn[2], rw[2];
     uint32_t w[2];
@@ -768,30 +774,13 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
         a = valid[h] && (AB ? ((in.act >> (8 * h)) & 0xFFu) != 0u
                             : pick_action(ACT, action, i0 + h, rnd[h], T[h], tg[h], p.deadband, w0[h]));
       }
-      w[h] = hvac_fsm(w0[h], a, p.dt, p.L);
-      const bool on = hv_on(w[h]);
-      double qc = q_on[0];
+      double qc = q_on[0];  // (selects over the scalar table: no lookup behind the in-flight loads)
 #pragma unroll
       for (int c = 1; c < kPipeCap; ++c) qc = cls[h] == c ? q_on[c] : qc;
-      const double q = on ? qc : 0.0;
-      RcCoef kc;
-      if (tile_fast) {
-        kc = rc_coeffs_t<true>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-        rc_apply_t<true>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
-      } else {
-        kc = rc_coeffs_t<false>(ua[h], ca[h], cm[h], hm[h], (double)p.dt);
-        rc_apply_t<false>(T[h], Tm[h], ua[h], ca[h], hm[h], kc, q, tk.solar, tk.t_od_prev, Tn[h], Tmn[h]);
-      }
+      house_tick(p, tk, tile_fast, a, qc, w0[h], T[h], Tm[h], ua[h], ca[h], cm[h], hm[h], w[h], Tn[h], Tmn[h]);
       rw[h] = reward_individual(p, deadband_l2(tg[h], p.deadband, Tn[h]), sig_term);
-      on1[h] = false;
-      if (LA) {
-        bool an;
-        if (LA == MDR_ACT_RANDOM) an = rnd1[h];
-        else if (LA == MDR_ACT_ALWAYS_ON) an = true;
-        else if (LA == kActBangBang) an = ctrl_bangbang(Tn[h], tg[h]);
-        else an = ctrl_deadband(Tn[h], tg[h], p.deadband, on);
-        on1[h] = valid[h] && hv_on(hvac_fsm(w[h], an, p.dt, p.L));
-      }
+      on1[h] = LA && valid[h] &&
+               hv_on(hvac_fsm(w[h], lookahead_action(LA, rnd1[h], Tn[h], tg[h], p.deadband, hv_on(w[h])), p.dt, p.L));
     }
     if (GQ == 2 && gq.act_out) {  // (the fused tick: the applied actions, when the caller keeps them)
       if (valid[1] && ((uintptr_t)gq.act_out & 1u) == 0u) {
@@ -801,16 +790,7 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
         if (valid[1]) gq.act_out[i0 + 1] = act_ap[1] ? 1 : 0;
       }
     }
-    if (valid[1]) {
-      const uint32_t o8 = i0 * 8u;
-      sto(p.t_air, o8, make_double2(Tn[0], Tn[1]));
-      sto(p.t_mass, o8, make_double2(Tmn[0], Tmn[1]));
-      sto(p.hvac, i0 * 4u, make_uint2(w[0], w[1]));
-      if (counts) sto_nt(reward, o8, make_double2(rw[0], rw[1]));
-    } else if (valid[0]) {
-      p.t_air[i0] = Tn[0]; p.t_mass[i0] = Tmn[0]; p.hvac[i0] = w[0];
-      if (counts) __builtin_nontemporal_store(rw[0], reward + i0);
-    }
+    store_tile2(p, i0, valid, Tn, Tmn, w, counts != nullptr, reward, rw);
     if (GQ == 2) {  // the next decision's producer (gq_key_of of the post-step state)
       const uint32_t Lu = p.L < 0 ? 0u : (uint32_t)p.L;
 #pragma unroll
@@ -885,9 +865,7 @@ __global__ void __launch_bounds__(GQ ? 64 * kStepGqWaves : 256) k_step_pipe(KPar
       for (int c = 0; c < kPipeCap; ++c)
         if (c < p.n_cap && la_cnt[c]) atomicAdd(&hist[c], la_cnt[c]);
     }
-    __syncthreads();
-    if (tid < p.n_cap && hist[tid])
-      atomicAdd(&next_slab[(blockIdx.x % kCountShards) * p.n_cap + tid], (unsigned long long)hist[tid]);
+    lookahead_flush(hist, next_slab, p.n_cap);
   }
   if (GQ == 1) {
     __syncthreads();
@@ -1035,8 +1013,7 @@ __device__ __forceinline__ double win_power(const KParams& p, const unsigned lon
 
 // the negated signal penalty of a tick with cluster power P (rewards_calculator.py:183-203)
 __device__ __forceinline__ double win_nsig(const KParams& p, double P, double s_prev) {
-  const double x = (P - s_prev) / (double)p.n_global;
-  return -(p.alpha_sig * (x * x) / p.norm_sig);
+  return -signal_term(p, P, s_prev);
 }
 
 __device__ __forceinline__ void win_tick_record(const KParams& p, const unsigned long long* cnt, const TickArgs& tk,
@@ -1045,7 +1022,7 @@ __device__ __forceinline__ void win_tick_record(const KParams& p, const unsigned
   rec[0] = tk.t_od_prev + 273.0;  // rc_apply's od_k
   rec[1] = tk.solar;
   rec[2] = win_nsig(p, P, tk.s_prev);
-  rec[3] = fabs(tk.t_od_prev) < 1048576.0 && fabs(tk.solar) < 1099511627776.0 ? 1.0 : 0.0;  // fast-division ranges
+  rec[3] = fast_tick_ok(tk.t_od_prev, tk.solar) ? 1.0 : 0.0;
   if (p_out) *p_out = P;
 }
 
@@ -1629,7 +1606,7 @@ struct WinHouses {
         uint64_t ok_m = ~0ull;
 #pragma unroll
         for (int h = 0; h < HPT; ++h)
-          ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
+          ok_m &= __builtin_amdgcn_ballot_w64(fast_temp_ok(T[h])) & __builtin_amdgcn_ballot_w64(fast_temp_ok(Tm[h]));
         const bool fast = params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
         auto houses = [&](auto fast_c) {
           constexpr bool F = decltype(fast_c)::value;
@@ -2000,11 +1977,11 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
     const TickArgs tk = nx;
     nx = tkp[j + 1 < K ? j + 1 : j];
     const double od_k = tk.t_od_prev + 273.0;  // rc_apply_t's od_k
-    const bool tick_ok = fabs(tk.t_od_prev) < 1048576.0 && fabs(tk.solar) < 1099511627776.0;
+    const bool tick_ok = fast_tick_ok(tk.t_od_prev, tk.solar);
     uint64_t ok_m = ~0ull;
 #pragma unroll
     for (int h = 0; h < HPT; ++h)
-      ok_m &= __builtin_amdgcn_ballot_w64(fabs(T[h]) < 1048576.0) & __builtin_amdgcn_ballot_w64(fabs(Tm[h]) < 1048576.0);
+      ok_m &= __builtin_amdgcn_ballot_w64(fast_temp_ok(T[h])) & __builtin_amdgcn_ballot_w64(fast_temp_ok(Tm[h]));
     const bool fast = hs.params_ok && tick_ok && ok_m == __builtin_amdgcn_read_exec();
     // only the last row of a shared reward row (rew_stride == 0) is ever finalised
     const bool store = rew_stride != 0 || j == K - 1;
@@ -2290,8 +2267,7 @@ __device__ __forceinline__ void reward_finalize_body(const KParams& p, double s_
                                                      const double* __restrict__ partial2,
                                                      double* __restrict__ reward) {
   const double P = wave_power(counts, p.p_on, p.n_cap);
-  const double x = (P - s_prev) / (double)p.n_global;
-  const double sig_term = p.alpha_sig * (x * x) / p.norm_sig;
+  const double sig_term = signal_term(p, P, s_prev);
   const double common_l2 = partial2[0], common_max = partial2[1];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
@@ -2331,6 +2307,18 @@ __global__ void __launch_bounds__(256) k_win_pen_reduce(const double* __restrict
   pen_tree(s, m, res + 2 * blockIdx.x);
 }
 
+// the thread's house of reward row j of a common-penalty window from the tick's {sum, max} res[j] and
+// its signal term
+__device__ __forceinline__ void common_reward_row(const KParams& p, int j, const double* __restrict__ res,
+                                                  double sig_term, double* __restrict__ reward, int64_t rew_stride) {
+  const double common_l2 = res[2 * j], common_max = res[2 * j + 1];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  double* r = reward + (int64_t)j * rew_stride + i;
+  const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
+  __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
+}
+
 // Reward row of tick j = j0 + blockIdx.y of the window (blockIdx.x: 256 houses): k_reward_finalize's
 // expression from res[j] and sig[j].  mixture reads the row's raw pen_i and rewrites it in place;
 // the other two modes write a uniform row.  rew_stride == 0: every tick shares one row, which holds
@@ -2339,12 +2327,7 @@ __global__ void __launch_bounds__(256) k_win_reward_common(KParams p, const doub
                                                            const double* __restrict__ sig, int j0,
                                                            double* __restrict__ reward, int64_t rew_stride) {
   const int j = j0 + (int)blockIdx.y;
-  const double common_l2 = res[2 * j], common_max = res[2 * j + 1], sig_term = sig[j];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  double* r = reward + (int64_t)j * rew_stride + i;
-  const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
-  __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
+  common_reward_row(p, j, res, sig[j], reward, rew_stride);
 }
 
 // the thread's house of reward row j of a closed-loop window: the raw pen_i rewritten in place with
@@ -2396,12 +2379,7 @@ __global__ void __launch_bounds__(256) k_closed_reward_common(KParams p, const d
                                                               const double* __restrict__ rec, int j0,
                                                               double* __restrict__ reward, int64_t rew_stride) {
   const int j = j0 + (int)blockIdx.y;
-  const double common_l2 = res[2 * j], common_max = res[2 * j + 1], sig_term = -rec[j * kWinRec + 2];
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= p.n) return;
-  double* r = reward + (int64_t)j * rew_stride + i;
-  const double pen = p.penalty_mode == MDR_PEN_MIXTURE ? *r : 0.0;
-  __builtin_nontemporal_store(common_reward(p, pen, common_l2, common_max, sig_term), r);
+  common_reward_row(p, j, res, -rec[j * kWinRec + 2], reward, rew_stride);
 }
 
 // Reward of the last tick of an overlapped multi-GPU rollout (the k_step launches there write
@@ -2411,8 +2389,7 @@ __global__ void __launch_bounds__(256) k_reward_state(KParams p, const TickArgs*
                                                       const unsigned long long* __restrict__ counts,
                                                       double* __restrict__ reward, double* p_out) {
   const double P = wave_power(counts, p.p_on, p.n_cap);
-  const double x = (P - tkp->s_prev) / (double)p.n_global;
-  const double sig_term = p.alpha_sig * (x * x) / p.norm_sig;
+  const double sig_term = signal_term(p, P, tkp->s_prev);
   if (p_out && blockIdx.x == 0 && threadIdx.x == 0) *p_out = P;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= p.n) return;
@@ -2888,8 +2865,8 @@ __global__ void k_halo_pack(KParams p, ObsArgs o, int lo, int hi, float* out) {
 // The sharded MA-PPO tick's one collective (mdr_actor_rollout_sharded): the ring halo of tick t + 1
 // needs the POST-step message features of this shard's first hi and last lo houses, and those need
 // only the houses' own state, the actions just sampled and the tick's drivers — not the cluster
-// power — so they are computed here, before the step (the same FSM and one-tick RC expressions as
-// the step kernels: bit-identical to the state the step will write), and packed into this rank's
+// power — so they are computed here, before the step (house_tick, the step kernels' own piece, with
+// the plain division: bit-identical to the state the step will write), and packed into this rank's
 // slot of `rows` [world][hi + lo][msg_w] (rows 0..hi: first hi houses, hi..hi+lo: last lo), every
 // other slot zeroed: summed with the count slab in one integer allreduce, the slots become every
 // rank's rows (x + 0 is exact on the bit patterns).  One block.
@@ -2909,11 +2886,8 @@ __global__ void k_halo_step_pack(KParams p, ObsArgs o, const uint8_t* __restrict
     if (j < 0) j = ((j % p.n) + p.n) % p.n;
     HouseRegs r;
     house_load(p, j, true, r);
-    r.w = hvac_fsm(r.w, action[j] != 0, p.dt, p.L);
-    const double q = hv_on(r.w) ? p.q_on[r.cls] : 0.0;
-    const RcCoef kc = rc_coeffs_t<false>(r.ua, r.ca, r.cm, r.hm, (double)p.dt);
     double Tn, Tmn;
-    rc_apply_t<false>(r.T, r.Tm, r.ua, r.ca, r.hm, kc, q, tk.solar, tk.t_od_prev, Tn, Tmn);
+    house_tick(p, tk, false, action[j] != 0, p.q_on[r.cls], r.w, r.T, r.Tm, r.ua, r.ca, r.cm, r.hm, r.w, Tn, Tmn);
     r.T = Tn;
     r.Tm = Tmn;
     msg_from_regs(p, o, r, cf, rows + (size_t)rank * slot + (size_t)t * M, dv);
