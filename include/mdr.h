@@ -364,6 +364,40 @@ int mdr_rollout_stats(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const ui
 #define MDR_STATS_PER_TICK 2
 int mdr_rollout_stats_path(mdr_ctx* ctx, int action_mode);
 
+/* mdr_rollout that writes no reward row and instead adds every house's weighted rewards to
+ * returns[n_local] (device doubles, accumulated on top of their contents): the discounted return the
+ * reference forms from a stored reward sequence (ppo.py:196-206) and TrainingManager.test averages
+ * (training_manager.py:265-295), without a [n_ticks, N] reward matrix.
+ *     returns[i] <- returns[i] + weights[0] r_i(0) + weights[1] r_i(1) + ...   (left to right)
+ * weights: n_ticks host doubles (the caller's w[t + 1] = w[t] * gamma; read before the call returns).
+ * r_i(t) has the bits mdr_rollout would have written to reward row t; state, FSM words, P, and p_out
+ * are mdr_rollout's.  Three sequences (mdr_rollout_returns_path), never captured into a graph:
+ *   - MDR_RETURNS_GROUPED: the open-loop sources under individual_L2, <= 4 capacity classes, window > 0,
+ *     consecutive tick ids — k_count_window, then k_step_group_ret per group of MDR_OPT_WINDOW_GROUP
+ *     windows (0: groups of one), the sum in a register across the group.  One multiply and one add per
+ *     house and tick, never fused: bit for bit a NumPy loop ret = ret + w[t] * rows[t]; under
+ *     MDR_THERMAL_EXACT independent of window, grouping and the per-tick sequence.
+ *   - MDR_RETURNS_CLOSED_WINDOWS: the bang-bang sources where mdr_rollout runs closed-loop windows under
+ *     individual_L2 — per window k_step_closed's ClosedRet form (a_i = sum_j w_j pen_i(j)), k_win_reduce and
+ *     k_closed_return (S = sum_j w_j sig(j); returns[i] += -(alpha_temp a_i [/ norm_temp] + S)).  The
+ *     same sum regrouped: with alpha_temp, alpha_sig >= 0, norm_* > 0 and weights of one sign it is
+ *     within 2 (T + 8) 2^-53 relative of the row form after T accumulated ticks; state and P are exact;
+ *     fixed order, so two runs agree bit for bit.
+ *   - MDR_RETURNS_PER_TICK: everything else (window 0, > 4 classes, the common penalty modes, tick ids
+ *     with gaps): mdr_rollout's one launch per tick into a context-owned row, k_return_acc behind each
+ *     tick's final reward.  The row form's bits.
+ * MDR_EARG: null ticks / weights / returns, n_ticks < 1, an unknown action source, MDR_ACT_BUFFER
+ * without actions (all before any HIP call).  MDR_ESTATE: a context with a communicator or world > 1. */
+#define MDR_RETURNS_GROUPED 0
+#define MDR_RETURNS_CLOSED_WINDOWS 1
+#define MDR_RETURNS_PER_TICK 2
+int mdr_rollout_returns(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
+                        int64_t act_stride, int action_mode, const double* weights, double* returns,
+                        double* p_out, void* stream);
+/* Which sequence mdr_rollout_returns takes for this action source on this context as it stands
+ * (tick ids taken as consecutive); nothing is launched. */
+int mdr_rollout_returns_path(mdr_ctx* ctx, int action_mode);
+
 /* Open-loop sources (MDR_ACT_RANDOM / _ALWAYS_ON / _BUFFER) with <= 4 capacity classes (every
  * penalty mode on an unsharded context; individual_L2 on a sharded one) run TEMPORALLY BLOCKED: windows of up to `ticks` steps per launch (k_step_window), the
  * state and parameters read and written once per window, rewards written every tick, each tick's

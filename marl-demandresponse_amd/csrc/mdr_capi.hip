@@ -164,6 +164,8 @@ struct mdr_ctx {
   Dev<double> d_wres;                    // their per-tick {sum, max} [kWindowMax][2], then signal terms [kWindowMax]
   Dev<double> d_wstat;                   // closed-loop windows with stats rows: block partials [kWindowMax][grid][kStats]
   Dev<double> d_stat_p;                  // mdr_rollout_stats per tick without a caller's p_out: the tick's P
+  Dev<double> d_ret_w;                   // mdr_rollout_returns: the call's staged weights (whole 32-byte records)
+  Dev<double> d_ret_row;                 //   its scratch row [n_local]: the closed-loop windows' a_i, or the tick's rewards
   int pen_blocks = 0;
   // ---- options (mdr_set_option; defaults are the measured-fastest exact configuration)
   int tpw = 0;                           // MDR_OPT_STEP_TPW: k_step_pipe tiles per wave (0: k_step_t)
@@ -1164,9 +1166,11 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
 }
 
 // one k_step_group launch: the (ACT, SIMPLE, KA, FORM) instantiation for this context (individual_L2)
+// wts (mdr_rollout_returns): k_step_group_ret instead, `reward` the returns row, wts the staged weights
+// at the group's first tick
 static int launch_step_group(mdr_ctx* c, int mode, bool ka, const uint8_t* action, int64_t act_stride,
                              const TickArgs* tk, const WinGrp& g, double* reward, int64_t rew_stride,
-                             const WinDrv& dv, hipStream_t st) {
+                             const WinDrv& dv, hipStream_t st, const double* wts = nullptr) {
   if (c->d_onb.capacity() < c->onb_rows) return fail(MDR_ESTATE, "window group launch: no group mask rows");
   if (int rc = mdr_window_group_check(c->kp.n, kWinGroup, dev_bytes(c->d_onb) - c->onb_rows * sizeof(uint64_t),
                                       dev_bytes(c->d_wah)))
@@ -1180,8 +1184,14 @@ static int launch_step_group(mdr_ctx* c, int mode, bool ka, const uint8_t* actio
   const KParams kp = c->kp;
   uint64_t* onb = c->d_onb + c->onb_rows;  // the group rows, behind the first window's
 #define MDR_SG_L(A, SI, KA_, FO)                                                                               \
-  hipLaunchKernelGGL((k_step_group<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, act_stride, tk, g, \
-                     reward, rew_stride, onb, (uint32_t*)c->d_wah, dv)
+  do {                                                                                                         \
+    if (wts)                                                                                                   \
+      hipLaunchKernelGGL((k_step_group_ret<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, \
+                         act_stride, tk, g, reward, wts, onb, (uint32_t*)c->d_wah, dv);                        \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_step_group<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, act_stride, \
+                         tk, g, reward, rew_stride, onb, (uint32_t*)c->d_wah, dv);                             \
+  } while (0)
 #define MDR_SG_F(A, SI, KA_)                                                         \
   do {                                                                               \
     if (c->thermal == MDR_THERMAL_AFFINE) MDR_SG_L(A, SI, KA_, MDR_THERMAL_AFFINE);  \
@@ -1274,7 +1284,9 @@ static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream
 // the first window's count, k_step_group<KA>({w0}; counting w1..wG ahead), the later drivers' staging,
 // then per group one reduce launch and one k_step_group (counting the next group ahead).  Window w
 // counts into slot w % kWinSlots.
-static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tick* host_ticks) {
+// wts (mdr_rollout_returns): the call's staged weights; a.reward is then the returns row (stride 0)
+static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tick* host_ticks,
+                         const double* wts = nullptr) {
   mdr_ctx* c = s.c;
   const RolloutArgs& a = s.a;
   const int nw = s.plan.count(), K0 = s.plan.size(0), ncap = c->kp.n_cap;
@@ -1292,7 +1304,7 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
     g.nw = 1, g.K[0] = K0, g.rec[0] = rec(0), g.first_onb = c->d_onb;
     ahead(g, 1);
     if (int rc = launch_step_group(c, a.mode, true, a.act_row(0), a.act_stride, s.tk(0), g, a.rew_row(0), a.rew_stride,
-                                   dv, s.st))
+                                   dv, s.st, wts))
       return rc;
   }
   if (a.n > K0)
@@ -1313,7 +1325,7 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
     LAUNCH_CHECK("k_win_reduce_group");
     ahead(g, w + cnt);
     if (int rc = launch_step_group(c, a.mode, false, a.act_row(t0), a.act_stride, s.tk(w), g, a.rew_row(t0),
-                                   a.rew_stride, none, s.st))
+                                   a.rew_stride, none, s.st, wts ? wts + t0 : nullptr))
       return rc;
   }
   return MDR_OK;
@@ -1324,6 +1336,20 @@ enum FirstCounts {  // where the first window's per-tick counts of a direct sequ
   kBegun,           // the same launch, already issued by mdr_rollout_begin
   kBegunAllreduced  // ... on a sharded context: P from the allreduced class totals (WinDrv::red)
 };
+
+// the first window's drivers as the KA step kernels take them
+static WinDrv first_window_drivers(const mdr_tick* host_ticks, int K) {
+  WinDrv dv{};
+  for (int j = 0; j < K; ++j) {
+    const mdr_tick& h = host_ticks[j];
+    dv.od_k[j] = h.t_od_prev + 273.0;  // (k_win_reduce's rec[0]: the same IEEE addition)
+    dv.solar[j] = h.solar;
+    dv.s_prev[j] = h.s_prev;
+    if (fast_tick_ok(h.t_od_prev, h.solar)) dv.ok |= 1u << j;  // (win_tick_record's rec[3])
+  }
+  dv.tick0 = host_ticks[0].tick;
+  return dv;
+}
 
 // The direct sequence (ids consecutive, checked by the caller): the first window's count and P-only
 // reduce need only the tick ids; its step kernel then takes the drivers as kernel arguments
@@ -1339,15 +1365,7 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
     if (int rc = launch_count(c, a.mode, a.action, a.act_stride, nullptr, host_ticks[0].tick, K, s.slot(0), c->d_onb,
                               c->d_wah, nullptr, st, true))
       return rc;
-  WinDrv dv{};
-  for (int j = 0; j < K; ++j) {
-    const mdr_tick& h = host_ticks[j];
-    dv.od_k[j] = h.t_od_prev + 273.0;  // (k_win_reduce's rec[0]: the same IEEE addition)
-    dv.solar[j] = h.solar;
-    dv.s_prev[j] = h.s_prev;
-    if (fast_tick_ok(h.t_od_prev, h.solar)) dv.ok |= 1u << j;  // (win_tick_record's rec[3])
-  }
-  dv.tick0 = host_ticks[0].tick;
+  WinDrv dv = first_window_drivers(host_ticks, K);
   if (nw == 1) dv.p_out = a.p_out;
   if (first == kBegunAllreduced) dv.red = win_red_ptr(c, s.slot(0));
   // an unsharded context under individual_L2: the windows in groups (MDR_OPT_WINDOW_GROUP)
@@ -1629,10 +1647,18 @@ static int stats_rows_exchange(mdr_ctx* c, int m, bool closed, double* rows, hip
 // stats (mdr_rollout_stats; never on the open-loop window sequence): row t -> stats + t * kTickRow,
 // by the closed-loop windows themselves, or per tick by mdr_tick_stats' two kernels behind the
 // tick's step (and its finalise kernels in the common penalty modes), every tick's P on the device.
-static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr) {
+// ret (mdr_rollout_returns' one launch per tick, whatever the window sequences could do): a.reward is
+// one context-owned row; behind each tick's final reward k_return_acc adds weights[t] times the row to
+// `returns`.
+struct ReturnsAcc {
+  const double* weights;  // host, a.n
+  double* returns;
+};
+static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, double* stats = nullptr,
+                            const ReturnsAcc* ret = nullptr) {
   const int n = a.n, mode = a.mode;
-  if (window_ok(c, mode)) return window_launches(c, a, false, st);
-  if (closed_ok(c, mode, stats != nullptr)) return closed_launches(c, a, st, stats);
+  if (!ret && window_ok(c, mode)) return window_launches(c, a, false, st);
+  if (!ret && closed_ok(c, mode, stats != nullptr)) return closed_launches(c, a, st, stats);
   double* const p_tick = a.p_out ? a.p_out : c->d_stat_p;  // (stats: every tick's P, for its row)
   if (int rc = zero_slabs(c, st)) return rc;
   c->v.slabs_zeroed();
@@ -1658,6 +1684,11 @@ static int rollout_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st, do
     }
     if (stats)  // the post-step state, this tick's reward row and P: mdr_tick_stats' launches
       if (int rc2 = launch_tick_stats(c, r, p_tick, 0.0, stats + (size_t)t * kTickRow, st)) return rc2;
+    if (ret) {
+      hipLaunchKernelGGL(k_return_acc, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, (int64_t)c->kp.n, ret->weights[t],
+                         (const double*)r, ret->returns);
+      LAUNCH_CHECK("k_return_acc");
+    }
     if (e1) HIP_TRY(hipEventRecord(e1, st));
   }
   return MDR_OK;
@@ -1768,6 +1799,125 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
 int mdr_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride,
                 int mode, double* reward, int64_t rew_stride, double* p_out, int use_graph, void* stream) {
   return mdr_rollout_stats(c, n, ticks, action, act_stride, mode, reward, rew_stride, p_out, nullptr, 0, use_graph, stream);
+}
+
+// ---- rollouts that accumulate per-house discounted returns
+// which sequence a returns call from this action source takes (the ticks' ids consecutive)
+static int returns_path(const mdr_ctx* c, int mode) {
+  if (!win_common(c) && window_ok(c, mode)) return MDR_RETURNS_GROUPED;
+  if (!win_common(c) && closed_ok(c, mode)) return MDR_RETURNS_CLOSED_WINDOWS;
+  return MDR_RETURNS_PER_TICK;
+}
+
+int mdr_rollout_returns_path(mdr_ctx* c, int mode) {
+  if (!c) return fail(MDR_EARG, "mdr_rollout_returns_path: null ctx");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_returns_path: context not bound");
+  if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_returns_path: bad action source");
+  return returns_path(c, mode);
+}
+
+// the weight row (whole staging records) and the scratch row, grown outside any launch sequence;
+// queued work may still read the old buffers, so a growth synchronises first (no graph holds them)
+static int returns_scratch(mdr_ctx* c, int n_ticks, bool row) {
+  const size_t need_w = ((size_t)n_ticks + 3) / 4 * 4, need_r = row ? (size_t)c->kp.n : 0;
+  if (need_w <= c->d_ret_w.capacity() && need_r <= c->d_ret_row.capacity()) return MDR_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = dev_reserve(c->d_ret_w, need_w < 128 ? 128 : need_w, "d_ret_w")) return rc;
+  return need_r ? dev_reserve(c->d_ret_row, need_r, "d_ret_row") : MDR_OK;
+}
+
+// The grouped direct sequence with k_step_group_ret: window_launches_direct's grouped branch, the
+// weights staged by value ahead of everything (they depend on the call's arguments alone), groups of
+// one window under MDR_OPT_WINDOW_GROUP 0.  a.reward: the returns row (a.rew_stride 0).
+static int returns_group_launches(mdr_ctx* c, const RolloutArgs& a, const mdr_tick* host_ticks, const double* weights,
+                                  hipStream_t st) {
+  const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
+  const int K = s.plan.size(0), nw = s.plan.count();
+  std::vector<double> wpad(((size_t)a.n + 3) / 4 * 4, 0.0);
+  std::copy(weights, weights + a.n, wpad.begin());
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
+  if (int rc = stage_recs(wpad.data(), (int)(wpad.size() / 4), c->d_ret_w, st)) return rc;
+  if (int rc = launch_count(c, a.mode, a.action, a.act_stride, nullptr, host_ticks[0].tick, K, s.slot(0), c->d_onb,
+                            c->d_wah, nullptr, st, true))
+    return rc;
+  WinDrv dv = first_window_drivers(host_ticks, K);
+  if (nw == 1) dv.p_out = a.p_out;
+  if (int rc = window_groups(s, c->win_group > 0 ? c->win_group : 1, dv, host_ticks, c->d_ret_w)) return rc;
+  return slots.done();
+}
+
+// The closed-loop windows of a returns call (closed_launches' rules: a bang-bang source under
+// individual_L2, drivers and weights staged): per window k_step_closed<..., ClosedRet> (a_i to the scratch row),
+// k_win_reduce, k_closed_return.  The one count slot serves every window, as there.
+static int returns_closed_launches(mdr_ctx* c, const RolloutArgs& a, hipStream_t st) {
+  const WinPlan plan(a.n, c->win);
+  const int nw = plan.count(), ncap = c->kp.n_cap;
+  const KParams kp = c->kp;
+  const TickArgs* const tk = c->d_ticks;
+  const double* const wts = c->d_ret_w;
+  unsigned long long* slot = c->d_wslab;
+  const double* rec = reinterpret_cast<const double*>(win_red_ptr(c, slot) + (size_t)kWindowMax * ncap);
+  const unsigned grid = win_grid(c);
+  SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
+  for (int w = 0; w < nw; ++w) {
+    const int K = plan.size(w), t0 = plan.start(w);
+    const ClosedRet cr{wts + t0};
+    if (a.mode == MDR_ACT_BANGBANG)
+      hipLaunchKernelGGL((k_step_closed<kActBangBang, kWinHpt, false, false, ClosedRet>), dim3(grid), dim3(256), 0, st, kp,
+                         tk + t0, K, (double*)c->d_ret_row, (int64_t)0, slot, cr);
+    else
+      hipLaunchKernelGGL((k_step_closed<kActDeadband, kWinHpt, false, false, ClosedRet>), dim3(grid), dim3(256), 0, st, kp,
+                         tk + t0, K, (double*)c->d_ret_row, (int64_t)0, slot, cr);
+    LAUNCH_CHECK("k_step_closed<ClosedRet>");
+    hipLaunchKernelGGL(k_win_reduce, dim3(K), dim3(64 * ncap), 0, st, kp, slot, K, tk + t0,
+                       w == nw - 1 ? a.p_out : nullptr);
+    LAUNCH_CHECK("k_win_reduce");
+    hipLaunchKernelGGL(k_closed_return, dim3(blocks(kp.n, 256)), dim3(256), 0, st, kp, rec, wts + t0, K,
+                       (const double*)c->d_ret_row, a.reward);
+    LAUNCH_CHECK("k_closed_return");
+  }
+  return slots.done();
+}
+
+int mdr_rollout_returns(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride, int mode,
+                        const double* weights, double* returns, double* p_out, void* stream) {
+  const char* const who = "mdr_rollout_returns";
+  RolloutArgs a{n, action, act_stride, mode, returns, 0, p_out};
+  // what needs no context first, so each refusal names its argument (all before any HIP call)
+  if (n < 1) return fail(MDR_EARG, std::string(who) + ": n_ticks < 1");
+  if (!weights || !returns) return fail(MDR_EARG, std::string(who) + ": null weights or returns");
+  if (!check_mode(mode)) return fail(MDR_EARG, std::string(who) + ": unknown action source");
+  if (mode == MDR_ACT_BUFFER && !action) return fail(MDR_EARG, std::string(who) + ": a buffer source without actions");
+  if (int rc = rollout_preamble(c, who, ticks != nullptr, a, 0)) return rc;
+  if (has_comm(c) || c->world > 1)
+    return fail(MDR_ESTATE, std::string(who) + ": a sharded context (communicator attached) has no returns rollout");
+  hipStream_t st = S(stream);
+  c->v.drop_early_count();  // (an early count is mdr_rollout's: its shards are cleared below)
+  int path = returns_path(c, a.mode);
+  if (path == MDR_RETURNS_GROUPED && !consecutive(ticks, a.n)) path = MDR_RETURNS_PER_TICK;  // (the KA count takes ids)
+  if (int rc = returns_scratch(c, a.n, path != MDR_RETURNS_GROUPED)) return rc;
+  Sequence seq(c->v, Sequence::kRollout);
+  int rc = refresh_if_dirty(c, st);
+  if (rc) return rc;
+  if (path == MDR_RETURNS_GROUPED) {
+    rc = ensure_ticks(c, a.n);
+    if (!rc) rc = wslab_clean(c, st);
+    if (!rc) rc = returns_group_launches(c, a, ticks, weights, st);
+    return seq.end(rc);
+  }
+  rc = stage_ticks(c, a.n, ticks, st);
+  if (!rc) rc = wslab_clean(c, st);
+  if (rc) return rc;
+  if (path == MDR_RETURNS_CLOSED_WINDOWS) {
+    std::vector<double> wpad(((size_t)a.n + 3) / 4 * 4, 0.0);
+    std::copy(weights, weights + a.n, wpad.begin());
+    rc = stage_recs(wpad.data(), (int)(wpad.size() / 4), c->d_ret_w, st);
+    if (!rc) rc = returns_closed_launches(c, a, st);
+    return seq.end(rc);
+  }
+  const ReturnsAcc ret{weights, returns};
+  a.reward = c->d_ret_row;  // the tick's rewards, one row every tick overwrites
+  return seq.end(rollout_launches(c, a, st, nullptr, &ret));
 }
 
 // The first window's FSM counts (and its cluster power P) of an mdr_rollout of n ticks from tick

@@ -198,6 +198,12 @@ struct WinGrp {
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
 __global__ void k_step_group(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, WinGrp g,
                              double* reward, int64_t rew_stride, uint64_t* onb, uint32_t* wah, WinDrv dv);
+// ... that writes no reward row (mdr_rollout_returns): returns[i] <- returns[i] + wts[j] r_i(j) over the
+// group's ticks j in order, a multiply then an add per tick, the sum kept in registers between the one
+// load and the one store of the launch.  wts: the call's staged weights at the group's first tick.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+__global__ void k_step_group_ret(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, WinGrp g,
+                                 double* returns, const double* wts, uint64_t* onb, uint32_t* wah, WinDrv dv);
 // k_win_reduce for the windows of a group in one launch: block (j, w) is tick j of window w
 struct WinRed {
   int nw;
@@ -229,6 +235,20 @@ __global__ void k_step_closed(KParams p, const TickArgs* tkp, int K, double* rew
                               unsigned long long* slot, W... wstat);
 // reward rows j0 + blockIdx.y of a closed-loop window from their raw pen_i and the tick records
 __global__ void k_closed_reward(KParams p, const double* rec, int j0, double* reward, int64_t rew_stride);
+// The closed-loop window of mdr_rollout_returns is k_step_closed<CTRL, HPT, false, false, ClosedRet> (its RET
+// form: see the kernel): `reward` is a scratch row acc[n] and rew_stride unused; the raw pen_i of tick j is
+// not stored; a_i = sum_j wts[j] pen_i(j) (from 0.0, a multiply then an add, in tick order) goes once to
+// acc[i].  k_win_reduce and k_closed_return follow it.
+struct ClosedRet {
+  const double* wts;  // the staged weights of the window's ticks
+};
+// ... its finish: S = sum_j wts[j] (-rec[j][2]) serially in tick order (scalar work), then
+// returns[i] <- returns[i] + reward_individual(a_i, S)
+__global__ void k_closed_return(KParams p, const double* rec, const double* wts, int K, const double* acc,
+                                double* returns);
+// returns[i] <- returns[i] + w * reward_row[i] (a multiply then an add): behind each tick of the
+// one-launch-per-tick loop of mdr_rollout_returns, after the tick's reward is final
+__global__ void k_return_acc(int64_t n, double w, const double* reward_row, double* returns);
 // ... of a COMMON closed-loop window: k_win_reward_common, the signal term from the tick records
 __global__ void k_closed_reward_common(KParams p, const double* res, const double* rec, int j0, double* reward,
                                        int64_t rew_stride);

@@ -1458,9 +1458,13 @@ struct WinHouses {
   AffWin aw[AFF ? HPT : 1];
   double tk[HPT], tmk[HPT], hk[HPT];  // AFFINE: Kelvin state, Kelvin penalty threshold
   bool win_finite;                    // AFFINE: every coefficient and temperature finite
+  double ret[HPT];                    // RET: the houses' discounted returns (mdr_rollout_returns)
 
   // ---- state + parameters, once per launch (fsm: where the caller keeps the houses' FSM words)
-  __device__ __forceinline__ void load(const KParams& p, const WinTile<HPT>& t, const uint32_t* fsm) {
+  // RET: returns[i] beside it, the tile's own houses only (a lane without a house keeps 0.0)
+  template <bool RET = false>
+  __device__ __forceinline__ void load(const KParams& p, const WinTile<HPT>& t, const uint32_t* fsm,
+                                       const double* returns = nullptr) {
     params_ok = !*p.params_bad && p.fast_tick_ok;
 #pragma unroll
     for (int h = 0; h < HPT; ++h) {
@@ -1469,6 +1473,7 @@ struct WinHouses {
       ca[h] = p.ca[i]; cm[h] = p.cm[i];
       w[h] = fsm[i];
       cls[h] = p.cap_idx[i];
+      if constexpr (RET) ret[h] = t.v[h] ? returns[t.i0 + 64u * h] : 0.0;
     }
   }
 
@@ -1523,11 +1528,18 @@ struct WinHouses {
   // order never depends on scheduling) and lane 0 stores the pair to wp.part[tick][tile]; every wave
   // stores all K pairs (an empty tile: zeros), so the buffer is never cleared.  The reward row gets
   // the raw pen_i (mixture) or nothing.
-  template <bool SIMPLE, bool KA, bool COMMON>
+  // RET (mdr_rollout_returns): no reward row; ret[h] = ret[h] + wts[j] * r stands where the store
+  // stands, a multiply and an add (two roundings: the NumPy line ret = ret + w[t] * rows[t]).  wts: the
+  // staged weights of the window's ticks, a scalar load one tick ahead with the record.
+  template <bool SIMPLE, bool KA, bool COMMON, bool RET = false>
   __device__ __forceinline__ void ticks(const KParams& p, const WinTile<HPT>& t, int K, const double* __restrict__ rec,
                                         const uint64_t* onb_w, double* reward, int j0, int64_t rew_stride, const WinDrv& dv,
-                                        uint32_t ns_lo, uint32_t ns_hi, const WinPen& wp) {
+                                        uint32_t ns_lo, uint32_t ns_hi, const WinPen& wp,
+                                        const double* __restrict__ wts = nullptr) {
     static_assert(!(COMMON && SIMPLE), "the common penalty modes use the general dead-band penalty");
+    static_assert(!(COMMON && RET), "returns under a common penalty mode take one launch per tick");
+    [[maybe_unused]] double r_w = 0.0;
+    if constexpr (RET) r_w = wts[0];
     // the tick's scalars (record, ON masks) are loaded one tick ahead (scalar loads, no vector work)
     auto lane_nsig = [&](int j) { return __longlong_as_double((long long)readlane_u64(ns_lo, ns_hi, j)); };
     double r_od = KA ? dv.od_k[0] : rec[0], r_sol = KA ? dv.solar[0] : rec[1], r_sig = KA ? lane_nsig(0) : rec[2];
@@ -1542,10 +1554,12 @@ struct WinHouses {
       [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
       const double od_k = r_od, solar = r_sol, nsig = r_sig;
       const bool tick_ok = r_ok != 0;
+      [[maybe_unused]] const double wj = r_w;
       uint64_t on_m[HPT];
 #pragma unroll
       for (int h = 0; h < HPT; ++h) on_m[h] = r_on[h];
       const int jn = j + 1 < K ? j + 1 : j;
+      if constexpr (RET) r_w = wts[jn];
       if (KA) {
         r_od = dv.od_k[jn];
         r_sol = dv.solar[jn];
@@ -1559,7 +1573,8 @@ struct WinHouses {
       }
 #pragma unroll
       for (int h = 0; h < HPT; ++h) r_on[h] = onb_w[jn * HPT + h];
-      char* rrow = reinterpret_cast<char*>(reward + (int64_t)(j0 + j) * rew_stride);
+      [[maybe_unused]] char* rrow = nullptr;
+      if constexpr (!RET) rrow = reinterpret_cast<char*>(reward + (int64_t)(j0 + j) * rew_stride);
       // the reward from the new Celsius temperature Tn (Kelvin tkn on the affine path)
       auto reward_of = [&](int h, double Tn, double tkn, auto fast_c) {
         constexpr bool F = decltype(fast_c)::value;
@@ -1596,7 +1611,8 @@ struct WinHouses {
             tmk[h] = tmkn;
             const double r = reward_of(h, tkn - 273.0, tkn, fast_c);  // (Celsius unused on the SIMPLE fast path)
             if constexpr (COMMON) pen_t[h] = r;
-            if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+            if constexpr (RET) ret[h] = ret[h] + wj * r;
+            else if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
           }
         };
         if (win_finite && tick_ok) houses(std::true_type());
@@ -1620,7 +1636,8 @@ struct WinHouses {
             Tm[h] = Tmn;
             const double r = reward_of(h, Tn, 0.0, fast_c);
             if constexpr (COMMON) pen_t[h] = r;
-            if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
+            if constexpr (RET) ret[h] = ret[h] + wj * r;
+            else if ((!COMMON || mix) && t.v[h]) __builtin_nontemporal_store(r, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
           }
         };
         if (fast) houses(std::true_type());
@@ -1658,12 +1675,14 @@ struct WinHouses {
   }
 
   // ---- state back, once per launch
-  __device__ __forceinline__ void store(const KParams& p, const WinTile<HPT>& t) const {
+  template <bool RET = false>
+  __device__ __forceinline__ void store(const KParams& p, const WinTile<HPT>& t, double* returns = nullptr) const {
 #pragma unroll
     for (int h = 0; h < HPT; ++h)
       if (t.v[h]) {
         const uint32_t i = t.i0 + 64u * h;
         p.t_air[i] = T[h]; p.t_mass[i] = Tm[h]; p.hvac[i] = w[h];
+        if constexpr (RET) returns[i] = ret[h];
       }
   }
 };
@@ -1748,12 +1767,14 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
 // The group's last end word is the one in wah on entry: the producer of the group's masks left it
 // after its last window.  Each counted window has its own LDS count rows, so one barrier separates
 // the lookahead's runs from their flushes.  No wave waits for another wave's data.
-template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
-__global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __restrict__ action,
-                                                    int64_t act_stride, const TickArgs* __restrict__ tkp, WinGrp g,
-                                                    double* __restrict__ reward, int64_t rew_stride,
-                                                    uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
-                                                    WinDrv dv) {
+// RET (k_step_group_ret, mdr_rollout_returns): `reward` is the houses' returns row, accumulated in
+// registers over the group's windows (WinHouses::ticks<..., RET>) with the staged weights wts[tick of
+// the group]; no reward row is written and rew_stride is unused.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool RET>
+__device__ __forceinline__ void step_group_body(const KParams& p, const uint8_t* action, int64_t act_stride,
+                                                const TickArgs* tkp, const WinGrp& g, double* reward,
+                                                int64_t rew_stride, uint64_t* onb, uint32_t* wah, const WinDrv& dv,
+                                                const double* wts) {
   __shared__ unsigned s_cnt[kWinGroup][4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6;
   const WinTile<HPT> t(p);
@@ -1775,17 +1796,17 @@ __global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __
 
   // ---- the group's windows (the FSM word at the group's end came with the ON masks)
   WinHouses<HPT, FORM> hs;
-  hs.load(p, t, wah);
+  hs.template load<RET>(p, t, wah, reward);
   hs.form(p);
   int tick_off = 0;  // the window's first tick, from the group's
   for (int gi = 0; gi < g.nw; ++gi) {
     hs.begin_window();
-    hs.template ticks<SIMPLE, KA, false>(p, t, g.K[gi], g.rec[gi], onb_r + gi * (kWinMax * HPT), reward, tick_off,
-                                         rew_stride, dv, ns_lo, ns_hi, WinPen{});
+    hs.template ticks<SIMPLE, KA, false, RET>(p, t, g.K[gi], g.rec[gi], onb_r + gi * (kWinMax * HPT), reward, tick_off,
+                                              rew_stride, dv, ns_lo, ns_hi, WinPen{}, RET ? wts + tick_off : nullptr);
     hs.end_window();
     tick_off += g.K[gi];
   }
-  hs.store(p, t);
+  hs.template store<RET>(p, t, reward);
 
   // ---- lookahead: the next group's ON masks, end word and class counts, window by window
   if (g.la_nw > 0) {
@@ -1804,6 +1825,28 @@ __global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __
     __syncthreads();
     for (int li = 0; li < g.la_nw; ++li) win_flush(p, g.la_K[li], s_cnt[li], g.la_slot[li]);
   }
+}
+
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+__global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __restrict__ action,
+                                                    int64_t act_stride, const TickArgs* __restrict__ tkp, WinGrp g,
+                                                    double* __restrict__ reward, int64_t rew_stride,
+                                                    uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
+                                                    WinDrv dv) {
+  step_group_body<ACT, HPT, SIMPLE, KA, FORM, false>(p, action, act_stride, tkp, g, reward, rew_stride, onb, wah, dv,
+                                                     nullptr);
+}
+
+// k_step_group that adds the weighted rewards of the group's ticks to returns[i] instead of writing
+// reward rows (mdr_rollout_returns).  wts: the call's staged weights at the group's
+// first tick.
+template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
+__global__ void __launch_bounds__(256) k_step_group_ret(KParams p, const uint8_t* __restrict__ action,
+                                                        int64_t act_stride, const TickArgs* __restrict__ tkp,
+                                                        WinGrp g, double* __restrict__ returns,
+                                                        const double* __restrict__ wts, uint64_t* __restrict__ onb,
+                                                        uint32_t* __restrict__ wah, WinDrv dv) {
+  step_group_body<ACT, HPT, SIMPLE, KA, FORM, true>(p, action, act_stride, tkp, g, returns, 0, onb, wah, dv, wts);
 }
 
 // --------------------------------------------------------------------------------------- K1C
@@ -1945,11 +1988,23 @@ __device__ __forceinline__ ClosedPenLds& closed_pen_lds() {
 
 // (W: empty, or the one double* of a STATS (wstat) or COMMON (wpen) launch — the other
 // instantiations keep the parent's kernel arguments, and with them the offsets of the implicit ones)
+// W = <ClosedRet> (the RET form, mdr_rollout_returns; STATS = COMMON = false): `reward` is the scratch
+// row acc[i]; the raw pen_i of tick j is not stored but added, weighted, to a register: a_i = a_i +
+// wts[j] * pen_i(j) from 0.0 (a multiply then an add), stored once behind the tick loop.  The form is
+// an instantiation of this kernel, not a second kernel around a shared body: with the statements moved
+// into a __forceinline__ function five of the six instantiations below changed registers and
+// <deadband, plain> lost a wave (126 -> 135 VGPRs), with p by value or by reference, with or without
+// __restrict__ on the function's pointers; in place they compile to the parent's registers.
 template <int CTRL, int HPT, bool STATS, bool COMMON, class... W>
 __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* __restrict__ tkp, int K,
                                                      double* __restrict__ reward, int64_t rew_stride,
                                                      unsigned long long* __restrict__ slot, W... wstat_arg) {
-  static_assert(sizeof...(W) == (STATS || COMMON ? 1 : 0), "a partial buffer rides only on a STATS or COMMON launch");
+  constexpr bool RET = (std::is_same_v<W, ClosedRet> || ...);
+  static_assert(sizeof...(W) == (STATS || COMMON || RET ? 1 : 0),
+                "a partial buffer rides only on a STATS or COMMON launch, the weights on a RET launch");
+  static_assert(!(RET && (STATS || COMMON)), "the returns form has neither stats rows nor a common penalty mode");
+  [[maybe_unused]] const double* wts = nullptr;
+  if constexpr (RET) wts = std::get<0>(std::tuple<W...>(wstat_arg...)).wts;
   static_assert(!(STATS && COMMON), "stats rows under a common penalty mode stay on the per-tick sequence");
   static_assert(!COMMON || HPT == 2, "the COMMON order restates k_step_t's two houses per lane");
   static_assert(CTRL == kActBangBang || CTRL == kActDeadband, "a bang-bang action source");
@@ -1972,10 +2027,18 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
   const uint32_t rb = t.i0 * 8u;  // byte offset of the lane's house in a reward row (n < 2^29)
   const bool mix = COMMON && p.penalty_mode == MDR_PEN_MIXTURE;  // COMMON: only mixture keeps the raw pen_i
   TickArgs nx = tkp[0];
+  [[maybe_unused]] double racc[HPT], r_w = 0.0;  // RET: a_i; the tick's weight, loaded a tick ahead
+  if constexpr (RET) {
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) racc[h] = 0.0;
+    r_w = wts[0];
+  }
   for (int j = 0; j < K; ++j) {
     [[maybe_unused]] double pen_t[HPT];  // COMMON: the tick's pen_i
     const TickArgs tk = nx;
     nx = tkp[j + 1 < K ? j + 1 : j];
+    [[maybe_unused]] const double wj = r_w;
+    if constexpr (RET) r_w = wts[j + 1 < K ? j + 1 : j];
     const double od_k = tk.t_od_prev + 273.0;  // rc_apply_t's od_k
     const bool tick_ok = fast_tick_ok(tk.t_od_prev, tk.solar);
     uint64_t ok_m = ~0ull;
@@ -2010,7 +2073,8 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
         Tm[h] = Tmn;
         const double pen = deadband_l2(tg[h], p.deadband, Tn);
         if constexpr (COMMON) pen_t[h] = pen;
-        if ((!COMMON || mix) && store && t.v[h])
+        if constexpr (RET) racc[h] = racc[h] + wj * pen;
+        else if ((!COMMON || mix) && store && t.v[h])
           __builtin_nontemporal_store(pen, reinterpret_cast<double*>(rrow + (rb + 512u * h)));
         if constexpr (STATS) {  // the post-step state of tick j
           if (t.v[h]) closed_acc(acc, Tn, Tmn, tg[h], pen, (double)p.n_global);
@@ -2058,6 +2122,11 @@ __global__ void __launch_bounds__(256) k_step_closed(KParams p, const TickArgs* 
   }
 
   hs.store(p, t);
+  if constexpr (RET) {
+#pragma unroll
+    for (int h = 0; h < HPT; ++h)
+      if (t.v[h]) reward[t.i0 + 64u * h] = racc[h];
+  }
 
   // ---- the window's ON counts into its slot (the lookahead's tail of k_step_window)
   if (lane < K) {
@@ -2114,6 +2183,12 @@ template __global__ void k_step_closed<kActBangBang, kWinHpt, false, true, doubl
 template __global__ void k_step_closed<kActDeadband, kWinHpt, false, true, double*>(KParams, const TickArgs*, int,
                                                                                     double*, int64_t,
                                                                                     unsigned long long*, double*);
+template __global__ void k_step_closed<kActBangBang, kWinHpt, false, false, ClosedRet>(KParams, const TickArgs*, int,
+                                                                                       double*, int64_t,
+                                                                                       unsigned long long*, ClosedRet);
+template __global__ void k_step_closed<kActDeadband, kWinHpt, false, false, ClosedRet>(KParams, const TickArgs*, int,
+                                                                                       double*, int64_t,
+                                                                                       unsigned long long*, ClosedRet);
 
 
 #define MDR_INST_WIN_C(A, SI, KA_, FO, CO)                                                                     \
@@ -2139,7 +2214,10 @@ MDR_INST_WIN(MDR_ACT_BUFFER)
 
 #define MDR_INST_GRP_F(A, SI, KA_, FO)                                                                         \
   template __global__ void k_step_group<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
-                                                                 WinGrp, double*, int64_t, uint64_t*, uint32_t*, WinDrv);
+                                                                 WinGrp, double*, int64_t, uint64_t*, uint32_t*, WinDrv); \
+  template __global__ void k_step_group_ret<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
+                                                                     WinGrp, double*, const double*, uint64_t*,  \
+                                                                     uint32_t*, WinDrv);
 #define MDR_INST_GRP(A)                                                                                    \
   MDR_INST_GRP_F(A, true, false, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, false, MDR_THERMAL_EXACT)     \
   MDR_INST_GRP_F(A, true, true, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, true, MDR_THERMAL_EXACT)       \
@@ -2348,6 +2426,28 @@ __global__ void __launch_bounds__(256) k_closed_reward(KParams p, const double* 
                                                        double* __restrict__ reward, int64_t rew_stride) {
   const int j = j0 + (int)blockIdx.y;
   closed_reward_row(p, j, -rec[j * kWinRec + 2], reward, rew_stride);
+}
+
+// Finish of a closed-loop window of mdr_rollout_returns (behind k_step_closed<..., ClosedRet> and k_win_reduce):
+// S = sum_j wts[j] * (-rec[j][2]) from 0.0 in tick order (uniform in the block: scalar loads, a
+// multiply then an add), then returns[i] <- returns[i] + reward_individual(a_i, S) — the window's
+// weighted rewards with the addends regrouped (DESIGN §3.1.6 bounds the difference).
+__global__ void __launch_bounds__(256) k_closed_return(KParams p, const double* __restrict__ rec,
+                                                       const double* __restrict__ wts, int K,
+                                                       const double* __restrict__ acc, double* __restrict__ returns) {
+  double S = 0.0;
+  for (int j = 0; j < K; ++j) S = S + wts[j] * -rec[j * kWinRec + 2];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n) return;
+  returns[i] = returns[i] + reward_individual(p, acc[i], S);
+}
+
+// returns[i] <- returns[i] + w * reward_row[i]: the one-launch-per-tick form of mdr_rollout_returns
+__global__ void __launch_bounds__(256) k_return_acc(int64_t n, double w, const double* __restrict__ reward_row,
+                                                    double* __restrict__ returns) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  returns[i] = returns[i] + w * reward_row[i];
 }
 
 // Finish of a closed-loop window on a sharded context (behind k_step_closed, k_win_shard_sum and the

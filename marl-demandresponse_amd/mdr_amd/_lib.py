@@ -168,6 +168,9 @@ SIGNATURES = {
     "mdr_rollout": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, I, VP]),  # ticks: const mdr_tick*
     "mdr_rollout_stats": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP, I, I, VP]),
     "mdr_rollout_stats_path": (I, [VP, I]),
+    # weights: const double* on the host (n_ticks); returns: device doubles [n_local]
+    "mdr_rollout_returns": (I, [VP, I, VP, VP, I64, I, VP, VP, VP, VP]),
+    "mdr_rollout_returns_path": (I, [VP, I]),
     "mdr_msg_width": (I, [P(mdr_obs_spec)]),
     "mdr_obs": (I, [VP, P(mdr_obs_spec), P(mdr_obs_scalars), VP, VP, VP]),
     "mdr_halo_pack": (I, [VP, P(mdr_obs_spec), VP, VP]),

@@ -43,6 +43,16 @@ ACTION_MODES = {"buffer": L.ACT_BUFFER, "random": L.ACT_RANDOM, "always_on": L.A
                 "bangbang": L.ACT_BANGBANG, "deadband_bangbang": L.ACT_DEADBAND_BANGBANG}
 
 
+def discount_weights(weight0: float, gamma: float, n: int) -> np.ndarray:
+    """w[0] = weight0, w[t + 1] = w[t] * gamma for t < n: n + 1 fp64 values, each product formed
+    from the previous one in that order (``rollout_returns``'s weights; w[n] chains the next call)."""
+    w = np.empty(n + 1, dtype=np.float64)
+    w[0] = weight0
+    for t in range(n):
+        w[t + 1] = w[t] * np.float64(gamma)
+    return w
+
+
 def _runs(key: np.ndarray):
     """(values of the runs of equal consecutive keys as ints, run index of every element)."""
     chg = np.empty(key.shape[0], bool)
@@ -707,6 +717,57 @@ class Environment:
             done += k
         self._counts_ready = 0
         return rewards
+
+    def rollout_returns(self, n_ticks: int, returns, gamma: float = 1.0, weight0: float = 1.0, actions=None,
+                        action_mode: str = "random") -> float:
+        """``rollout`` that writes no reward row: every house's weighted rewards of the call's ticks
+        are added to ``returns`` (float64 [N] on the environment's device, on top of its contents),
+
+            returns[i] += w[0] r_i(0) + w[1] r_i(1) + ...,   w[0] = weight0, w[t + 1] = w[t] * gamma
+
+        (fp64 products formed on the host in that order; the sum runs left to right).  Returns
+        ``w[n_ticks]``, the ``weight0`` of the next call of a chain.  State, FSM words, cluster power,
+        tick and date advance exactly as under ``rollout`` with the same arguments.  The open-loop
+        sources (random / always_on / buffer) under individual_L2 accumulate inside the window kernels
+        (k_step_group_ret): the bits of ``ret = ret + w[t] * rows[t]`` over ``rollout``'s rows.  The
+        bang-bang sources accumulate per closed-loop window (k_step_closed<..., ClosedRet> + k_closed_return): the
+        same sum regrouped, within ``2 (T + 8) 2**-53`` relative of the row form after T ticks.
+        Everything else (window 0, more than 4 capacity classes, the common penalty modes) runs one
+        launch per tick and has the row form's bits.  ``ValueError``: ``returns`` of another dtype,
+        shape or device, ``gamma`` outside (0, 1], a non-finite ``weight0``, ``n_ticks < 1``.
+        ``NotImplementedError``: a sharded environment; the random_sample comm mode."""
+        import math
+
+        import torch
+
+        if int(n_ticks) != n_ticks or n_ticks < 1:
+            raise ValueError(f"n_ticks = {n_ticks!r}: at least one tick")
+        if not (isinstance(gamma, (int, float)) and 0.0 < gamma <= 1.0):
+            raise ValueError(f"gamma = {gamma!r} outside (0, 1]")
+        if not (isinstance(weight0, (int, float)) and math.isfinite(weight0)):
+            raise ValueError(f"weight0 = {weight0!r} is not finite")
+        if self._comm is not None:
+            raise NotImplementedError("rollout_returns: sharded environments have no returns rollout")
+        sh = self._shard
+        if (not isinstance(returns, torch.Tensor) or returns.dtype != torch.float64 or returns.dim() != 1
+                or returns.shape[0] != self._n_local or not returns.is_contiguous()
+                or returns.device != torch.device(sh.device)):
+            raise ValueError(f"returns: a contiguous float64 [{self._n_local}] tensor on {sh.device}")
+        mode = ACTION_MODES[action_mode]
+        if mode == L.ACT_BUFFER and actions is None:
+            raise ValueError("action_mode='buffer' needs actions")
+        weights = discount_weights(float(weight0), float(gamma), n_ticks)
+        done = 0
+        while done < n_ticks:  # one window unless interpolation ends it early (driver_window)
+            ticks = self.driver_window(n_ticks - done)
+            k = len(ticks)
+            a = None if actions is None else actions[done:done + k]
+            sh.rollout_returns(ticks, a, self._n_local if a is not None else 0, mode, weights[done:done + k], returns)
+            self._P_dev_valid = True
+            self.finish_grid_step()
+            done += k
+        self._counts_ready = 0
+        return float(weights[n_ticks])
 
     def greedy_rollout(self, n_ticks: int, actions=None, rewards=None, stats=None):
         """Config C3's loop for n_ticks: ``greedy_actions`` then ``step_tensor(actions,

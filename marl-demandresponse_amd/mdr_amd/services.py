@@ -395,6 +395,34 @@ def evaluate_controller(env, controller: str, n_ticks: int, twin=None) -> dict:
     return evaluation_means(stats.host(), stats.prev()["signal_post"], ev.n, n_ticks)
 
 
+RETURNS_CONTROLLERS = ("random", "always_on", "bangbang", "deadband_bangbang")
+
+
+def controller_returns(env, controller: str, n_ticks: int, gamma: float = 1.0, twin=None):
+    """Every house's discounted return ``sum_t gamma**t r_i(t)`` (ppo.py:196-206) of a baseline run for
+    ``n_ticks`` on a reset copy of ``env``, as ONE ``rollout_returns`` — no reward matrix.  The
+    controllers: the open-loop baselines 'random' and 'always_on' and the two bang-bang controllers.
+    The copy-and-reset protocol is ``evaluate_controller``'s (``twin`` None: ``copy.deepcopy(env)``;
+    the copy is ``reset``; ``env`` is not touched).  Returns ``(returns, means)``: the float64 [N]
+    device tensor and ``{"Mean test return": mean(returns) / n_ticks}``, which at gamma = 1 is
+    TrainingManager.test's mean reward per house and tick (training_manager.py:265-295)."""
+    import copy
+
+    import torch
+
+    if controller not in RETURNS_CONTROLLERS:
+        raise ValueError(f"controller_returns: controller must be one of {RETURNS_CONTROLLERS}, not {controller!r}")
+    if n_ticks < 1:
+        raise ValueError("n_ticks must be at least 1")
+    ev = copy.deepcopy(env) if twin is None else twin
+    if ev is env:
+        raise ValueError("controller_returns() resets its env: pass a copy as twin, not the env itself")
+    ev.reset(return_obs=False)
+    returns = torch.zeros(ev.n_local, dtype=torch.float64, device=ev.shard.device)
+    ev.rollout_returns(n_ticks, returns, gamma=gamma, action_mode=controller)
+    return returns, {"Mean test return": float(returns.mean().item()) / n_ticks}
+
+
 def observe(env) -> dict:
     """The per-tick scalars every house's obs dict carries (environment.py:110-130)."""
     return {"reg_signal": env.power_grid.current_signal, "OD_temp": env.current_od_temp,

@@ -220,6 +220,27 @@ class HipShard:
             L.check(rc, "mdr_rollout_stats")
         return rc
 
+    def rollout_returns(self, ticks, action, act_stride, mode, weights, returns):
+        """mdr_rollout_returns: ``rollout`` that writes no reward row and adds ``weights[t]`` times tick
+        t's rewards to ``returns`` (device float64 [n_local]).  ``weights``: a C double array or a
+        contiguous float64 NumPy array of ``len(ticks)`` host values."""
+        import numpy as np
+
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (len(ticks),):
+            raise ValueError(f"{w.shape[0] if w.ndim == 1 else w.shape} weights for {len(ticks)} ticks")
+        L.check(self.lib.mdr_rollout_returns(self.ctx, len(ticks), ticks.ptr(), L.ptr(action), act_stride, mode,
+                                             w.ctypes.data, L.ptr(returns), L.ptr(self.p_dev), self.stream()),
+                "mdr_rollout_returns")
+
+    def rollout_returns_path(self, mode) -> int:
+        """mdr_rollout_returns_path: 0 (grouped open-loop windows), 1 (closed-loop windows) or 2 (one
+        launch per tick).  Nothing is launched."""
+        rc = self.lib.mdr_rollout_returns_path(self.ctx, mode)
+        if rc < 0:
+            L.check(rc, "mdr_rollout_returns_path")
+        return rc
+
     def rollout_begin(self, n, tick0, action, act_stride, mode):
         """mdr_rollout_begin: the first window's count, launched before the host computes the drivers."""
         L.check(self.lib.mdr_rollout_begin(self.ctx, n, tick0, L.ptr(action), act_stride, mode, self.stream()),
