@@ -136,6 +136,10 @@ const char* mdr_last_error(void);
  * walked (every capture fails with MDR_EHIP on a memset node), their nodes; returns the number
  * written. */
 int mdr_graph_info(mdr_ctx* ctx, int64_t* out, int n);
+/* The carried first-group counts of direct rollouts (MDR_OPT_ROLLOUT_CARRY): out[0..3] = calls whose
+ * last launch counted the next call's first group, calls that started from such a count, counts
+ * discarded unused, 1 if one is outstanding now; returns the number written. */
+int mdr_rollout_carry_info(mdr_ctx* ctx, int64_t* out, int n);
 /* Diagnostic (synchronises, overwrites the count slabs): captures hipMemsetAsync of the count slabs
  * to zero in this context and reports out[13] = {nodes, memset nodes, dst == the slabs, value,
  * elementSize, width, height, pitch, bytes passed, non-zero 64-bit words after replays 1..3 (slabs
@@ -148,7 +152,9 @@ int mdr_bind(mdr_ctx* ctx, const mdr_soa* soa);
 
 /* The caller rewrote ua/ca/cm/hm (or dt changed): the per-house flag that routes a house outside
  * the exact shared-reciprocal division range to the IEEE operator is recomputed before the next
- * step.  mdr_bind and mdr_populate imply it. */
+ * step.  mdr_bind and mdr_populate imply it.  Also the call that announces an in-place write to
+ * hvac or cap_idx between two rollouts: it discards a first-group count the previous direct rollout
+ * made for the next one from the old FSM words (MDR_OPT_ROLLOUT_CARRY). */
 int mdr_params_changed(mdr_ctx* ctx);
 
 /* ---- options (no reference counterpart) ------------------------------------------------ */
@@ -211,12 +217,24 @@ int mdr_params_changed(mdr_ctx* ctx);
  *                           launch (k_step_group: state, parameters and per-window coefficients
  *                           loaded and formed once per group, one reduce launch per group; default
  *                           4), 0 = one k_step_window launch per window.  Bit-identical results
- *                           either way; graphs, sharded and common-penalty rollouts ignore it */
+ *                           either way; graphs, sharded and common-penalty rollouts ignore it
+ *   MDR_OPT_ROLLOUT_CARRY   the grouped direct sequence from a random or always_on source: 1 (default) =
+ *                           a call that continues the previous one (same n, source, window and stream,
+ *                           the next tick id) lets its last step launch run its FSM lookahead on over
+ *                           the first group of the NEXT such call, which then starts from staged
+ *                           drivers with no count kernel and no KA launch (mdr_rollout_begin for it
+ *                           launches nothing); any other entry point, option or state write in between
+ *                           discards that count (mdr_rollout_carry_info).  0 = every call counts its own
+ *                           first window.  Bit-identical results either way.  The count runs on from the
+ *                           FSM words (soa.hvac) as the previous call left them: a caller that rewrites
+ *                           the bound arrays in place between two calls must say so (mdr_params_changed,
+ *                           mdr_bind), as for every other derived state the library keeps; an unannounced
+ *                           write to hvac would be missed by the next call's first group */
 enum { MDR_OPT_STEP_TPW = 1, MDR_OPT_FASTDIV = 2, MDR_OPT_WINDOW_PIPELINE = 3, MDR_OPT_SHARDED_OVERLAP = 4,
        MDR_OPT_GREEDY_SORT = 5, MDR_OPT_FORCE_HALO = 6, MDR_OPT_WINDOW_THERMAL = 7,
        MDR_OPT_HALO_OVERLAP = 9, MDR_OPT_ACTOR_GENERIC = 10, MDR_OPT_HALO_IN_COUNTS = 12,
        MDR_OPT_GQ_BAND = 13, MDR_OPT_ACTOR_FP32_FORM = 14, MDR_OPT_GQ_FUSED = 15, MDR_OPT_GQ_ADAPTIVE = 16,
-       MDR_OPT_ACTOR_GRID = 17, MDR_OPT_WINDOW_GROUP = 18 };
+       MDR_OPT_ACTOR_GRID = 17, MDR_OPT_WINDOW_GROUP = 18, MDR_OPT_ROLLOUT_CARRY = 19 };
 enum { MDR_FP32_F16_SPLIT = 0, MDR_FP32_BF16_SPLIT3 = 1 };
 /* (8 was MDR_OPT_ACTOR_PINGPONG, a k_actor schedule measured slower and retired in r04: rejected) */
 enum { MDR_THERMAL_EXACT = 0, MDR_THERMAL_AFFINE = 1 };

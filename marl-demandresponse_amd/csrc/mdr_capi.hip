@@ -188,6 +188,7 @@ struct mdr_ctx {
                                          // then (from onb_rows on) the group rows [tiles][kWinGroup][kWindowMax][HPT]
   size_t onb_rows = 0;                   // u64 words of the first part (the whole buffer before window groups)
   int win_group = kWinGroup;             // MDR_OPT_WINDOW_GROUP: windows per k_step_group launch (0: k_step_window)
+  bool carry = true;                     // MDR_OPT_ROLLOUT_CARRY: a call's last step launch counts the next call's first group
   Dev<uint32_t> d_wah;                   // FSM word at the end of the next window, per house
   Dev<uint64_t> d_onb2;                  // second set for the count-ahead pipeline (pipe_buffers: a unit)
   Dev<uint32_t> d_wah2;
@@ -492,6 +493,15 @@ int mdr_abi_sizes(int64_t* out, int n) {
 
 const char* mdr_last_error(void) { return g_err.c_str(); }
 
+int mdr_rollout_carry_info(mdr_ctx* c, int64_t* out, int n) {
+  if (!c || !out || n < 0) return fail(MDR_EARG, "mdr_rollout_carry_info: bad argument");
+  const CarryCounters& k = c->v.carry_counters();
+  const int64_t v[4] = {k.speculated, k.consumed, k.dropped, c->v.carry().on ? 1 : 0};
+  int i = 0;
+  for (; i < n && i < 4; ++i) out[i] = v[i];
+  return i;
+}
+
 int mdr_graph_info(mdr_ctx* c, int64_t* out, int n) {
   if (!c || !out || n < 0) return fail(MDR_EARG, "mdr_graph_info: bad argument");
   const int64_t v[6] = {(int64_t)c->graphs.size(), (int64_t)c->actor_graphs.size(), c->graph_launches[0],
@@ -749,6 +759,7 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
         return fail(MDR_EARG, "mdr_set_option: WINDOW_THERMAL must be MDR_THERMAL_EXACT or _AFFINE");
       c->thermal = (int)value;
       break;
+    case MDR_OPT_ROLLOUT_CARRY: c->carry = value != 0; break;
     default: return fail(MDR_EARG, "mdr_set_option: unknown option");
   }
   HIP_TRY(hipDeviceSynchronize());  // cached graphs may be in flight
@@ -1285,31 +1296,47 @@ static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream
 // then per group one reduce launch and one k_step_group (counting the next group ahead).  Window w
 // counts into slot w % kWinSlots.
 // wts (mdr_rollout_returns): the call's staged weights; a.reward is then the returns row (stride 0)
+// The call boundary (mdr_validity.h CarriedCount): with cb.speculate the call's LAST launch runs its
+// lookahead on over the first min(G, nw) windows of the next call — the same plan from the id behind
+// this call's last, into the slots behind this call's (carry_slot) — and with cb.carried this call's
+// first group was counted that way: no count kernel and no KA launch, every driver staged, window 0
+// in a staged group like any later one.  Window w counts into slot carry_slot(cb.slot_base, w).
+struct CallBoundary {
+  bool carried = false, speculate = false;
+  int slot_base = 0;
+};
+static_assert(kCarryGroup == kWinGroup && kCarrySlots == kWinSlots, "mdr_validity.h mirrors the group geometry");
 static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tick* host_ticks,
-                         const double* wts = nullptr) {
+                         const double* wts = nullptr, const CallBoundary& cb = CallBoundary{}) {
   mdr_ctx* c = s.c;
   const RolloutArgs& a = s.a;
   const int nw = s.plan.count(), K0 = s.plan.size(0), ncap = c->kp.n_cap;
-  auto slot = [&](int w) { return c->d_wslab + (size_t)(w % kWinSlots) * c->wslab_len; };
+  auto slot = [&](int w) { return c->d_wslab + (size_t)carry_slot(cb.slot_base, w) * c->wslab_len; };
   auto rec = [&](int w) {
     return reinterpret_cast<const double*>(win_red_ptr(c, slot(w)) + (size_t)kWindowMax * ncap);
   };
-  auto ahead = [&](WinGrp& g, int w1) {  // the lookahead over the group that starts at window w1
-    g.la_nw = std::max(0, std::min(G, nw - w1));
-    for (int i = 0; i < g.la_nw; ++i) g.la_K[i] = s.plan.size(w1 + i), g.la_slot[i] = slot(w1 + i);
+  // the lookahead over the group that starts at window w1; w1 == nw: the next call's first group
+  auto ahead = [&](WinGrp& g, int w1) {
+    const bool next_call = w1 >= nw;
+    g.la_nw = next_call ? (cb.speculate ? std::min(G, nw) : 0) : std::min(G, nw - w1);
+    for (int i = 0; i < g.la_nw; ++i) g.la_K[i] = s.plan.size(next_call ? i : w1 + i), g.la_slot[i] = slot(w1 + i);
+    g.la_tick0 = host_ticks[0].tick + (uint64_t)(next_call ? a.n : s.plan.start(w1));
+    g.la_by_id = next_call;  // (those ticks are not staged)
   };
   static const WinDrv none{};
-  {
+  if (!cb.carried) {
     WinGrp g{};
     g.nw = 1, g.K[0] = K0, g.rec[0] = rec(0), g.first_onb = c->d_onb;
     ahead(g, 1);
     if (int rc = launch_step_group(c, a.mode, true, a.act_row(0), a.act_stride, s.tk(0), g, a.rew_row(0), a.rew_stride,
                                    dv, s.st, wts))
       return rc;
+    if (a.n > K0)
+      if (int rc = stage_recs(host_ticks + K0, a.n - K0, c->d_ticks + K0, s.st)) return rc;
+  } else if (int rc = stage_recs(host_ticks, a.n, c->d_ticks, s.st)) {
+    return rc;
   }
-  if (a.n > K0)
-    if (int rc = stage_recs(host_ticks + K0, a.n - K0, c->d_ticks + K0, s.st)) return rc;
-  for (int w = 1; w < nw; w += G) {
+  for (int w = cb.carried ? 0 : 1; w < nw; w += G) {
     const int cnt = std::min(G, nw - w), t0 = s.plan.start(w);
     WinRed r{};
     WinGrp g{};
@@ -1334,8 +1361,29 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
 enum FirstCounts {  // where the first window's per-tick counts of a direct sequence come from
   kCountNow,        // counted here; the count kernel's last block does the P-only reduce
   kBegun,           // the same launch, already issued by mdr_rollout_begin
-  kBegunAllreduced  // ... on a sharded context: P from the allreduced class totals (WinDrv::red)
+  kBegunAllreduced, // ... on a sharded context: P from the allreduced class totals (WinDrv::red)
+  kCarried          // the whole first group, by the previous call's last step launch (CallBoundary::carried)
 };
+
+// the grouped direct sequence: an unsharded context under individual_L2 (MDR_OPT_WINDOW_GROUP)
+static bool direct_grouped(const mdr_ctx* c) {
+  return c->win_group > 0 && !has_comm(c) && c->world <= 1 && !win_common(c);
+}
+
+// ... whose calls may count the next call's first group (never a buffer source: the next call's action
+// rows are unknown)
+static bool carry_ok(const mdr_ctx* c, int mode) {
+  return c->carry && direct_grouped(c) && window_ok(c, mode) && (mode == MDR_ACT_RANDOM || mode == MDR_ACT_ALWAYS_ON);
+}
+
+// the windows a carried count holds are the first group this call's plan steps (they were planned from
+// the same n, window and group, so a mismatch means the record is not of this plan: count afresh)
+static bool carry_plan_matches(const CarriedCount& k, const WinPlan& plan, int G) {
+  if (k.nw != std::min(G, plan.count())) return false;
+  for (int i = 0; i < k.nw; ++i)
+    if (k.K[i] != plan.size(i)) return false;
+  return true;
+}
 
 // the first window's drivers as the KA step kernels take them
 static WinDrv first_window_drivers(const mdr_tick* host_ticks, int K) {
@@ -1356,11 +1404,17 @@ static WinDrv first_window_drivers(const mdr_tick* host_ticks, int K) {
 // (k_step_window<..., KA>), and the later windows' drivers are staged into d_ticks behind it (their
 // first reader is the first step kernel's lookahead... which reads tick ids only: tick0 + K + j).
 static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_tick* host_ticks, FirstCounts first,
-                                  hipStream_t st) {
+                                  hipStream_t st, const CallBoundary& cb = CallBoundary{}) {
   if (int rc = win_common_unsharded(c, first == kBegunAllreduced)) return rc;
   const WinSeq s{c, a, st, WinPlan(a.n, c->win)};
   const int K = s.plan.size(0), nw = s.plan.count();
+  if ((first == kCarried) != cb.carried || ((cb.carried || cb.speculate) && !direct_grouped(c)))
+    return fail(MDR_ESTATE, "window launches: a carried count outside the grouped direct sequence");
   SlotsGuard slots(c->v);  // dirty until the sequence is fully issued
+  if (first == kCarried) {  // (no count, no KA launch: the group sequence from window 0)
+    if (int rc = window_groups(s, c->win_group, WinDrv{}, host_ticks, nullptr, cb)) return rc;
+    return slots.done();
+  }
   if (first == kCountNow)
     if (int rc = launch_count(c, a.mode, a.action, a.act_stride, nullptr, host_ticks[0].tick, K, s.slot(0), c->d_onb,
                               c->d_wah, nullptr, st, true))
@@ -1369,8 +1423,8 @@ static int window_launches_direct(mdr_ctx* c, const RolloutArgs& a, const mdr_ti
   if (nw == 1) dv.p_out = a.p_out;
   if (first == kBegunAllreduced) dv.red = win_red_ptr(c, s.slot(0));
   // an unsharded context under individual_L2: the windows in groups (MDR_OPT_WINDOW_GROUP)
-  if (c->win_group > 0 && first != kBegunAllreduced && !has_comm(c) && c->world <= 1 && !win_common(c)) {
-    if (int rc = window_groups(s, c->win_group, dv, host_ticks)) return rc;
+  if (first != kBegunAllreduced && direct_grouped(c)) {
+    if (int rc = window_groups(s, c->win_group, dv, host_ticks, nullptr, cb)) return rc;
     return slots.done();
   }
   if (int rc = s.step(0, nw > 1 ? s.plan.size(1) : 0, c->d_onb, c->d_wah, s.slot(1), &dv)) return rc;
@@ -1735,12 +1789,13 @@ static bool common_sharded(const mdr_ctx* c) { return win_common(c) && (has_comm
 enum {
   kDropBegun = 1,    // discard an early count once the arguments are there (the others settle it themselves)
   kShardedOnly = 2,  // mdr_rollout_sharded: a communicator
-  kNoCommon = 4      // no common penalty mode (mdr_rollout / mdr_rollout_begin decide behind the preamble)
+  kNoCommon = 4,     // no common penalty mode (mdr_rollout / mdr_rollout_begin decide behind the preamble)
+  kSettlesCarry = 8  // mdr_rollout / mdr_rollout_begin: the caller consumes or drops a carried count itself
 };
 static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const RolloutArgs& a, int flags) {
   if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
   if (flags & kDropBegun) c->v.drop_early_count();
-  c->v.state_may_change();
+  c->v.state_may_change((flags & kSettlesCarry) != 0);
   if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
   if ((flags & kShardedOnly) && !has_comm(c))
     return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
@@ -1766,25 +1821,52 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
                       int use_graph, void* stream) {
   const RolloutArgs a{n, action, act_stride, mode, reward, rew_stride, p_out};
   const char* const who = stats ? "mdr_rollout_stats" : "mdr_rollout";
-  if (int rc = rollout_preamble(c, who, ticks && a.reward, a, 0)) return rc;
+  if (int rc = rollout_preamble(c, who, ticks && a.reward, a, kSettlesCarry)) return rc;
+  hipStream_t st = S(stream);
+  // the direct sequence, and the first group counted by the previous call for exactly this one?
+  const bool direct_seq = !stats && !use_graph && window_ok(c, a.mode) && consecutive(ticks, a.n);
+  const bool may_carry = direct_seq && carry_ok(c, a.mode);
+  const bool carried = may_carry && c->v.carry_matches(a.n, a.mode, ticks[0].tick, c->win, c->win_group, st) &&
+                       carry_plan_matches(c->v.carry(), WinPlan(a.n, c->win), c->win_group);
+  CallBoundary cb{};
+  if (carried) {
+    cb.carried = true;
+    cb.slot_base = c->v.carry().slot_base;
+    c->v.carry_consumed();
+  } else {
+    c->v.drop_carry();  // an unmatched one: its shards are cleared below
+  }
+  // speculate only behind a call this one continues: one-off and irregular callers never pay for it
+  cb.speculate = may_carry && c->v.continues_direct(a.n, a.mode, ticks[0].tick, c->win, c->win_group, st);
+  c->v.direct_call_forgotten();
   if (stats) {
     if (row0 < 0) return fail(MDR_EARG, std::string(who) + ": row0 < 0");
     if (int rc = rollout_stats_path(c, a.mode, who); rc < 0) return rc;
   }
   if (common_sharded(c))
     return fail(MDR_EARG, std::string(who) + ": common penalty modes on a sharded context need the per-step API");
-  hipStream_t st = S(stream);
   double* const srow = stats ? stats + (size_t)row0 * kTickRow : nullptr;
-  const bool counted = begun_matches(c, a, ticks, false);
+  const bool counted = !carried && begun_matches(c, a, ticks, false);
   if (counted) c->v.early_consumed();
   else c->v.drop_early_count();  // an unmatched early count: its shards are cleared below
   Sequence seq(c->v, Sequence::kRollout);
   int rc = refresh_if_dirty(c, st);
   if (rc) return rc;
-  if (counted || (!use_graph && window_ok(c, a.mode) && consecutive(ticks, a.n))) {
+  if (counted || direct_seq) {
     rc = ensure_ticks(c, a.n);
     if (!rc) rc = wslab_clean(c, st);
-    if (!rc) rc = window_launches_direct(c, a, ticks, counted ? kBegun : kCountNow, st);
+    if (!rc) rc = window_launches_direct(c, a, ticks, carried ? kCarried : counted ? kBegun : kCountNow, st, cb);
+    if (!rc && may_carry) {  // the shape the next call must continue, and what this one counted for it
+      const WinPlan plan(a.n, c->win);
+      const uint64_t next = ticks[0].tick + (uint64_t)a.n;
+      c->v.direct_call_issued(DirectCall{true, a.n, a.mode, c->win, c->win_group, next, st});
+      if (cb.speculate) {
+        CarriedCount k{true, a.n, a.mode, next, c->win, c->win_group, std::min(c->win_group, plan.count()), {},
+                       carry_slot(cb.slot_base, plan.count()), st};
+        for (int i = 0; i < k.nw; ++i) k.K[i] = plan.size(i);
+        c->v.carry_counted(k);
+      }
+    }
     return seq.end(rc);
   }
   rc = stage_ticks(c, a.n, ticks, st);
@@ -1928,8 +2010,13 @@ int mdr_rollout_returns(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t*
 int mdr_rollout_begin(mdr_ctx* c, int n, uint64_t tick0, const uint8_t* action, int64_t act_stride, int mode,
                       void* stream) {
   const RolloutArgs a{n, action, act_stride, mode, nullptr, 0, nullptr};
-  if (int rc = rollout_preamble(c, "mdr_rollout_begin", true, a, 0)) return rc;
+  if (int rc = rollout_preamble(c, "mdr_rollout_begin", true, a, kSettlesCarry)) return rc;
   c->v.drop_early_count();  // a previous one that no rollout consumed
+  // the previous call counted this call's first group already: nothing to launch (mdr_rollout checks the
+  // rest — the tick ids, no graph — and drops the carry if it is not the call announced here)
+  // (action / act_stride are not compared: carry_ok admits random and always_on only, which read no action rows)
+  if (carry_ok(c, mode) && c->v.carry_matches(n, mode, tick0, c->win, c->win_group, S(stream))) return MDR_OK;
+  c->v.drop_carry();  // its shards are cleared below, or before the next rollout
   if (!window_ok(c, mode)) return MDR_OK;
   // a sharded context (RCCL attached): single-window rollouts only, counts allreduced here, so
   // the matching mdr_rollout_sharded launches just the KA step kernel

@@ -190,6 +190,9 @@ struct WinGrp {
   const double* rec[kWinGroup];            // the stepped windows' tick records (KA: rec[0], P only)
   unsigned long long* la_slot[kWinGroup];  // the counted windows' slots
   const uint64_t* first_onb;               // KA: the first window's mask rows as k_count_window left them
+  uint64_t la_tick0;                       // id of the first counted tick (ids are consecutive) ...
+  int la_by_id;                            // ... which the lookahead takes where tkp does not cover the counted
+                                           // ticks: the NEXT call's first group (not staged yet; KA takes ids anyway)
 };
 // onb: the group rows [tile][kWinGroup][kWindowMax][HPT] — read (the stepped windows'; KA reads
 // first_onb instead), then replaced by the counted windows'; wah: the end word after the last

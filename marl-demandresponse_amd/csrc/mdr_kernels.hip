@@ -1812,12 +1812,15 @@ __device__ __forceinline__ void step_group_body(const KParams& p, const uint8_t*
   if (g.la_nw > 0) {
     uint64_t cmk[HPT][kWinCap];
     win_classes<HPT>(t, hs.cls, cmk);
+    const bool by_id = KA || g.la_by_id != 0;  // (wave-uniform: a kernel argument)
+    uint64_t la_tick = g.la_tick0;
     for (int li = 0; li < g.la_nw; ++li) {
       const int la_K = g.la_K[li];
-      win_run<ACT, HPT>(p, hs.w, cmk, t, KA ? nullptr : tkp + tick_off, KA ? dv.tick0 + (uint64_t)tick_off : 0, la_K,
+      win_run<ACT, HPT>(p, hs.w, cmk, t, by_id ? nullptr : tkp + tick_off, la_tick, la_K,
                         ACT == MDR_ACT_BUFFER ? action + (int64_t)tick_off * act_stride : nullptr, act_stride,
                         s_cnt[li][wv], onb_w + li * (kWinMax * HPT));
       tick_off += la_K;
+      la_tick += (uint64_t)la_K;
     }
 #pragma unroll
     for (int h = 0; h < HPT; ++h)

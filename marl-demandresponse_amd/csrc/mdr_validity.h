@@ -18,6 +18,38 @@ struct EarlyCount {
   bool sharded = false;  // counts allreduced over the ranks (for mdr_rollout_sharded)
 };
 
+// The first group of windows of the NEXT direct rollout, counted by the last step launch of the
+// previous one (its speculative lookahead): mask rows, end words and slot shards are on
+// the device for exactly the call {n, mode, tick0} under {window, group}, issued on `stream`.
+constexpr int kCarryGroup = 4;  // = kWinGroup
+constexpr int kCarrySlots = 8;  // = kWinSlots
+struct CarriedCount {
+  bool on = false;
+  int n = 0, mode = 0;
+  uint64_t tick0 = 0;      // the counted call's first tick id
+  int window = 0, group = 0;
+  int nw = 0;              // windows counted: the call's first min(group, windows)
+  int K[kCarryGroup] = {};  // their ticks
+  int slot_base = 0;       // window w of the counted call is in slot carry_slot(slot_base, w)
+  const void* stream = nullptr;
+};
+// window w of a call whose first window is in slot `base`; the call after one of nw windows starts at
+// carry_slot(base, nw): consecutive windows take consecutive slots across the call boundary, so a
+// launch's stepped group (<= kCarryGroup) and counted group (<= kCarryGroup) never share a slot
+constexpr int carry_slot(int base, int w) { return (base + w) % kCarrySlots; }
+
+// the last direct grouped rollout that could have speculated (the shape the next one must continue)
+struct DirectCall {
+  bool on = false;
+  int n = 0, mode = 0, window = 0, group = 0;
+  uint64_t next_tick = 0;  // its last tick id + 1
+  const void* stream = nullptr;
+};
+
+struct CarryCounters {
+  int64_t speculated = 0, consumed = 0, dropped = 0;
+};
+
 class Validity {
  public:
   // ---- queries
@@ -30,6 +62,18 @@ class Validity {
   bool coef_dirty() const { return coef_dirty_; }       // k_refresh must run before the next launch sequence
   bool slots_dirty() const { return slots_dirty_; }     // the window slots' shard part is not known to be zero
   const EarlyCount& early() const { return early_; }
+  const CarriedCount& carry() const { return carry_; }
+  const CarryCounters& carry_counters() const { return carry_n_; }
+  // the carried count is of exactly this call (the options it was planned under still hold)
+  bool carry_matches(int n, int mode, uint64_t tick0, int window, int group, const void* stream) const {
+    return carry_.on && carry_.n == n && carry_.mode == mode && carry_.tick0 == tick0 && carry_.window == window &&
+           carry_.group == group && carry_.stream == stream;
+  }
+  // this call continues the previous direct call: same shape, the next tick id (so it may speculate)
+  bool continues_direct(int n, int mode, uint64_t tick0, int window, int group, const void* stream) const {
+    return last_.on && last_.n == n && last_.mode == mode && last_.next_tick == tick0 && last_.window == window &&
+           last_.group == group && last_.stream == stream;
+  }
   bool keys_ready() const { return keys_ready_; }       // (the checks; the library takes them: take_keys)
   bool hist_dirty() const { return hist_dirty_; }
   bool fused_ready() const { return fz_ready_; }
@@ -47,15 +91,23 @@ class Validity {
   }
   // mdr_params_changed (the counts stay: they are of the actions, and the caller vouches for those)
   void params_replaced() {
+    drop_carry();  // (the FSM words or the class indices may be new)
+    last_.on = false;
     coef_dirty_ = true;
     map_stale_ = true;
     s1_ = s2_ = NAN;
   }
   void coef_refreshed() { coef_dirty_ = false; }
-  // an entry point that may write the house state or the count slabs is entered
-  void state_may_change() {
+  // an entry point that may write the house state, the count slabs, the mask rows or the window slots
+  // is entered.  keep_carry: mdr_rollout / mdr_rollout_begin, which settle the carried count
+  // themselves (consume it, or drop it) once their arguments are checked
+  void state_may_change(bool keep_carry = false) {
     keys_ready_ = false;
     fz_ready_ = false;
+    if (!keep_carry) {
+      drop_carry();
+      last_.on = false;
+    }
   }
 
   // ---- the count slabs
@@ -146,6 +198,30 @@ class Validity {
     early_.on = true;
   }
 
+  // ---- the carried count (the next direct rollout's first group)
+  void drop_carry() {  // nobody will consume it: its shards are still in the slots
+    if (carry_.on) {
+      carry_.on = false;
+      slots_dirty_ = true;
+      carry_n_.dropped += 1;
+    }
+  }
+  void carry_consumed() {  // by the rollout it was counted for
+    if (carry_.on) carry_n_.consumed += 1;
+    carry_.on = false;
+  }
+  void carry_counted(const CarriedCount& k) {  // behind the fully issued sequence whose last launch counted it
+    carry_ = k;
+    carry_.on = true;
+    carry_n_.speculated += 1;
+  }
+  // a direct grouped rollout that may carry was fully issued / another rollout ran instead
+  void direct_call_issued(const DirectCall& d) {
+    last_ = d;
+    last_.on = true;
+  }
+  void direct_call_forgotten() { last_.on = false; }
+
   // ---- a sequence failed part-way: nothing derived is vouched for (coef_dirty and map_stale are
   // only ever cleared behind their own launches, so they stay as they are)
   void sequence_failed() {
@@ -154,6 +230,9 @@ class Validity {
     fz_ready_ = false;
     slots_dirty_ = true;
     early_.on = false;
+    if (carry_.on) carry_n_.dropped += 1;
+    carry_.on = false;
+    last_.on = false;
   }
 
  private:
@@ -170,6 +249,9 @@ class Validity {
   bool coef_dirty_ = true;
   bool slots_dirty_ = true;
   EarlyCount early_{};
+  CarriedCount carry_{};
+  DirectCall last_{};
+  CarryCounters carry_n_{};
   double s1_ = NAN, s2_ = NAN;  // the last two budgets mdr_greedy_rollout decided for
 };
 

@@ -24,7 +24,8 @@ ERRORS = {-1: "MDR_EARG", -2: "MDR_EHIP", -3: "MDR_ERCCL", -4: "MDR_ENOMEM", -5:
 # mdr_set_option (mdr.h): alternative launch forms of the same computation
 OPTIONS = {"step_tpw": 1, "fastdiv": 2, "window_pipeline": 3, "sharded_overlap": 4, "greedy_sort": 5, "halo_overlap": 9, "actor_generic": 10,
            "force_halo": 6, "window_thermal": 7, "halo_in_counts": 12,
-           "gq_band": 13, "actor_fp32_form": 14, "gq_fused": 15, "gq_adaptive": 16, "actor_grid": 17, "window_group": 18}
+           "gq_band": 13, "actor_fp32_form": 14, "gq_fused": 15, "gq_adaptive": 16, "actor_grid": 17, "window_group": 18,
+           "rollout_carry": 19}
 THERMAL_EXACT, THERMAL_AFFINE = 0, 1
 FP32_F16_SPLIT, FP32_BF16_SPLIT3 = 0, 1  # MDR_OPT_ACTOR_FP32_FORM
 HEADS = {"softmax": 0, "q": 1}  # MDR_HEAD_* (mdr_actor_set_head)
@@ -138,6 +139,7 @@ SIGNATURES = {
     "mdr_abi_sizes": (I, [P(I64), I]),
     "mdr_last_error": (C.c_char_p, []),
     "mdr_graph_info": (I, [VP, P(I64), I]),
+    "mdr_rollout_carry_info": (I, [VP, P(I64), I]),
     "mdr_graph_memset_probe": (I, [VP, P(I64), I, VP]),
     "mdr_actor_status": (I, [VP, P(I64), I, VP]),
     "mdr_actor_set_head": (I, [VP, I, C.c_float, VP]),

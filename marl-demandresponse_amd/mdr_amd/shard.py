@@ -158,6 +158,15 @@ class HipShard:
         return dict(zip(("rollout_graphs", "actor_graphs", "rollout_launches", "actor_launches", "guarded",
                          "guarded_nodes"), list(out)))
 
+    def carry_info(self):
+        """{speculated, consumed, dropped, outstanding}: direct rollouts whose last launch counted the
+        next call's first group, calls that started from such a count, counts discarded unused, and
+        whether one is outstanding (mdr_rollout_carry_info; mdr.h MDR_OPT_ROLLOUT_CARRY)."""
+        out = (C.c_int64 * 4)()
+        rc = self.lib.mdr_rollout_carry_info(self.ctx, out, 4)
+        L.check(0 if rc == 4 else rc, "mdr_rollout_carry_info")
+        return dict(zip(("speculated", "consumed", "dropped", "outstanding"), list(out)))
+
     def graph_memset_probe(self):
         """mdr_graph_memset_probe: a memset node captured in this context, its parameters and what
         its replays leave in the count slabs (diagnostic; synchronises and overwrites the slabs)."""
