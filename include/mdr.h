@@ -229,12 +229,27 @@ int mdr_params_changed(mdr_ctx* ctx);
  *                           FSM words (soa.hvac) as the previous call left them: a caller that rewrites
  *                           the bound arrays in place between two calls must say so (mdr_params_changed,
  *                           mdr_bind), as for every other derived state the library keeps; an unannounced
- *                           write to hvac would be missed by the next call's first group */
+ *                           write to hvac would be missed by the next call's first group
+ *   MDR_OPT_GROUP_LA_ORDER  k_step_group launches: which blocks run the FSM lookahead over the next group
+ *                           BEFORE their ticks instead of behind them, so that part of the chip counts while
+ *                           the rest writes reward rows.  MDR_LA_AFTER = none (every block counts last),
+ *                           MDR_LA_ALT1 / _ALT8 / _ALT256 = blocks alternate in runs of 1 / 8 / 256,
+ *                           MDR_LA_BEFORE = every block; | MDR_LA_TAIL_BEFORE = also every block past the
+ *                           launch's first resident round (occupancy API x CUs); value >> 8, when non-zero,
+ *                           is that threshold in blocks instead (for the tests).  Default MDR_LA_ALT8 |
+ *                           MDR_LA_TAIL_BEFORE (measured).  Bit-identical results for every
+ *                           value: the lookahead reads the end words and tick ids only and writes the half
+ *                           of the group mask rows the launch does not read.  The AFFINE staged form
+ *                           (the rollout default) has both orders; the EXACT, first-window and returns
+ *                           forms keep the one order (a second position costs them a wave per SIMD) */
+enum { MDR_LA_AFTER = 0, MDR_LA_ALT1 = 1, MDR_LA_ALT8 = 2, MDR_LA_ALT256 = 3, MDR_LA_BEFORE = 4,
+       MDR_LA_TAIL_BEFORE = 16 };
 enum { MDR_OPT_STEP_TPW = 1, MDR_OPT_FASTDIV = 2, MDR_OPT_WINDOW_PIPELINE = 3, MDR_OPT_SHARDED_OVERLAP = 4,
        MDR_OPT_GREEDY_SORT = 5, MDR_OPT_FORCE_HALO = 6, MDR_OPT_WINDOW_THERMAL = 7,
        MDR_OPT_HALO_OVERLAP = 9, MDR_OPT_ACTOR_GENERIC = 10, MDR_OPT_HALO_IN_COUNTS = 12,
        MDR_OPT_GQ_BAND = 13, MDR_OPT_ACTOR_FP32_FORM = 14, MDR_OPT_GQ_FUSED = 15, MDR_OPT_GQ_ADAPTIVE = 16,
-       MDR_OPT_ACTOR_GRID = 17, MDR_OPT_WINDOW_GROUP = 18, MDR_OPT_ROLLOUT_CARRY = 19 };
+       MDR_OPT_ACTOR_GRID = 17, MDR_OPT_WINDOW_GROUP = 18, MDR_OPT_ROLLOUT_CARRY = 19,
+       MDR_OPT_GROUP_LA_ORDER = 20 };
 enum { MDR_FP32_F16_SPLIT = 0, MDR_FP32_BF16_SPLIT3 = 1 };
 /* (8 was MDR_OPT_ACTOR_PINGPONG, a k_actor schedule measured slower and retired in r04: rejected) */
 enum { MDR_THERMAL_EXACT = 0, MDR_THERMAL_AFFINE = 1 };
@@ -254,6 +269,12 @@ int mdr_window_geometry_check(int64_t n_local, size_t onb_bytes, size_t wah_byte
  * mdr_window_onb_bytes(n_local, 4)) and wah_bytes an end word per house; MDR_EARG otherwise.  Every
  * k_step_group launch checks its context's buffers with it. */
 int mdr_window_group_check(int64_t n_local, int windows, size_t onb_bytes, size_t wah_bytes);
+/* The group rows come in two halves (a launch reads its windows' rows from one and writes the counted
+ * windows' rows to the other): bytes of one half, 4 * mdr_window_onb_bytes(n_local, 4), which is also
+ * where the second half starts; and MDR_OK when group rows of onb_bytes hold both halves and wah_bytes
+ * an end word per house, MDR_EARG otherwise.  Every k_step_group launch checks its buffers with it. */
+size_t mdr_window_group_half_bytes(int64_t n_local);
+int mdr_window_group_halves_check(int64_t n_local, size_t onb_bytes, size_t wah_bytes);
 /* Bytes of the per-tick, per-wave penalty partial rows ([32][tiles_padded][2] doubles, tiles of 128
  * houses rounded up to whole 4-wave blocks) that a common-penalty window launch over n_local houses
  * writes: ceil(ceil(n_local / 128) / 4) * 4 * 32 * 2 * 8.  0 for n_local < 0. */

@@ -185,10 +185,14 @@ struct mdr_ctx {
   Dev<unsigned long long> d_wslab;       // kWinSlots window count slots (mdr_kernels.hip K1W: slab | red | rec)
   int wslab_len = 0;
   Dev<uint64_t> d_onb;                   // per-tick ON lane masks of the next window [tiles][kWindowMax][HPT],
-                                         // then (from onb_rows on) the group rows [tiles][kWinGroup][kWindowMax][HPT]
+                                         // then (from onb_rows on) two halves of group rows
+                                         // [tiles][kWinGroup][kWindowMax][HPT] (group_rows: a launch reads one, writes the other)
   size_t onb_rows = 0;                   // u64 words of the first part (the whole buffer before window groups)
   int win_group = kWinGroup;             // MDR_OPT_WINDOW_GROUP: windows per k_step_group launch (0: k_step_window)
   bool carry = true;                     // MDR_OPT_ROLLOUT_CARRY: a call's last step launch counts the next call's first group
+  int la_order = MDR_LA_ALT8 | MDR_LA_TAIL_BEFORE;  // MDR_OPT_GROUP_LA_ORDER: which blocks of a k_step_group launch count
+                                         // before they step (the measured default)
+  std::map<const void*, int> grp_resident;  // resident blocks of a k_step_group instantiation (occupancy API x CUs)
   Dev<uint32_t> d_wah;                   // FSM word at the end of the next window, per house
   Dev<uint64_t> d_onb2;                  // second set for the count-ahead pipeline (pipe_buffers: a unit)
   Dev<uint32_t> d_wah2;
@@ -651,7 +655,7 @@ int mdr_create(mdr_ctx** out, const mdr_config* cfg) {
     // last block store and load the mask rows of their (empty) tiles too
     const size_t tiles64 = whole_blocks(win_tiles(cfg->n_local) + 1, kCountWaves) * kWinHpt + 1;
     c->onb_rows = tiles64 * kWindowMax;
-    if (c->d_wslab.reserve((size_t)kWinSlots * c->wslab_len) || c->d_onb.reserve((1 + kWinGroup) * c->onb_rows) ||
+    if (c->d_wslab.reserve((size_t)kWinSlots * c->wslab_len) || c->d_onb.reserve((1 + 2 * kWinGroup) * c->onb_rows) ||
         c->d_wah.reserve((size_t)cfg->n_local + 1))
       return cleanup(fail(MDR_ENOMEM, "window count slabs"));
   } else {
@@ -760,6 +764,11 @@ int mdr_set_option(mdr_ctx* c, int option, int64_t value) {
       c->thermal = (int)value;
       break;
     case MDR_OPT_ROLLOUT_CARRY: c->carry = value != 0; break;
+    case MDR_OPT_GROUP_LA_ORDER:
+      if (value < 0 || value > INT32_MAX || (value & 0xf) > MDR_LA_BEFORE || (value & 0xe0))
+        return fail(MDR_EARG, "mdr_set_option: GROUP_LA_ORDER: unknown pattern");
+      c->la_order = (int)value;
+      break;
     default: return fail(MDR_EARG, "mdr_set_option: unknown option");
   }
   HIP_TRY(hipDeviceSynchronize());  // cached graphs may be in flight
@@ -1039,6 +1048,21 @@ extern "C" int mdr_window_group_check(int64_t n_local, int windows, size_t onb_b
   return MDR_OK;
 }
 
+// the two halves of group rows, packed: half h starts h * kWinGroup * mdr_window_onb_bytes(n_local, 4)
+// bytes into the group rows; a launch reads kWinGroup windows of one and writes kWinGroup of the other
+extern "C" size_t mdr_window_group_half_bytes(int64_t n_local) {
+  return (size_t)kWinGroup * mdr_window_onb_bytes(n_local, 4);
+}
+
+extern "C" int mdr_window_group_halves_check(int64_t n_local, size_t onb_bytes, size_t wah_bytes) {
+  if (int rc = mdr_window_group_check(n_local, kWinGroup, onb_bytes, wah_bytes)) return rc;
+  const size_t need = 2 * mdr_window_group_half_bytes(n_local);
+  if (onb_bytes < need)
+    return fail(MDR_EARG, "window group launch: ON-mask rows of " + std::to_string(onb_bytes) +
+                              " B, the two halves of group rows take " + std::to_string(need) + " B");
+  return MDR_OK;
+}
+
 extern "C" size_t mdr_window_pen_bytes(int64_t n_local) {
   if (n_local < 0) return 0;
   return whole_blocks(win_tiles(n_local), 4) * kWindowMax * 2 * sizeof(double);  // (step-window blocks hold 4 waves)
@@ -1180,12 +1204,14 @@ static int launch_step_window(mdr_ctx* c, int mode, bool ka, const uint8_t* acti
 // wts (mdr_rollout_returns): k_step_group_ret instead, `reward` the returns row, wts the staged weights
 // at the group's first tick
 static int launch_step_group(mdr_ctx* c, int mode, bool ka, const uint8_t* action, int64_t act_stride,
-                             const TickArgs* tk, const WinGrp& g, double* reward, int64_t rew_stride,
+                             const TickArgs* tk, const WinGrp& g_in, int wr_half, double* reward, int64_t rew_stride,
                              const WinDrv& dv, hipStream_t st, const double* wts = nullptr) {
+  WinGrp g = g_in;
   if (c->d_onb.capacity() < c->onb_rows) return fail(MDR_ESTATE, "window group launch: no group mask rows");
-  if (int rc = mdr_window_group_check(c->kp.n, kWinGroup, dev_bytes(c->d_onb) - c->onb_rows * sizeof(uint64_t),
-                                      dev_bytes(c->d_wah)))
+  if (int rc = mdr_window_group_halves_check(c->kp.n, dev_bytes(c->d_onb) - c->onb_rows * sizeof(uint64_t),
+                                             dev_bytes(c->d_wah)))
     return rc;
+  if (wr_half != 0 && wr_half != 1) return fail(MDR_EARG, "window group launch: half outside 0..1");
   if (g.nw < 1 || g.nw > kWinGroup || g.la_nw < 0 || g.la_nw > kWinGroup)
     return fail(MDR_EARG, "window group launch: windows outside 1..4");
   for (int i = 0; i < kWinGroup; ++i)
@@ -1193,15 +1219,38 @@ static int launch_step_group(mdr_ctx* c, int mode, bool ka, const uint8_t* actio
       return fail(MDR_EARG, "window group launch: a window of more than 32 ticks");
   const unsigned grid = win_grid(c);
   const KParams kp = c->kp;
-  uint64_t* onb = c->d_onb + c->onb_rows;  // the group rows, behind the first window's
+  // the group rows, behind the first window's: the lookahead writes half wr_half, the stepped windows'
+  // rows are in the other (KA: the count kernel's rows, in front)
+  uint64_t* const halves = c->d_onb + c->onb_rows;
+  const size_t half_words = mdr_window_group_half_bytes(c->kp.n) / sizeof(uint64_t);
+  uint64_t* onb = halves + (size_t)wr_half * half_words;
+  g.rd_onb = ka ? c->d_onb.get() : halves + (size_t)(1 - wr_half) * half_words;
+  // which blocks count before they step (MDR_OPT_GROUP_LA_ORDER)
+  static const unsigned kShift[] = {31u, 0u, 3u, 8u, 31u};
+  const int pat = c->la_order & 0xf;
+  g.la_shift = kShift[pat];
+  g.la_from = pat == MDR_LA_BEFORE ? 0u : UINT32_MAX;
+  auto tail_from = [&](const void* fn) {  // the blocks past the first resident round go early
+    if (ka || wts || c->thermal != MDR_THERMAL_AFFINE) return;  // (forms compiled with the one order: mdr_kernels.hip)
+    if (c->la_order >> 8) { g.la_from = (unsigned)(c->la_order >> 8); return; }  // (the tests' threshold)
+    if (!(c->la_order & MDR_LA_TAIL_BEFORE)) return;
+    auto it = c->grp_resident.find(fn);
+    if (it == c->grp_resident.end()) {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0) != hipSuccess || per_cu < 1) per_cu = 0;
+      it = c->grp_resident.emplace(fn, per_cu * c->n_cu).first;
+    }
+    if (it->second > 0) g.la_from = (unsigned)it->second;
+  };
 #define MDR_SG_L(A, SI, KA_, FO)                                                                               \
   do {                                                                                                         \
+    tail_from(wts ? (const void*)k_step_group_ret<A, kWinHpt, SI, KA_, FO> : (const void*)k_step_group<A, kWinHpt, SI, KA_, FO>); \
     if (wts)                                                                                                   \
       hipLaunchKernelGGL((k_step_group_ret<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, \
-                         act_stride, tk, g, reward, wts, onb, (uint32_t*)c->d_wah, dv);                        \
+                         act_stride, tk, g, reward, wts, onb, (uint32_t*)c->d_wah, c->d_wslab.get(), dv);                        \
     else                                                                                                       \
       hipLaunchKernelGGL((k_step_group<A, kWinHpt, SI, KA_, FO>), dim3(grid), dim3(256), 0, st, kp, action, act_stride, \
-                         tk, g, reward, rew_stride, onb, (uint32_t*)c->d_wah, dv);                             \
+                         tk, g, reward, rew_stride, onb, (uint32_t*)c->d_wah, c->d_wslab.get(), dv);                             \
   } while (0)
 #define MDR_SG_F(A, SI, KA_)                                                         \
   do {                                                                               \
@@ -1304,6 +1353,7 @@ static int window_launches(mdr_ctx* c, const RolloutArgs& a, bool shd, hipStream
 struct CallBoundary {
   bool carried = false, speculate = false;
   int slot_base = 0;
+  int half = 0;  // carried: the half of the group mask rows that holds the carried group (mdr_validity.h group_half)
 };
 static_assert(kCarryGroup == kWinGroup && kCarrySlots == kWinSlots, "mdr_validity.h mirrors the group geometry");
 static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tick* host_ticks,
@@ -1319,16 +1369,16 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
   auto ahead = [&](WinGrp& g, int w1) {
     const bool next_call = w1 >= nw;
     g.la_nw = next_call ? (cb.speculate ? std::min(G, nw) : 0) : std::min(G, nw - w1);
-    for (int i = 0; i < g.la_nw; ++i) g.la_K[i] = s.plan.size(next_call ? i : w1 + i), g.la_slot[i] = slot(w1 + i);
+    for (int i = 0; i < g.la_nw; ++i) g.la_K[i] = s.plan.size(next_call ? i : w1 + i), g.la_slot[i] = (size_t)(slot(w1 + i) - c->d_wslab.get());
     g.la_tick0 = host_ticks[0].tick + (uint64_t)(next_call ? a.n : s.plan.start(w1));
     g.la_by_id = next_call;  // (those ticks are not staged)
   };
   static const WinDrv none{};
   if (!cb.carried) {
     WinGrp g{};
-    g.nw = 1, g.K[0] = K0, g.rec[0] = rec(0), g.first_onb = c->d_onb;
+    g.nw = 1, g.K[0] = K0, g.rec[0] = rec(0);
     ahead(g, 1);
-    if (int rc = launch_step_group(c, a.mode, true, a.act_row(0), a.act_stride, s.tk(0), g, a.rew_row(0), a.rew_stride,
+    if (int rc = launch_step_group(c, a.mode, true, a.act_row(0), a.act_stride, s.tk(0), g, 0, a.rew_row(0), a.rew_stride,
                                    dv, s.st, wts))
       return rc;
     if (a.n > K0)
@@ -1336,7 +1386,8 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
   } else if (int rc = stage_recs(host_ticks, a.n, c->d_ticks, s.st)) {
     return rc;
   }
-  for (int w = cb.carried ? 0 : 1; w < nw; w += G) {
+  int k = 0;  // the group launch: it reads half group_half(.., k) and writes the other
+  for (int w = cb.carried ? 0 : 1; w < nw; w += G, ++k) {
     const int cnt = std::min(G, nw - w), t0 = s.plan.start(w);
     WinRed r{};
     WinGrp g{};
@@ -1351,8 +1402,9 @@ static int window_groups(const WinSeq& s, int G, const WinDrv& dv, const mdr_tic
     hipLaunchKernelGGL(k_win_reduce_group, dim3(r.K[0], cnt), dim3(64 * ncap), 0, s.st, c->kp, r);  // (the larger windows first)
     LAUNCH_CHECK("k_win_reduce_group");
     ahead(g, w + cnt);
-    if (int rc = launch_step_group(c, a.mode, false, a.act_row(t0), a.act_stride, s.tk(w), g, a.rew_row(t0),
-                                   a.rew_stride, none, s.st, wts ? wts + t0 : nullptr))
+    if (int rc = launch_step_group(c, a.mode, false, a.act_row(t0), a.act_stride, s.tk(w), g,
+                                   1 - group_half(cb.carried, cb.half, k), a.rew_row(t0), a.rew_stride, none, s.st,
+                                   wts ? wts + t0 : nullptr))
       return rc;
   }
   return MDR_OK;
@@ -1832,6 +1884,7 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
   if (carried) {
     cb.carried = true;
     cb.slot_base = c->v.carry().slot_base;
+    cb.half = c->v.carry().half;
     c->v.carry_consumed();
   } else {
     c->v.drop_carry();  // an unmatched one: its shards are cleared below
@@ -1862,7 +1915,8 @@ int mdr_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
       c->v.direct_call_issued(DirectCall{true, a.n, a.mode, c->win, c->win_group, next, st});
       if (cb.speculate) {
         CarriedCount k{true, a.n, a.mode, next, c->win, c->win_group, std::min(c->win_group, plan.count()), {},
-                       carry_slot(cb.slot_base, plan.count()), st};
+                       carry_slot(cb.slot_base, plan.count()), st,
+                       group_half(cb.carried, cb.half, group_launches(cb.carried, plan.count(), c->win_group))};
         for (int i = 0; i < k.nw; ++i) k.K[i] = plan.size(i);
         c->v.carry_counted(k);
       }

@@ -188,25 +188,33 @@ struct WinGrp {
   int nw, la_nw;                           // windows stepped; windows counted ahead (0: none)
   int K[kWinGroup], la_K[kWinGroup];       // their ticks (WinPlan sizes)
   const double* rec[kWinGroup];            // the stepped windows' tick records (KA: rec[0], P only)
-  unsigned long long* la_slot[kWinGroup];  // the counted windows' slots
-  const uint64_t* first_onb;               // KA: the first window's mask rows as k_count_window left them
+  size_t la_slot[kWinGroup];               // the counted windows' slots: their offsets into wslab (u64 words)
+  const uint64_t* rd_onb;                  // the stepped windows' mask rows: the group rows of the OTHER half
+                                           // (KA: the first window's rows as k_count_window left them)
   uint64_t la_tick0;                       // id of the first counted tick (ids are consecutive) ...
   int la_by_id;                            // ... which the lookahead takes where tkp does not cover the counted
                                            // ticks: the NEXT call's first group (not staged yet; KA takes ids anyway)
+  // block b runs its lookahead BEFORE its ticks when ((b >> la_shift) & 1) || b >= la_from, else behind
+  // them (MDR_OPT_GROUP_LA_ORDER; {31, UINT_MAX}: every block behind).  The results do not depend on it
+  unsigned la_shift, la_from;
 };
-// onb: the group rows [tile][kWinGroup][kWindowMax][HPT] — read (the stepped windows'; KA reads
-// first_onb instead), then replaced by the counted windows'; wah: the end word after the last
-// stepped window, replaced by the one after the last counted window.  action / tkp / reward: at the
-// group's first tick.  KA: the group is the call's first window alone, its drivers in dv.
+// onb: the group rows [tile][kWinGroup][kWindowMax][HPT] the lookahead writes (the counted windows'),
+// one half of the context's two; g.rd_onb: the rows the launch reads (the stepped windows'), the other
+// half, so a block may count before it steps.  wah: the end word after the last stepped window,
+// replaced by the one after the last counted window (each wave reads its houses' words before it
+// rewrites them).  action / tkp / reward: at the group's first tick.  KA: the group is the call's first
+// window alone, its drivers in dv.  wslab: the window count slots (the counted windows': g.la_slot).
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
 __global__ void k_step_group(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, WinGrp g,
-                             double* reward, int64_t rew_stride, uint64_t* onb, uint32_t* wah, WinDrv dv);
+                             double* reward, int64_t rew_stride, uint64_t* onb, uint32_t* wah, unsigned long long* wslab,
+                             WinDrv dv);
 // ... that writes no reward row (mdr_rollout_returns): returns[i] <- returns[i] + wts[j] r_i(j) over the
 // group's ticks j in order, a multiply then an add per tick, the sum kept in registers between the one
 // load and the one store of the launch.  wts: the call's staged weights at the group's first tick.
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
 __global__ void k_step_group_ret(KParams p, const uint8_t* action, int64_t act_stride, const TickArgs* tkp, WinGrp g,
-                                 double* returns, const double* wts, uint64_t* onb, uint32_t* wah, WinDrv dv);
+                                 double* returns, const double* wts, uint64_t* onb, uint32_t* wah,
+                                 unsigned long long* wslab, WinDrv dv);
 // k_win_reduce for the windows of a group in one launch: block (j, w) is tick j of window w
 struct WinRed {
   int nw;

@@ -1465,15 +1465,28 @@ struct WinHouses {
   template <bool RET = false>
   __device__ __forceinline__ void load(const KParams& p, const WinTile<HPT>& t, const uint32_t* fsm,
                                        const double* returns = nullptr) {
+    load_state<RET>(p, t, returns);
+    load_fsm(p, t, fsm);
+  }
+  // ... in two parts, for a kernel that runs its FSM lookahead between them (step_group_body): the
+  // thermal state and parameters,
+  template <bool RET = false>
+  __device__ __forceinline__ void load_state(const KParams& p, const WinTile<HPT>& t, const double* returns = nullptr) {
     params_ok = !*p.params_bad && p.fast_tick_ok;
 #pragma unroll
     for (int h = 0; h < HPT; ++h) {
       const uint32_t i = t.idx[h];
       T[h] = p.t_air[i]; Tm[h] = p.t_mass[i]; ua[h] = p.ua[i]; hm[h] = p.hm[i]; tg[h] = p.target[i];
       ca[h] = p.ca[i]; cm[h] = p.cm[i];
-      w[h] = fsm[i];
-      cls[h] = p.cap_idx[i];
       if constexpr (RET) ret[h] = t.v[h] ? returns[t.i0 + 64u * h] : 0.0;
+    }
+  }
+  // and the FSM word and capacity class, all a lookahead needs
+  __device__ __forceinline__ void load_fsm(const KParams& p, const WinTile<HPT>& t, const uint32_t* fsm) {
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) {
+      w[h] = fsm[t.idx[h]];
+      cls[h] = p.cap_idx[t.idx[h]];
     }
   }
 
@@ -1767,20 +1780,34 @@ __global__ void __launch_bounds__(256) k_step_window(KParams p, const uint8_t* _
 // The group's last end word is the one in wah on entry: the producer of the group's masks left it
 // after its last window.  Each counted window has its own LDS count rows, so one barrier separates
 // the lookahead's runs from their flushes.  No wave waits for another wave's data.
+// The lookahead needs the end word, the class, the tick ids and the Philox key only, and writes mask
+// rows of the half the launch does not read: a block runs it before or behind its ticks (WinGrp
+// la_shift / la_from), so that part of the chip counts (no memory traffic) while the rest writes reward
+// rows, instead of every block counting at the end of its round with HBM idle.
+// The counted windows' slots are named by their offsets into wslab, a __restrict__ kernel argument like
+// onb and wah: the compiler must see that nothing an early lookahead writes (mask rows, end words, the
+// shard adds) can be what the tick loop reads through g.rec / g.rd_onb, or it turns the loop's scalar
+// loads into vector loads (+24 VGPRs: a wave per SIMD lost).
 // RET (k_step_group_ret, mdr_rollout_returns): `reward` is the houses' returns row, accumulated in
 // registers over the group's windows (WinHouses::ticks<..., RET>) with the staged weights wts[tick of
 // the group]; no reward row is written and rew_stride is unused.
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM, bool RET>
 __device__ __forceinline__ void step_group_body(const KParams& p, const uint8_t* action, int64_t act_stride,
                                                 const TickArgs* tkp, const WinGrp& g, double* reward,
-                                                int64_t rew_stride, uint64_t* onb, uint32_t* wah, const WinDrv& dv,
-                                                const double* wts) {
+                                                int64_t rew_stride, uint64_t* onb, uint32_t* wah,
+                                                unsigned long long* wslab, const WinDrv& dv, const double* wts) {
   __shared__ unsigned s_cnt[kWinGroup][4][kWinMax * kWinCap];
   const int wv = threadIdx.x >> 6;
   const WinTile<HPT> t(p);
-  uint64_t* onb_w = onb + (size_t)t.tile * kWinGroup * HPT * kWinMax;  // this wave's rows [kWinGroup][kWinMax][HPT]
-  // the stepped windows' rows (KA: the first window's, from the count kernel)
-  const uint64_t* onb_r = KA ? g.first_onb + (size_t)t.tile * HPT * kWinMax : onb_w;
+  // this wave's rows [kWinGroup][kWinMax][HPT] of the half the lookahead writes, and the stepped windows'
+  // rows: the other half (KA: the first window's, from the count kernel)
+  uint64_t* onb_w = onb + (size_t)t.tile * kWinGroup * HPT * kWinMax;
+  const uint64_t* onb_r = g.rd_onb + (size_t)t.tile * (KA ? 1 : kWinGroup) * HPT * kWinMax;
+  // the block's order (block-uniform: a barrier sits between the lookahead's runs and its flushes).
+  // Compiled for the AFFINE staged forms alone: in the EXACT, KA and RET forms the second position costs
+  // the 4 to 8 VGPRs that are a wave per SIMD there, so they keep the one order (the lookahead last)
+  constexpr bool kEarlyForm = FORM == MDR_THERMAL_AFFINE && !KA && !RET;
+  const bool early = kEarlyForm && (((blockIdx.x >> g.la_shift) & 1u) != 0 || blockIdx.x >= g.la_from);
   // KA: lane j = tick j's negated signal penalty (k_step_window's)
   uint32_t ns_lo = 0, ns_hi = 0;
   if (KA) {
@@ -1794,9 +1821,44 @@ __device__ __forceinline__ void step_group_body(const KParams& p, const uint8_t*
     ns_hi = (uint32_t)((uint64_t)__double_as_longlong(ns) >> 32);
   }
 
-  // ---- the group's windows (the FSM word at the group's end came with the ON masks)
+  // ---- the FSM word at the group's end (it came with the ON masks) and the class: what the lookahead needs
   WinHouses<HPT, FORM> hs;
-  hs.template load<RET>(p, t, wah, reward);
+  hs.load_fsm(p, t, wah);
+  int grp_ticks = 0;  // the first counted tick, from the group's
+  for (int gi = 0; gi < g.nw; ++gi) grp_ticks += g.K[gi];
+
+  // ---- lookahead: the next group's ON masks, end word and class counts, window by window.  It runs on
+  // a copy of the word (hs.w is the one the launch stores to p.hvac) and touches neither the thermal
+  // state nor the stepped windows' rows (the other half), so a block may run it before its ticks
+  auto lookahead = [&]() {
+    uint64_t cmk[HPT][kWinCap];
+    win_classes<HPT>(t, hs.cls, cmk);
+    uint32_t w_la[HPT];
+#pragma unroll
+    for (int h = 0; h < HPT; ++h) w_la[h] = hs.w[h];
+    const bool by_id = KA || g.la_by_id != 0;  // (wave-uniform: a kernel argument)
+    uint64_t la_tick = g.la_tick0;
+    int tick_off = grp_ticks;
+    for (int li = 0; li < g.la_nw; ++li) {
+      const int la_K = g.la_K[li];
+      win_run<ACT, HPT>(p, w_la, cmk, t, by_id ? nullptr : tkp + tick_off, la_tick, la_K,
+                        ACT == MDR_ACT_BUFFER ? action + (int64_t)tick_off * act_stride : nullptr, act_stride,
+                        s_cnt[li][wv], onb_w + li * (kWinMax * HPT));
+      tick_off += la_K;
+      la_tick += (uint64_t)la_K;
+    }
+#pragma unroll
+    for (int h = 0; h < HPT; ++h)
+      if (t.v[h]) wah[t.i0 + 64u * h] = w_la[h];
+    __syncthreads();
+    for (int li = 0; li < g.la_nw; ++li) win_flush(p, g.la_K[li], s_cnt[li], wslab + g.la_slot[li]);
+  };
+  if constexpr (kEarlyForm)
+    if (g.la_nw > 0 && early) lookahead();
+
+  // ---- the group's windows (state and parameters are loaded behind an early lookahead, so nothing of
+  // them is live across it)
+  hs.template load_state<RET>(p, t, reward);
   hs.form(p);
   int tick_off = 0;  // the window's first tick, from the group's
   for (int gi = 0; gi < g.nw; ++gi) {
@@ -1808,26 +1870,7 @@ __device__ __forceinline__ void step_group_body(const KParams& p, const uint8_t*
   }
   hs.template store<RET>(p, t, reward);
 
-  // ---- lookahead: the next group's ON masks, end word and class counts, window by window
-  if (g.la_nw > 0) {
-    uint64_t cmk[HPT][kWinCap];
-    win_classes<HPT>(t, hs.cls, cmk);
-    const bool by_id = KA || g.la_by_id != 0;  // (wave-uniform: a kernel argument)
-    uint64_t la_tick = g.la_tick0;
-    for (int li = 0; li < g.la_nw; ++li) {
-      const int la_K = g.la_K[li];
-      win_run<ACT, HPT>(p, hs.w, cmk, t, by_id ? nullptr : tkp + tick_off, la_tick, la_K,
-                        ACT == MDR_ACT_BUFFER ? action + (int64_t)tick_off * act_stride : nullptr, act_stride,
-                        s_cnt[li][wv], onb_w + li * (kWinMax * HPT));
-      tick_off += la_K;
-      la_tick += (uint64_t)la_K;
-    }
-#pragma unroll
-    for (int h = 0; h < HPT; ++h)
-      if (t.v[h]) wah[t.i0 + 64u * h] = hs.w[h];
-    __syncthreads();
-    for (int li = 0; li < g.la_nw; ++li) win_flush(p, g.la_K[li], s_cnt[li], g.la_slot[li]);
-  }
+  if (g.la_nw > 0 && !early) lookahead();
 }
 
 template <int ACT, int HPT, bool SIMPLE, bool KA, int FORM>
@@ -1835,9 +1878,9 @@ __global__ void __launch_bounds__(256) k_step_group(KParams p, const uint8_t* __
                                                     int64_t act_stride, const TickArgs* __restrict__ tkp, WinGrp g,
                                                     double* __restrict__ reward, int64_t rew_stride,
                                                     uint64_t* __restrict__ onb, uint32_t* __restrict__ wah,
-                                                    WinDrv dv) {
-  step_group_body<ACT, HPT, SIMPLE, KA, FORM, false>(p, action, act_stride, tkp, g, reward, rew_stride, onb, wah, dv,
-                                                     nullptr);
+                                                    unsigned long long* __restrict__ wslab, WinDrv dv) {
+  step_group_body<ACT, HPT, SIMPLE, KA, FORM, false>(p, action, act_stride, tkp, g, reward, rew_stride, onb, wah, wslab,
+                                                     dv, nullptr);
 }
 
 // k_step_group that adds the weighted rewards of the group's ticks to returns[i] instead of writing
@@ -1848,8 +1891,9 @@ __global__ void __launch_bounds__(256) k_step_group_ret(KParams p, const uint8_t
                                                         int64_t act_stride, const TickArgs* __restrict__ tkp,
                                                         WinGrp g, double* __restrict__ returns,
                                                         const double* __restrict__ wts, uint64_t* __restrict__ onb,
-                                                        uint32_t* __restrict__ wah, WinDrv dv) {
-  step_group_body<ACT, HPT, SIMPLE, KA, FORM, true>(p, action, act_stride, tkp, g, returns, 0, onb, wah, dv, wts);
+                                                        uint32_t* __restrict__ wah,
+                                                        unsigned long long* __restrict__ wslab, WinDrv dv) {
+  step_group_body<ACT, HPT, SIMPLE, KA, FORM, true>(p, action, act_stride, tkp, g, returns, 0, onb, wah, wslab, dv, wts);
 }
 
 // --------------------------------------------------------------------------------------- K1C
@@ -2217,10 +2261,11 @@ MDR_INST_WIN(MDR_ACT_BUFFER)
 
 #define MDR_INST_GRP_F(A, SI, KA_, FO)                                                                         \
   template __global__ void k_step_group<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
-                                                                 WinGrp, double*, int64_t, uint64_t*, uint32_t*, WinDrv); \
+                                                                 WinGrp, double*, int64_t, uint64_t*, uint32_t*,  \
+                                                                 unsigned long long*, WinDrv);                 \
   template __global__ void k_step_group_ret<A, kWinHpt, SI, KA_, FO>(KParams, const uint8_t*, int64_t, const TickArgs*, \
                                                                      WinGrp, double*, const double*, uint64_t*,  \
-                                                                     uint32_t*, WinDrv);
+                                                                     uint32_t*, unsigned long long*, WinDrv);
 #define MDR_INST_GRP(A)                                                                                    \
   MDR_INST_GRP_F(A, true, false, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, false, MDR_THERMAL_EXACT)     \
   MDR_INST_GRP_F(A, true, true, MDR_THERMAL_EXACT) MDR_INST_GRP_F(A, false, true, MDR_THERMAL_EXACT)       \

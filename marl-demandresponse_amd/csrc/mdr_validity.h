@@ -32,11 +32,20 @@ struct CarriedCount {
   int K[kCarryGroup] = {};  // their ticks
   int slot_base = 0;       // window w of the counted call is in slot carry_slot(slot_base, w)
   const void* stream = nullptr;
+  int half = 0;            // the half of the group mask rows that holds the counted windows' rows (group_half)
 };
 // window w of a call whose first window is in slot `base`; the call after one of nw windows starts at
 // carry_slot(base, nw): consecutive windows take consecutive slots across the call boundary, so a
 // launch's stepped group (<= kCarryGroup) and counted group (<= kCarryGroup) never share a slot
 constexpr int carry_slot(int base, int w) { return (base + w) % kCarrySlots; }
+// The group mask rows come in two halves: a step launch reads its windows' rows from one and writes the
+// counted windows' rows to the other (so a block may count before it steps).  The KA launch of a plain
+// call reads the count kernel's rows and writes half 0; a carried call starts from the half its record
+// names.  The k-th group launch of a call (from 0) reads half group_half(carried, half_in, k) and writes
+// the other; behind a call of L group launches the counted rows are in group_half(carried, half_in, L).
+constexpr int group_half(bool carried, int half_in, int k) { return ((carried ? half_in : 0) + k) & 1; }
+// the group launches of a call of nw windows in groups of G (a plain call's first window goes to the KA launch)
+constexpr int group_launches(bool carried, int nw, int G) { return ((carried ? nw : nw - 1) + G - 1) / G; }
 
 // the last direct grouped rollout that could have speculated (the shape the next one must continue)
 struct DirectCall {
@@ -205,10 +214,12 @@ class Validity {
       slots_dirty_ = true;
       carry_n_.dropped += 1;
     }
+    carry_.half = 0;  // (a call that starts from no record starts at half 0)
   }
   void carry_consumed() {  // by the rollout it was counted for
     if (carry_.on) carry_n_.consumed += 1;
     carry_.on = false;
+    carry_.half = 0;  // (the consumer took it with the slot base before this)
   }
   void carry_counted(const CarriedCount& k) {  // behind the fully issued sequence whose last launch counted it
     carry_ = k;
@@ -232,6 +243,7 @@ class Validity {
     early_.on = false;
     if (carry_.on) carry_n_.dropped += 1;
     carry_.on = false;
+    carry_.half = 0;
     last_.on = false;
   }
 

@@ -25,7 +25,8 @@ ERRORS = {-1: "MDR_EARG", -2: "MDR_EHIP", -3: "MDR_ERCCL", -4: "MDR_ENOMEM", -5:
 OPTIONS = {"step_tpw": 1, "fastdiv": 2, "window_pipeline": 3, "sharded_overlap": 4, "greedy_sort": 5, "halo_overlap": 9, "actor_generic": 10,
            "force_halo": 6, "window_thermal": 7, "halo_in_counts": 12,
            "gq_band": 13, "actor_fp32_form": 14, "gq_fused": 15, "gq_adaptive": 16, "actor_grid": 17, "window_group": 18,
-           "rollout_carry": 19}
+           "rollout_carry": 19, "group_la_order": 20}
+LA_AFTER, LA_ALT1, LA_ALT8, LA_ALT256, LA_BEFORE, LA_TAIL_BEFORE = 0, 1, 2, 3, 4, 16  # MDR_OPT_GROUP_LA_ORDER
 THERMAL_EXACT, THERMAL_AFFINE = 0, 1
 FP32_F16_SPLIT, FP32_BF16_SPLIT3 = 0, 1  # MDR_OPT_ACTOR_FP32_FORM
 HEADS = {"softmax": 0, "q": 1}  # MDR_HEAD_* (mdr_actor_set_head)
@@ -154,6 +155,8 @@ SIGNATURES = {
     "mdr_window_onb_bytes": (C.c_size_t, [I64, I]),
     "mdr_window_geometry_check": (I, [I64, C.c_size_t, C.c_size_t]),
     "mdr_window_group_check": (I, [I64, I, C.c_size_t, C.c_size_t]),
+    "mdr_window_group_half_bytes": (C.c_size_t, [I64]),
+    "mdr_window_group_halves_check": (I, [I64, C.c_size_t, C.c_size_t]),
     "mdr_window_pen_bytes": (C.c_size_t, [I64]),
     "mdr_window_pen_check": (I, [I64, C.c_size_t]),
     "mdr_window_stats_bytes": (C.c_size_t, [I64]),

@@ -125,7 +125,8 @@ class HipShard:
         step_tpw, fastdiv, window_pipeline, sharded_overlap, greedy_sort, force_halo, halo_overlap,
         actor_generic, window_thermal, halo_in_counts, gq_band, actor_fp32_form, gq_fused, gq_adaptive;
         actor_grid: v >= 1 caps the fused actor's grid at min(v, CUs) blocks, 0 = the default grid,
-        the same outputs bit for bit — the tests' way to many tiles per wave; negative: MDR_EARG)."""
+        the same outputs bit for bit — the tests' way to many tiles per wave; negative: MDR_EARG;
+        group_la_order: _lib.LA_*, which blocks of a k_step_group launch count before they step)."""
         L.check(self.lib.mdr_set_option(self.ctx, L.OPTIONS[name], int(value)), f"mdr_set_option({name})")
 
     def params_changed(self):
