@@ -958,6 +958,45 @@ int mdr_rollout_sharded(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const 
  * the step of tick t (that tick's reward written by the next launch, bit-identical). */
 int mdr_rollout_sharded_mode(mdr_ctx* ctx, int* window_pipeline, int* tick_overlap);
 
+/* ---- environment batches: many independent small clusters in one context ------------------ */
+/* A batch is n_envs independent clusters of env_len <= MDR_BATCH_MAX_LEN houses each (the same
+ * mdr_config: dt, lockout, capacity table, reward weights), resident in ONE context and stepped by ONE
+ * launch per rollout call: a cluster fits one workgroup, so its per-tick cluster power never leaves
+ * the block (k_batch_rollout).  Layout: cluster e is elements [e * S, e * S + env_len) of the bound
+ * SoA arrays, S = mdr_batch_stride(env_len) = 128 * ceil(env_len / 128); the pad elements in between
+ * are never read into a result, written, counted or rewarded.
+ *
+ * mdr_batch_set declares the segmentation of a bound context created with n_local = n_global =
+ * n_envs * S and global_offset 0; seeds[e] (host) is cluster e's Philox key for MDR_ACT_RANDOM: house
+ * i of cluster e draws what house i of a stand-alone context with that seed draws.  The bound arrays
+ * must be 16-byte aligned.  Calling it again with the same geometry replaces the seeds.
+ * MDR_EARG: n_envs < 1, env_len outside 1..MDR_BATCH_MAX_LEN, a context of another size or with a
+ * global offset, a common penalty mode, a communicator or world > 1.  MDR_ESTATE: not bound.
+ * After it the entry points that form a cluster-level quantity over the whole context (counts, step,
+ * the rollouts, stats, greedy, actor, obs and their sharded forms) answer MDR_ESTATE: nobody gets a
+ * power summed across clusters. */
+#define MDR_BATCH_MAX_LEN 1024
+size_t mdr_batch_stride(int64_t env_len); /* 0 for env_len < 1 */
+int mdr_batch_set(mdr_ctx* ctx, int32_t n_envs, int32_t env_len, const uint64_t* seeds);
+/* n_ticks steps of every cluster in one launch.  ticks: host [n_envs][n_ticks], cluster e's drivers
+ * (its own outdoor temperature, solar gain, signal and tick ids), staged into a context-owned buffer.
+ * action (MDR_ACT_BUFFER) / reward: rows of n_envs * S elements in the layout above, advancing by
+ * act_stride / rew_stride elements per tick (rew_stride 0: one row that keeps the last tick);
+ * reward 16-byte aligned, rew_stride even.  p_out: device doubles [n_envs] <- every cluster's power of
+ * the last tick.  Per cluster bit for bit the loop of mdr_step(action_mode = lookahead = the source) on
+ * a stand-alone context of env_len houses, with env_len in place of n_global in the signal penalty.
+ * MDR_EARG (before anything is staged or launched): null ticks / reward / p_out, n_ticks < 1, an
+ * unknown source, MDR_ACT_BUFFER without actions, a misaligned reward.  MDR_ESTATE: no mdr_batch_set. */
+int mdr_batch_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
+                      int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
+                      double* p_out, void* stream);
+/* float32 obs[n_envs][env_len][n_feat]: mdr_obs of every cluster, MDR_COMM_RING only (the ring wraps
+ * inside the cluster).  sc: host [n_envs], each cluster's scalars; p_dev, when non-NULL, overrides
+ * sc[e].p with the device doubles [n_envs] mdr_batch_rollout wrote.  MDR_EARG: MDR_COMM_TABLE, a
+ * halo or msg_all pointer, n_feat not matching the flags.  MDR_ESTATE: no mdr_batch_set. */
+int mdr_batch_obs(mdr_ctx* ctx, const mdr_obs_spec* spec, const mdr_obs_scalars* sc, const double* p_dev,
+                  float* obs, void* stream);
+
 /* ---- diagnostics ------------------------------------------------------------------------ */
 /* Memory-floor probe: the loads/stores of one mdr_step over the bound arrays with no arithmetic
  * (writes the state back unchanged, garbage into reward).  Roofline calibration only. */

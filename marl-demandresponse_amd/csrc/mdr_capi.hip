@@ -269,6 +269,11 @@ struct mdr_ctx {
   int64_t graph_launches[2] = {0, 0};  // hipGraphLaunch calls: rollout graphs, actor rollout graphs
   int64_t graphs_guarded = 0;            // captured graphs the memset guard walked (graph_memset_guard)
   int64_t graph_nodes_checked = 0;       //   and their nodes
+  // a batch of independent clusters (mdr_batch_set): batch.n_envs != 0 is the mark
+  BatchArgs batch{};
+  Dev<uint64_t> d_batch_seeds;   // [n_envs] the clusters' Philox keys
+  Dev<TickArgs> d_batch_ticks;   // [n_envs][n_ticks] of the call being issued (batch_reserve)
+  Dev<double> d_batch_sc;        // [n_envs][4] mdr_batch_obs' scalars
   // interpolated base power (row a10): grid | table | capacities
   Dev<double> d_interp;
   InterpArgs interp{};
@@ -279,6 +284,15 @@ namespace {
 
 // the context has a communicator (the library's RCCL one, or the caller's host collectives)
 bool has_comm(const mdr_ctx* c) { return c->comm != nullptr || c->host.allreduce != nullptr; }
+
+// bound, and ONE cluster: what every entry point that forms a cluster-level quantity over the whole
+// context asks first (a batch of clusters has the mdr_batch_* entry points)
+int cluster_ready(const mdr_ctx* c, const std::string& who) {
+  if (!c->bound) return fail(MDR_ESTATE, who + ": context not bound");
+  if (c->batch.n_envs)
+    return fail(MDR_ESTATE, who + ": the context holds a batch of clusters (mdr_batch_set); use the mdr_batch_* entry points");
+  return MDR_OK;
+}
 
 // in-place allreduce ordered on st (op: the mdr_rccl_allreduce dtype codes; 0 = 64-bit sum, which
 // the unsigned count slabs use: the same bits for sums below 2^63)
@@ -817,7 +831,7 @@ int mdr_populate(mdr_ctx* c, const mdr_pop_spec* sp, void* stream) {
 int mdr_power_counts(mdr_ctx* c, const uint8_t* action, int mode, uint64_t tick, void* stream) {
   enter_writer(c);
   if (!c) return fail(MDR_EARG, "mdr_power_counts: null ctx");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_power_counts: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_power_counts")) return rc_;
   if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
     return fail(MDR_EARG, "mdr_power_counts: bad action source");
   Sequence seq(c->v);
@@ -840,7 +854,7 @@ int mdr_step(mdr_ctx* c, const uint8_t* action, int mode, const mdr_tick* tick, 
              int lookahead, int ctrl, uint8_t* ctrl_out, double* p_out, void* stream) {
   enter_writer(c);
   if (!c || !tick || !reward) return fail(MDR_EARG, "mdr_step: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_step: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_step")) return rc_;
   if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
     return fail(MDR_EARG, "mdr_step: bad action source");
   if (lookahead && (!check_mode(lookahead) || !lookahead_ok(lookahead)))
@@ -1828,7 +1842,7 @@ static int rollout_stats_path(mdr_ctx* c, int mode, const std::string& who) {
 
 int mdr_rollout_stats_path(mdr_ctx* c, int mode) {
   if (!c) return fail(MDR_EARG, "mdr_rollout_stats_path: null ctx");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_stats_path: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_rollout_stats_path")) return rc_;
   if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_stats_path: bad action source");
   return rollout_stats_path(c, mode, "mdr_rollout_stats");
 }
@@ -1848,7 +1862,7 @@ static int rollout_preamble(mdr_ctx* c, const char* who, bool ptrs, const Rollou
   if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, std::string(who) + ": bad argument");
   if (flags & kDropBegun) c->v.drop_early_count();
   c->v.state_may_change((flags & kSettlesCarry) != 0);
-  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (int rc_ = cluster_ready(c, std::string(who))) return rc_;
   if ((flags & kShardedOnly) && !has_comm(c))
     return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
   if (!check_mode(a.mode) || (a.mode == MDR_ACT_BUFFER && !a.action))
@@ -1947,7 +1961,7 @@ static int returns_path(const mdr_ctx* c, int mode) {
 
 int mdr_rollout_returns_path(mdr_ctx* c, int mode) {
   if (!c) return fail(MDR_EARG, "mdr_rollout_returns_path: null ctx");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_returns_path: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_rollout_returns_path")) return rc_;
   if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_returns_path: bad action source");
   return returns_path(c, mode);
 }
@@ -2184,7 +2198,7 @@ static int check_obs_spec(const mdr_obs_spec* sp, const char* who) {
 int mdr_obs(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const double* p_dev,
             float* obs, void* stream) {
   if (!c || !sp || !sc || !obs) return fail(MDR_EARG, "mdr_obs: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_obs: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_obs")) return rc_;
   if (int rc = check_obs_spec(sp, "mdr_obs")) return rc;
   ObsArgs o = obs_args(c, sp, sc);
   const int lo = sp->n_comm / 2, hi = (sp->n_comm + 1) / 2;
@@ -2200,7 +2214,7 @@ int mdr_obs(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const
 
 int mdr_msg_pack(mdr_ctx* c, const mdr_obs_spec* sp, float* out, void* stream) {
   if (!c || !sp || !out) return fail(MDR_EARG, "mdr_msg_pack: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_msg_pack: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_msg_pack")) return rc_;
   ObsArgs o = obs_args(c, sp, nullptr);
   if (o.msg_w > 16) return fail(MDR_EARG, "mdr_msg_pack: message wider than 16");
   hipLaunchKernelGGL(k_msg_pack, dim3(blocks(c->kp.n, 256)), dim3(256), 0, S(stream), c->kp, o, out);
@@ -2215,6 +2229,116 @@ int mdr_halo_pack(mdr_ctx* c, const mdr_obs_spec* sp, float* out, void* stream) 
   if (lo + hi == 0) return MDR_OK;
   hipLaunchKernelGGL(k_halo_pack, dim3(1), dim3(64), 0, S(stream), c->kp, o, lo, hi, out);
   LAUNCH_CHECK("k_halo_pack");
+  return MDR_OK;
+}
+
+// ------------------------------------------------------------------------------------ batch
+// E independent clusters of <= kBatchMaxLen houses in one context, one launch per rollout call
+// (mdr.h "environment batches").
+size_t mdr_batch_stride(int64_t env_len) { return env_len < 1 ? 0 : (size_t)((env_len + 127) / 128 * 128); }
+
+static int batch_ready(const mdr_ctx* c, const char* who) {
+  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (!c->batch.n_envs) return fail(MDR_ESTATE, std::string(who) + ": no batch declared (mdr_batch_set)");
+  return MDR_OK;
+}
+
+// room for n elements in a buffer queued work may still read: synchronise, then reserve
+extern "C++" template <class T>
+static int batch_reserve(Dev<T>& b, size_t n, const char* name) {
+  if (n <= b.capacity()) return MDR_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  return dev_reserve(b, n, name);
+}
+
+int mdr_batch_set(mdr_ctx* c, int32_t n_envs, int32_t env_len, const uint64_t* seeds) {
+  enter_writer(c);
+  if (!c || !seeds) return fail(MDR_EARG, "mdr_batch_set: null argument");
+  if (!c->bound) return fail(MDR_ESTATE, "mdr_batch_set: context not bound");
+  if (n_envs < 1) return fail(MDR_EARG, "mdr_batch_set: n_envs < 1");
+  if (env_len < 1 || env_len > kBatchMaxLen)
+    return fail(MDR_EARG, "mdr_batch_set: env_len outside 1..1024 (a cluster is stepped by one workgroup)");
+  static_assert(kBatchMaxLen == MDR_BATCH_MAX_LEN, "the header's limit is the kernels'");
+  const int64_t stride = (int64_t)mdr_batch_stride(env_len);
+  if (c->kp.n != (int64_t)n_envs * stride || c->kp.n_global != c->kp.n || c->kp.goff != 0)
+    return fail(MDR_EARG, "mdr_batch_set: the context must have n_local = n_global = n_envs * mdr_batch_stride(env_len), offset 0");
+  if (win_common(c)) return fail(MDR_EARG, "mdr_batch_set: the common penalty modes are not batched (individual_L2 only)");
+  if (has_comm(c) || c->world > 1) return fail(MDR_EARG, "mdr_batch_set: a context with a communicator holds no batch");
+  const KParams& k = c->kp;
+  const uintptr_t al = (uintptr_t)k.t_air | (uintptr_t)k.t_mass | (uintptr_t)k.hvac | (uintptr_t)k.ua | (uintptr_t)k.ca |
+                       (uintptr_t)k.cm | (uintptr_t)k.hm | (uintptr_t)k.target | (uintptr_t)k.cap_idx;
+  if (al & 15) return fail(MDR_EARG, "mdr_batch_set: the bound arrays must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  if (int rc = batch_reserve(c->d_batch_seeds, (size_t)n_envs, "d_batch_seeds")) return rc;
+  HIP_TRY(hipDeviceSynchronize());  // (a queued launch may still read the old keys)
+  HIP_TRY(hipMemcpy(c->d_batch_seeds, seeds, (size_t)n_envs * sizeof(uint64_t), hipMemcpyHostToDevice));
+  destroy_graphs(c);
+  c->batch = BatchArgs{n_envs, env_len, (int)stride, c->d_batch_seeds};
+  c->v.state_replaced();  // (nothing the single-cluster sequences derived is of this layout)
+  return MDR_OK;
+}
+
+int mdr_batch_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride, int mode,
+                      double* reward, int64_t rew_stride, double* p_out, void* stream) {
+  enter_writer(c);
+  if (!c || !ticks || !reward || !p_out || n < 1) return fail(MDR_EARG, "mdr_batch_rollout: bad argument");
+  if (int rc = batch_ready(c, "mdr_batch_rollout")) return rc;
+  if (!check_mode(mode) || (mode == MDR_ACT_BUFFER && !action))
+    return fail(MDR_EARG, "mdr_batch_rollout: bad action source");
+  if (((uintptr_t)reward & 15) || (rew_stride & 1))
+    return fail(MDR_EARG, "mdr_batch_rollout: reward rows must be 16-byte aligned (an even rew_stride)");
+  if ((int64_t)c->batch.n_envs * n > ((int64_t)1 << 27)) return fail(MDR_EARG, "mdr_batch_rollout: n_envs * n_ticks > 2^27");
+  hipStream_t st = S(stream);
+  const size_t nrec = (size_t)c->batch.n_envs * (size_t)n;
+  if (int rc = batch_reserve(c->d_batch_ticks, nrec, "d_batch_ticks")) return rc;
+  Sequence seq(c->v, Sequence::kRollout);
+  if (c->v.coef_dirty()) {  // refresh_if_dirty over the clusters' houses (the pads hold nothing)
+    HIP_TRY(hipMemsetAsync(c->d_flags, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_batch_refresh, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp, c->batch, c->d_flags);
+    LAUNCH_CHECK("k_batch_refresh");
+    c->v.coef_refreshed();
+  }
+  // stream order: an earlier launch reading d_batch_ticks on st precedes this write
+  static_assert(sizeof(TickArgs) == sizeof(mdr_tick), "mdr_tick records are copied as TickArgs");
+  HIP_TRY(hipMemcpyAsync(c->d_batch_ticks, ticks, nrec * sizeof(TickArgs), hipMemcpyHostToDevice, st));
+  const dim3 grid((unsigned)c->batch.n_envs), block(64u * blocks(c->batch.env_len, 128));
+#define MDR_LAUNCH_BATCH(A)                                                                                      \
+  hipLaunchKernelGGL((k_batch_rollout<A>), grid, block, 0, st, c->kp, c->batch, c->d_batch_ticks.get(), n, action, \
+                     act_stride, reward, rew_stride, p_out)
+  switch (mode) {
+    case MDR_ACT_BUFFER: MDR_LAUNCH_BATCH(MDR_ACT_BUFFER); break;
+    case MDR_ACT_RANDOM: MDR_LAUNCH_BATCH(MDR_ACT_RANDOM); break;
+    case MDR_ACT_ALWAYS_ON: MDR_LAUNCH_BATCH(MDR_ACT_ALWAYS_ON); break;
+    case MDR_ACT_BANGBANG: MDR_LAUNCH_BATCH(kActBangBang); break;
+    default: MDR_LAUNCH_BATCH(kActDeadband); break;
+  }
+#undef MDR_LAUNCH_BATCH
+  LAUNCH_CHECK("k_batch_rollout");
+  return seq.ok();
+}
+
+int mdr_batch_obs(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const double* p_dev, float* obs,
+                  void* stream) {
+  if (!c || !sp || !sc || !obs) return fail(MDR_EARG, "mdr_batch_obs: null argument");
+  if (int rc = batch_ready(c, "mdr_batch_obs")) return rc;
+  if (int rc = check_obs_spec(sp, "mdr_batch_obs")) return rc;
+  if (sp->comm_mode != MDR_COMM_RING || sp->halo_msg || sp->msg_all)
+    return fail(MDR_EARG, "mdr_batch_obs: the ring (neighbours) topology inside each cluster only");
+  ObsArgs o = obs_args(c, sp, nullptr);
+  const int lo = sp->n_comm / 2, hi = (sp->n_comm + 1) / 2;
+  const size_t tile = ((size_t)kObsBlock * sp->n_feat + 3) & ~(size_t)3;
+  const size_t msg = (size_t)(lo + kObsBlock + hi) * o.msg_w;
+  const size_t bytes = (tile + msg) * sizeof(float);
+  if (bytes > 160 * 1024) return fail(MDR_EARG, "mdr_batch_obs: obs row too wide for one LDS tile");
+  if (c->batch.n_envs > 65535) return fail(MDR_EARG, "mdr_batch_obs: more than 65,535 clusters (the grid's second dimension)");
+  hipStream_t st = S(stream);
+  static_assert(sizeof(mdr_obs_scalars) == 4 * sizeof(double), "the scalars are staged as rows of 4 doubles");
+  if (int rc = batch_reserve(c->d_batch_sc, (size_t)c->batch.n_envs * 4, "d_batch_sc")) return rc;
+  HIP_TRY(hipMemcpyAsync(c->d_batch_sc, sc, (size_t)c->batch.n_envs * sizeof(mdr_obs_scalars), hipMemcpyHostToDevice,
+                         st));
+  hipLaunchKernelGGL(k_batch_obs, dim3(blocks(c->batch.env_len, kObsBlock), (unsigned)c->batch.n_envs), dim3(kObsBlock),
+                     bytes, st, c->kp, o, c->batch, c->d_batch_sc.get(), p_dev, obs);
+  LAUNCH_CHECK("k_batch_obs");
   return MDR_OK;
 }
 
@@ -2323,7 +2447,7 @@ extern "C" {
 
 int mdr_ctrl_greedy(mdr_ctx* c, double budget, uint8_t* action, void* stream) {
   if (!c || !action) return fail(MDR_EARG, "mdr_ctrl_greedy: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_ctrl_greedy: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_ctrl_greedy")) return rc_;
   const bool keys_ready = c->v.take_keys() && c->g_cap >= c->kp.n;  // (the last step's epilogue wrote them)
   enter_writer(c);
   Sequence seq(c->v);
@@ -2624,7 +2748,7 @@ int mdr_greedy_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* action
                        double* reward, int64_t rew_stride, double* p_out, void* stream) {
   if (!c || (n > 0 && (!ticks || !action || !reward))) return fail(MDR_EARG, "mdr_greedy_rollout: null argument");
   if (n < 0 || act_stride < 0 || rew_stride < 0) return fail(MDR_EARG, "mdr_greedy_rollout: negative size");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_rollout: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_greedy_rollout")) return rc_;
   if (c->world > 1)  // (a shard-local decision and step would use shard-local counts: per-tick loop)
     return fail(MDR_ESTATE, "mdr_greedy_rollout: single-GPU only (sharded contexts: the per-tick greedy + step loop)");
   return greedy_rollout_seq(c, n, ticks, action, act_stride, reward, rew_stride, p_out, nullptr, stream);
@@ -2639,7 +2763,7 @@ int mdr_greedy_rollout_stats(mdr_ctx* c, int n, const mdr_tick* ticks, uint8_t* 
   if (n > 0 && !stats) return fail(MDR_EARG, "mdr_greedy_rollout_stats: null stats rows (mdr_greedy_rollout writes none)");
   if (!c || (n > 0 && (!ticks || !action || !reward)))
     return fail(MDR_EARG, "mdr_greedy_rollout_stats: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_rollout_stats: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_greedy_rollout_stats")) return rc_;
   if (int rc = check_tick_stats_ctx(c, "mdr_greedy_rollout_stats")) return rc;
   if (n == 0) return MDR_OK;
   if (int rc = rows_scratch(c)) return rc;
@@ -2674,7 +2798,7 @@ static double greedy_pmin(const mdr_ctx* c) {
 
 int mdr_gq_shard_begin(mdr_ctx* c, void* stream) {
   if (!c) return fail(MDR_EARG, "mdr_gq_shard_begin: null context");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_gq_shard_begin: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_gq_shard_begin")) return rc_;
   if (c->kp.n_cap > 4) return fail(MDR_EARG, "mdr_gq_shard_begin: more than 4 capacity classes (use the all-gather form)");
   const bool keys_ready = c->v.take_keys() && c->g_cap >= c->kp.n;
   enter_writer(c);
@@ -2760,7 +2884,7 @@ int mdr_rccl_allgather(mdr_ctx* c, const void* send, void* recv, int64_t bytes, 
 
 int mdr_greedy_inputs(mdr_ctx* c, double* key, double* power, uint8_t* lock, void* stream) {
   if (!c || !key || !power || !lock) return fail(MDR_EARG, "mdr_greedy_inputs: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_greedy_inputs: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_greedy_inputs")) return rc_;
   hipLaunchKernelGGL(k_greedy_inputs, dim3(blocks(c->kp.n, 256)), dim3(256), 0, S(stream), c->kp, key, power, lock);
   LAUNCH_CHECK("k_greedy_inputs");
   return MDR_OK;
@@ -2806,6 +2930,7 @@ int mdr_rccl_unique_id(uint8_t* id128) {
 int mdr_rccl_init(mdr_ctx* c, const uint8_t* id128, int world, int rank) {
   if (!c || !id128 || world < 1 || rank < 0 || rank >= world) return fail(MDR_EARG, "mdr_rccl_init: bad argument");
   if (c->host.allreduce) return fail(MDR_ESTATE, "mdr_rccl_init: the context already has host collectives");
+  if (c->batch.n_envs) return fail(MDR_ESTATE, "mdr_rccl_init: the context holds a batch of clusters (one GPU)");
   HIP_TRY(hipSetDevice(c->cfg.device));
   ncclUniqueId id;
   memcpy(&id, id128, 128);
@@ -2821,6 +2946,7 @@ int mdr_comm_host(mdr_ctx* c, int world, int rank, mdr_host_allreduce_fn allredu
   if (!c || !allreduce || !sendrecv || world < 1 || rank < 0 || rank >= world)
     return fail(MDR_EARG, "mdr_comm_host: bad argument");
   if (c->comm) return fail(MDR_ESTATE, "mdr_comm_host: the context already has an RCCL communicator");
+  if (c->batch.n_envs) return fail(MDR_ESTATE, "mdr_comm_host: the context holds a batch of clusters (one GPU)");
   HIP_TRY(hipSetDevice(c->cfg.device));
   if (!c->comm_stream) HIP_TRY(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
   c->host.allreduce = allreduce;
@@ -2921,7 +3047,7 @@ static int rollout_sharded_stats_path(mdr_ctx* c, int mode, const std::string& w
 int mdr_rollout_sharded_stats_path(mdr_ctx* c, int mode) {
   const char* const who = "mdr_rollout_sharded_stats";
   if (!c) return fail(MDR_EARG, "mdr_rollout_sharded_stats_path: null ctx");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_rollout_sharded_stats_path: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_rollout_sharded_stats_path")) return rc_;
   if (!has_comm(c)) return fail(MDR_ESTATE, std::string(who) + ": no communicator (mdr_rccl_init / mdr_comm_host)");
   if (!check_mode(mode)) return fail(MDR_EARG, "mdr_rollout_sharded_stats_path: bad action source");
   if (win_common(c)) return fail(MDR_EARG, std::string(who) + ": common penalty modes need the per-step API");
@@ -3032,7 +3158,7 @@ int mdr_set_rollout_window(mdr_ctx* c, int ticks) {
 
 int mdr_cluster_stats(mdr_ctx* c, const double* reward, double* out, void* stream) {
   if (!c || !out) return fail(MDR_EARG, "mdr_cluster_stats: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_cluster_stats: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_cluster_stats")) return rc_;
   if (int rc = dev_reserve(c->d_stats, (size_t)kStats * kStatsBlocks, "d_stats")) return rc;
   const unsigned nb = (unsigned)std::min<int64_t>(kStatsBlocks, (c->kp.n + 255) / 256);
   hipLaunchKernelGGL(k_cluster_stats, dim3(nb), dim3(256), 0, S(stream), c->kp, reward, c->d_stats);
@@ -3478,7 +3604,7 @@ int mdr_actor_act(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc,
                   void* stream) {
   enter_writer(c);
   if (!c || !sp || !sc) return fail(MDR_EARG, "mdr_actor_act: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_act: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_actor_act")) return rc_;
   if (int rc = check_actor_obs(c, sp, "mdr_actor_act", S(stream))) return rc;
   hipStream_t st = S(stream);
   Sequence seq(c->v);
@@ -3496,7 +3622,7 @@ int mdr_actor_act(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc,
 int mdr_actor_profile(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_obs_scalars* sc, const double* p_dev,
                       double* cycles_out, void* stream) {
   if (!c || !sp || !sc || !cycles_out) return fail(MDR_EARG, "mdr_actor_profile: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_actor_profile: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_actor_profile")) return rc_;
   if (int rc = check_actor_obs(c, sp, "mdr_actor_profile", S(stream))) return rc;
   hipStream_t st = S(stream);
   const int nb = c->n_cu * 16;  // waves (at most 16 per block, one block per CU)
@@ -3572,7 +3698,7 @@ int mdr_tick_stats(mdr_ctx* c, const double* reward, const double* p_dev, double
                    void* stream) {
   if (!out16) return fail(MDR_EARG, "mdr_tick_stats: null out16");
   if (!c) return fail(MDR_EARG, "mdr_tick_stats: null ctx");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_tick_stats: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_tick_stats")) return rc_;
   if (int rc = check_tick_stats_ctx(c, "mdr_tick_stats")) return rc;
   if (int rc = tick_scratch(c)) return rc;
   return launch_tick_stats(c, reward, p_dev, p_host, out16, S(stream));
@@ -3656,7 +3782,7 @@ int mdr_stats_exchange_ranks(mdr_ctx* c, int world, int rank) {
 static int check_stats_exchange(mdr_ctx* c, int m, const char* who) {
   if (!c) return fail(MDR_EARG, std::string(who) + ": null ctx");
   if (m < 1) return fail(MDR_EARG, std::string(who) + ": m < 1");
-  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (int rc_ = cluster_ready(c, std::string(who))) return rc_;
   if (!ctx_sharded(c))
     return fail(MDR_ESTATE, std::string(who) + ": neither a communicator nor a shard (single shard: mdr_tick_stats)");
   return MDR_OK;
@@ -3742,7 +3868,7 @@ int mdr_snapshot(mdr_ctx* c, const mdr_snap* sn, int row, const mdr_obs_scalars*
   if (sn)
     if (int rc = check_snap_struct(sn, "mdr_snapshot")) return rc;
   if (!c || !sn || !sc) return fail(MDR_EARG, "mdr_snapshot: null argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_snapshot: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_snapshot")) return rc_;
   if (int rc = check_snap(c, sn, row, 1, "mdr_snapshot")) return rc;
   return launch_snap(c, sn, row, nullptr, p_dev, *sc, S(stream));
 }
@@ -3752,7 +3878,7 @@ int mdr_obs_gather(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn, int r
   if (sn)
     if (int rc = check_snap_struct(sn, "mdr_obs_gather")) return rc;
   if (!c || !sp || !sn || m < 0 || (m > 0 && (!idx || !obs))) return fail(MDR_EARG, "mdr_obs_gather: bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, "mdr_obs_gather: context not bound");
+  if (int rc_ = cluster_ready(c, "mdr_obs_gather")) return rc_;
   if (int rc = check_obs_spec(sp, "mdr_obs_gather")) return rc;
   if (sp->halo_msg || sp->msg_all) return fail(MDR_EARG, "mdr_obs_gather: single shard only (halo_msg / msg_all set)");
   if (int rc = check_snap(c, sn, 0, rows, "mdr_obs_gather")) return rc;
@@ -3813,7 +3939,7 @@ int mdr_snapshot_sharded(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* sn,
   if (hl)
     if (int rc = check_snap_halo_struct(hl, who)) return rc;
   if (!c || !sp || !sn || !sc) return fail(MDR_EARG, std::string(who) + ": null argument");
-  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (int rc_ = cluster_ready(c, std::string(who))) return rc_;
   if (!ctx_sharded(c)) return fail(MDR_ESTATE, std::string(who) + ": not a shard and no communicator (mdr_snapshot)");
   if (int rc = check_obs_spec(sp, who)) return rc;
   const int K = sp->n_comm, M = mdr_msg_width(sp), lo = K / 2, hi = (K + 1) / 2;
@@ -3842,7 +3968,7 @@ int mdr_obs_gather_sharded(mdr_ctx* c, const mdr_obs_spec* sp, const mdr_snap* s
   if (hl)
     if (int rc = check_snap_halo_struct(hl, who)) return rc;
   if (!c || !sp || !sn || m < 0 || (m > 0 && (!idx || !obs))) return fail(MDR_EARG, std::string(who) + ": bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, std::string(who) + ": context not bound");
+  if (int rc_ = cluster_ready(c, std::string(who))) return rc_;
   if (!ctx_sharded(c)) return fail(MDR_ESTATE, std::string(who) + ": not a shard and no communicator (mdr_obs_gather)");
   if (int rc = check_obs_spec(sp, who)) return rc;
   if (sp->halo_msg || sp->msg_all)
@@ -3900,7 +4026,7 @@ static int actor_rollout_preamble(mdr_ctx* c, const ActorRolloutArgs& a, int fla
   if (!shd && a.stats && (rc = check_stats_rows(who, a.n, a.stats_rows, a.stats_row0))) return rc;
   const bool ptrs = a.ticks && a.osc && a.sp && a.reward && a.p_dev;
   if (!c || !ptrs || a.n < 1) return fail(MDR_EARG, base + ": bad argument");
-  if (!c->bound) return fail(MDR_ESTATE, base + ": context not bound");
+  if (int rc_ = cluster_ready(c, base)) return rc_;
   if (shd && !has_comm(c)) return fail(MDR_ESTATE, base + ": no communicator (mdr_rccl_init / mdr_comm_host)");
   const bool halo = shd && actor_halo(c, a.sp);
   if (a.snap && !shd && (rc = check_snap(c, a.snap, a.row0, a.n, who))) return rc;

@@ -418,6 +418,23 @@ __global__ void k_gq_remap(KParams p, const double* part, int nparts, unsigned* 
                            double* kmin_out, double* scale_out);
 void gqf_sel_init(void* sel, uint32_t* map);  // host: the fused record (both parities' cells = gq_sel_init's)
 void gqf_diag_of(const void* sel, uint64_t* out);  // host: {calls, band hits, misses, exact, last mode, last window}
+// ---- environment batches (mdr_batch_set / mdr_batch_rollout / mdr_batch_obs)
+constexpr int kBatchWaves = 8;                   // waves of a k_batch_rollout block at most: a tile of 128 houses each
+constexpr int kBatchMaxLen = 128 * kBatchWaves;  // houses per cluster at most (one workgroup)
+struct BatchArgs {
+  int n_envs, env_len, stride;  // cluster e = elements [e * stride, e * stride + env_len); stride % 128 == 0
+  const uint64_t* seeds;        // [n_envs] the clusters' Philox keys (device, context-owned)
+};
+__global__ void k_batch_refresh(KParams p, BatchArgs b, int* params_bad);
+// grid n_envs, 64 * ceil(env_len / 128) threads; ticks: device [n_envs][nt]; action / reward rows of
+// n_envs * stride elements (cluster e at e * stride), advancing by act_stride / rew_stride per tick;
+// p_out [n_envs] <- every cluster's power of the last tick
+template <int ACT>
+__global__ void k_batch_rollout(KParams p, BatchArgs b, const TickArgs* ticks, int nt, const uint8_t* action,
+                                int64_t act_stride, double* reward, int64_t rew_stride, double* p_out);
+// grid (ceil(env_len / kObsBlock), n_envs), kObsBlock threads, k_obs's dynamic LDS; sc: device
+// [n_envs][4] {p, s, solar, t_od}; p_dev: [n_envs] or null; obs: [n_envs][env_len][n_feat]
+__global__ void k_batch_obs(KParams p, ObsArgs o, BatchArgs b, const double* sc, const double* p_dev, float* obs);
 __global__ void k_greedy_inputs(KParams p, double* key, double* power, uint8_t* lock);
 __global__ void k_greedy_iota(int64_t n, int* idx);
 __global__ void k_greedy_gather_rows(int64_t n, const int* perm, const double* power, const uint8_t* lock,

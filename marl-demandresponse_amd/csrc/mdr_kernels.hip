@@ -5074,4 +5074,183 @@ __global__ void k_greedy_apply(int64_t n, const int* __restrict__ perm, const in
   action[perm[j]] = take ? 1 : 0;
 }
 
+// --------------------------------------------------------------------------------------- batch
+// E independent clusters of env_len <= 1,024 houses in one context (mdr_batch_set):
+// cluster e is elements [e * stride, e * stride + env_len) of the bound arrays, stride a multiple of
+// 128, so every wave tile of Tile2 is 128-aligned inside its cluster.  A block works on ONE cluster
+// through that cluster's own view of the context (batch_member): the pieces of the one-tick step
+// (Tile2 ... house_tick) and of the obs row (mdr_obs_dev.h) then run on it as on a stand-alone
+// context of env_len houses with that cluster's Philox key — their statements are not restated here.
+
+// the view of cluster e: its slice of every array, n = n_global = env_len, ids from 0, its own seed
+__device__ __forceinline__ KParams batch_member(const KParams& p, const BatchArgs& b, uint32_t e) {
+  KParams q = p;
+  const size_t base = (size_t)e * (size_t)b.stride;
+  q.n = q.n_global = b.env_len;
+  q.goff = 0;
+  q.seed = b.seeds[e];
+  q.t_air = p.t_air + base; q.t_mass = p.t_mass + base; q.hvac = p.hvac + base;
+  q.ua = p.ua + base; q.ca = p.ca + base; q.cm = p.cm + base; q.hm = p.hm + base;
+  q.target = p.target + base; q.cap_idx = p.cap_idx + base;
+  return q;
+}
+
+// k_refresh over the clusters' houses only (the pad elements hold nothing)
+__global__ void __launch_bounds__(256) k_batch_refresh(KParams p, BatchArgs b, int* params_bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.n || (int)(i % b.stride) >= b.env_len) return;
+  const bool ok = in_pow2_range(p.ua[i], -20, 20) && in_pow2_range(p.ca[i], -10, 50) &&
+                  in_pow2_range(p.cm[i], -10, 50) && in_pow2_range(p.hm[i], -10, 50);
+  if (!ok) atomicOr(params_bad, 1);
+}
+
+// the lane's pair of rewards into a row (store_tile2's reward stores, without the state)
+__device__ __forceinline__ void store_rew2(double* __restrict__ row, uint32_t i0, const bool (&valid)[2],
+                                           const double (&rw)[2]) {
+  if (valid[1]) sto_nt(row, i0 * 8u, make_double2(rw[0], rw[1]));
+  else if (valid[0]) __builtin_nontemporal_store(rw[0], row + i0);
+}
+
+// A whole rollout call of the batch in ONE launch: block e steps cluster e through its nt ticks,
+// wave w owning the cluster's tile w (two houses per lane), state and parameters in registers from
+// the first tick to the last.  The only cross-house quantity of a tick — the ON houses per capacity
+// class, which give the cluster power — stays inside the block: every wave leaves its tile's class
+// counts in its own LDS row (plain stores: nothing to zero), one barrier, and every wave adds the
+// rows up (integers: any order).  The rows are double-buffered by tick parity: a wave that runs ahead
+// into tick t + 1 writes the other buffer, and cannot reach tick t + 2 before every wave has passed
+// the barrier of tick t + 1, i.e. has finished reading tick t's rows.  A one-wave block takes its
+// counts from the ballots and has no barrier.  Per tick, in k_step_t's order: action (pick_action on
+// the pre-step state), house_tick, P in ascending class order, signal_term with the cluster's own
+// size, deadband_l2 on the new air temperature, reward_individual.  individual_L2 only.
+template <int ACT>
+__global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, BatchArgs b,
+                                                                    const TickArgs* __restrict__ ticks, int nt,
+                                                                    const uint8_t* __restrict__ action,
+                                                                    int64_t act_stride, double* __restrict__ reward,
+                                                                    int64_t rew_stride, double* __restrict__ p_out) {
+  __shared__ unsigned cnt[2][kBatchWaves][MDR_MAX_CAP];
+  const uint32_t e = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const uint32_t tile = (uint32_t)tid >> 6;
+  const int nwave = (int)(blockDim.x >> 6);
+  const KParams q = batch_member(p, b, e);
+  const size_t base = (size_t)e * (size_t)b.stride;
+  const TickArgs* __restrict__ tke = ticks + (size_t)e * (size_t)nt;
+  const uint32_t n = (uint32_t)b.env_len;
+  const uint32_t i0 = tile * 128u + (uint32_t)lane * 2u;
+  const bool valid[2] = {i0 < n, i0 + 1 < n};
+
+  Tile2 in;
+  load_tile2<false>(q, nullptr, i0, n, tile2_full(tile, n), in);
+  double T[2] = {in.T.x, in.T.y}, Tm[2] = {in.Tm.x, in.Tm.y};
+  uint32_t w[2] = {in.w.x, in.w.y};
+  const double ua[2] = {in.ua.x, in.ua.y}, ca[2] = {in.ca.x, in.ca.y}, cm[2] = {in.cm.x, in.cm.y};
+  const double hm[2] = {in.hm.x, in.hm.y}, tg[2] = {in.tg.x, in.tg.y};
+  const int cls[2] = {(int)(in.cls & 0xFF), (int)((in.cls >> 8) & 0xFF)};
+  const double q_cls[2] = {q.q_on[cls[0]], q.q_on[cls[1]]};
+  const bool params_ok = !*q.params_bad && q.fast_tick_ok;
+
+  double P = 0.0;
+  for (int t = 0; t < nt; ++t) {
+    const TickArgs tk = tke[t];  // uniform in the block
+    const uint8_t* act_row = action + base + (int64_t)t * act_stride;  // (read under MDR_ACT_BUFFER only)
+    bool rnd[2] = {false, false}, rnd1[2] = {false, false};
+    if (ACT == MDR_ACT_RANDOM) tile_random(q, tile, i0, tk.tick, rnd, rnd1);
+    // shared-reciprocal division only where it is provably the IEEE quotient (k_step_t's gate)
+    const bool tile_fast = params_ok && fast_tick_ok(tk.t_od_prev, tk.solar) && tile2_fast_ok(T, Tm);
+
+    double Tn[2], Tmn[2];
+    uint32_t wn[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool a = valid[h] && pick_action(ACT, act_row, i0 + h, rnd[h], T[h], tg[h], q.deadband, w[h]);
+      house_tick(q, tk, tile_fast, a, q_cls[h], w[h], T[h], Tm[h], ua[h], ca[h], cm[h], hm[h], wn[h], Tn[h], Tmn[h]);
+    }
+    const bool on[2] = {valid[0] && hv_on(wn[0]), valid[1] && hv_on(wn[1])};
+
+    // ---- the cluster power of the tick
+    P = 0.0;
+    if (nwave == 1) {
+      for (int k = 0; k < q.n_cap; ++k) {
+        const unsigned long long c = (unsigned long long)(__popcll(__ballot(on[0] && cls[0] == k)) +
+                                                          __popcll(__ballot(on[1] && cls[1] == k)));
+        P += (double)c * q.p_on[k];
+      }
+    } else {
+      unsigned(*row)[MDR_MAX_CAP] = cnt[t & 1];
+      for (int k = 0; k < q.n_cap; ++k) {
+        const unsigned c = (unsigned)__popcll(__ballot(on[0] && cls[0] == k)) +
+                           (unsigned)__popcll(__ballot(on[1] && cls[1] == k));
+        if (lane == 0) row[tile][k] = c;
+      }
+      __syncthreads();
+      for (int k = 0; k < q.n_cap; ++k) {
+        unsigned long long c = 0;
+        for (int v = 0; v < nwave; ++v) c += row[v][k];
+        P += (double)c * q.p_on[k];
+      }
+    }
+    const double sig_term = signal_term(q, P, tk.s_prev);
+
+    double rw[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      rw[h] = reward_individual(q, deadband_l2(tg[h], q.deadband, Tn[h]), sig_term);
+      T[h] = Tn[h]; Tm[h] = Tmn[h]; w[h] = wn[h];
+    }
+    store_rew2(reward + base + (int64_t)t * rew_stride, i0, valid, rw);
+  }
+
+  const double none[2] = {0.0, 0.0};
+  store_tile2(q, i0, valid, T, Tm, w, false, nullptr, none);
+  if (tid == 0) p_out[e] = P;
+}
+
+#define MDR_INST_BATCH(A)                                                                                  \
+  template __global__ void k_batch_rollout<A>(KParams, BatchArgs, const TickArgs*, int, const uint8_t*, int64_t, \
+                                              double*, int64_t, double*);
+MDR_INST_BATCH(MDR_ACT_BUFFER)
+MDR_INST_BATCH(MDR_ACT_RANDOM)
+MDR_INST_BATCH(MDR_ACT_ALWAYS_ON)
+MDR_INST_BATCH(kActBangBang)
+MDR_INST_BATCH(kActDeadband)
+
+// norm_state_dict rows of a batch, float32 [E][env_len][F]: block (x, e) builds houses [128 x, ..) of
+// cluster e from that cluster's view and its own obs scalars (sc[e] = {p, s, solar, t_od}; p_dev,
+// when given, overrides p with the device P of each cluster).  Ring messages wrap inside the cluster
+// (obs_stage_ring on the member view); no block straddles two clusters.
+__global__ void __launch_bounds__(kObsBlock) k_batch_obs(KParams p, ObsArgs o, BatchArgs b,
+                                                         const double* __restrict__ sc,
+                                                         const double* __restrict__ p_dev,
+                                                         float* __restrict__ obs) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const uint32_t e = blockIdx.y;
+  const KParams q = batch_member(p, b, e);
+  o.p = sc[4 * e]; o.s = sc[4 * e + 1]; o.solar = sc[4 * e + 2]; o.t_od = sc[4 * e + 3];
+  const int F = o.n_feat;
+  const int64_t b0 = (int64_t)blockIdx.x * kObsBlock;
+  const int nb = (int)min((int64_t)kObsBlock, q.n - b0);
+  float* tile = smem;                                  // [kObsBlock][F]
+  float* msg = smem + ((kObsBlock * F + 3) & ~3);      // [lo + kObsBlock + hi][M]
+  __shared__ float cf[kObsConst];
+  obs_consts(q, o, p_dev ? p_dev[e] : o.p, cf, threadIdx.x, kObsBlock);
+  __syncthreads();
+  const ObsDiv dv = obs_div(q);
+  obs_stage_ring(q, o, b0, nb, cf, msg, threadIdx.x, kObsBlock, dv);
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < nb) obs_build_row(q, o, b0 + t, t, cf, msg, tile + t * F, dv);
+  __syncthreads();
+  const int64_t nflt = (int64_t)nb * F;
+  float* dst = obs + ((int64_t)e * b.env_len + b0) * F;
+  if ((((uintptr_t)dst) & 15) == 0) {
+    const int64_t n4 = nflt >> 2;
+    for (int64_t x = threadIdx.x; x < n4; x += kObsBlock)
+      reinterpret_cast<float4*>(dst)[x] = reinterpret_cast<const float4*>(tile)[x];
+    for (int64_t x = (n4 << 2) + threadIdx.x; x < nflt; x += kObsBlock) dst[x] = tile[x];
+  } else {
+    for (int64_t x = threadIdx.x; x < nflt; x += kObsBlock) dst[x] = tile[x];
+  }
+}
+
 }  // namespace mdr

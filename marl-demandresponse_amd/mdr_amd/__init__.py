@@ -7,11 +7,11 @@ constructing an ``Environment`` loads the library and fails loudly if it (or a G
 from . import config
 from .config import EnvironmentProperties
 
-__all__ = ["Environment", "EnvironmentProperties", "config", "load_library", "DeviceDQN", "DQNConfig",
+__all__ = ["Environment", "EnvBatch", "EnvironmentProperties", "config", "load_library", "DeviceDQN", "DQNConfig",
            "ReplayStore", "make_qnet"]
 
 # names imported on first use (their modules pull in torch): name -> module
-_LAZY = {"Environment": "environment", "DeviceDQN": "dqn", "DQNConfig": "dqn", "ReplayStore": "replay",
+_LAZY = {"Environment": "environment", "EnvBatch": "batch", "DeviceDQN": "dqn", "DQNConfig": "dqn", "ReplayStore": "replay",
          "make_qnet": "actor"}
 
 

@@ -237,6 +237,12 @@ SIGNATURES = {
     "mdr_rollout_sharded_stats_path": (I, [VP, I]),
     "mdr_actor_rollout_sharded_stats": (I, [VP, I, VP, VP, P(mdr_obs_spec), VP, I64, VP, I64, VP, I64, VP,
                                             P(mdr_snap), P(mdr_snap_halo), I, VP, I64, I64, VP]),
+    # environment batches: seeds const uint64_t* (host), ticks const mdr_tick* (host [n_envs][n_ticks]),
+    # sc const mdr_obs_scalars* (host [n_envs])
+    "mdr_batch_stride": (C.c_size_t, [I64]),
+    "mdr_batch_set": (I, [VP, C.c_int32, C.c_int32, VP]),
+    "mdr_batch_rollout": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP]),
+    "mdr_batch_obs": (I, [VP, P(mdr_obs_spec), VP, VP, VP, VP]),
     "mdr_probe_stream": (I, [VP, VP, VP]),
     "mdr_div_check": (I, [VP, VP, I64, VP, VP]),
     "mdr_event_record": (I, [VP, I, VP]),
