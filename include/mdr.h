@@ -990,6 +990,30 @@ int mdr_batch_set(mdr_ctx* ctx, int32_t n_envs, int32_t env_len, const uint64_t*
 int mdr_batch_rollout(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
                       int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
                       double* p_out, void* stream);
+/* mdr_batch_rollout with stats rows and / or returns out of the same ONE launch (k_batch_eval); state,
+ * FSM words, p_out and the pad elements exactly as mdr_batch_rollout leaves them.
+ *   reward   device rows as in mdr_batch_rollout, or NULL: no reward row is written.
+ *   weights  host [n_envs][n_ticks], staged behind the tick records in the same context-owned buffer;
+ *   returns  device [n_envs * S] in the batch layout, 16-byte aligned.  Both or neither.  Per house of
+ *            cluster e, for t = 0 .. n_ticks - 1: returns[i] = returns[i] + weights[e][t] * r_i(t), one
+ *            multiply and one add, r_i(t) with the bits the reward row would hold; on top of the contents.
+ *            reward and returns exclude each other.
+ *   stats    device [n_envs][stats_cap][16], or NULL: row stats_row0 + t of cluster e is mdr_tick_stats'
+ *            16 doubles of that cluster after tick t (slots 0..11 with N = env_len, slot 12 the tick's
+ *            P, slots 13..15 written as 0).  Order of every sum: a lane starts every slot at 0.0 and adds
+ *            house 128 w + 2 l, then 128 w + 2 l + 1 (wave w, lane l; houses >= env_len add nothing);
+ *            the 64 lanes of a wave combine by the xor butterfly 32, 16, ..., 1, v = v + v[l ^ off]
+ *            (slot 2: fmax, from 0.0); the waves are added in ascending w, starting from wave 0's value.
+ *            stats alone (no reward, no returns) is allowed: the rows form without its reward stores.
+ * At least one of reward / returns / stats.  reward alone is mdr_batch_rollout's launch.
+ * MDR_EARG (before anything is staged or launched): null ticks / p_out, n_ticks < 1, an unknown source,
+ * MDR_ACT_BUFFER without actions, all three outputs NULL, reward together with returns, exactly one of
+ * weights / returns, stats_row0 < 0 or stats_row0 + n_ticks > stats_cap, a misaligned reward or
+ * returns, an odd rew_stride.  MDR_ESTATE: no mdr_batch_set. */
+int mdr_batch_rollout_eval(mdr_ctx* ctx, int n_ticks, const mdr_tick* ticks, const uint8_t* action,
+                           int64_t act_stride, int action_mode, double* reward, int64_t rew_stride,
+                           const double* weights, double* returns, double* stats, int stats_cap,
+                           int stats_row0, double* p_out, void* stream);
 /* float32 obs[n_envs][env_len][n_feat]: mdr_obs of every cluster, MDR_COMM_RING only (the ring wraps
  * inside the cluster).  sc: host [n_envs], each cluster's scalars; p_dev, when non-NULL, overrides
  * sc[e].p with the device doubles [n_envs] mdr_batch_rollout wrote.  MDR_EARG: MDR_COMM_TABLE, a

@@ -2278,6 +2278,33 @@ int mdr_batch_set(mdr_ctx* c, int32_t n_envs, int32_t env_len, const uint64_t* s
   return MDR_OK;
 }
 
+// refresh_if_dirty over the clusters' houses (the pads hold nothing)
+static int batch_refresh_if_dirty(mdr_ctx* c, hipStream_t st) {
+  if (!c->v.coef_dirty()) return MDR_OK;
+  HIP_TRY(hipMemsetAsync(c->d_flags, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_batch_refresh, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp, c->batch, c->d_flags);
+  LAUNCH_CHECK("k_batch_refresh");
+  c->v.coef_refreshed();
+  return MDR_OK;
+}
+static_assert(sizeof(TickArgs) == sizeof(mdr_tick), "mdr_tick records are copied as TickArgs");
+
+// k_batch_rollout<A> for a run-time source
+static void launch_batch_rollout(int mode, dim3 grid, dim3 block, hipStream_t st, const KParams& kp, const BatchArgs& b,
+                                 const TickArgs* tk, int n, const uint8_t* action, int64_t act_stride, double* reward,
+                                 int64_t rew_stride, double* p_out) {
+#define MDR_LAUNCH_BATCH(A) \
+  hipLaunchKernelGGL((k_batch_rollout<A>), grid, block, 0, st, kp, b, tk, n, action, act_stride, reward, rew_stride, p_out)
+  switch (mode) {
+    case MDR_ACT_BUFFER: MDR_LAUNCH_BATCH(MDR_ACT_BUFFER); break;
+    case MDR_ACT_RANDOM: MDR_LAUNCH_BATCH(MDR_ACT_RANDOM); break;
+    case MDR_ACT_ALWAYS_ON: MDR_LAUNCH_BATCH(MDR_ACT_ALWAYS_ON); break;
+    case MDR_ACT_BANGBANG: MDR_LAUNCH_BATCH(kActBangBang); break;
+    default: MDR_LAUNCH_BATCH(kActDeadband); break;
+  }
+#undef MDR_LAUNCH_BATCH
+}
+
 int mdr_batch_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride, int mode,
                       double* reward, int64_t rew_stride, double* p_out, void* stream) {
   enter_writer(c);
@@ -2292,28 +2319,82 @@ int mdr_batch_rollout(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* a
   const size_t nrec = (size_t)c->batch.n_envs * (size_t)n;
   if (int rc = batch_reserve(c->d_batch_ticks, nrec, "d_batch_ticks")) return rc;
   Sequence seq(c->v, Sequence::kRollout);
-  if (c->v.coef_dirty()) {  // refresh_if_dirty over the clusters' houses (the pads hold nothing)
-    HIP_TRY(hipMemsetAsync(c->d_flags, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_batch_refresh, dim3(blocks(c->kp.n, 256)), dim3(256), 0, st, c->kp, c->batch, c->d_flags);
-    LAUNCH_CHECK("k_batch_refresh");
-    c->v.coef_refreshed();
-  }
+  if (int rc = batch_refresh_if_dirty(c, st)) return rc;
   // stream order: an earlier launch reading d_batch_ticks on st precedes this write
-  static_assert(sizeof(TickArgs) == sizeof(mdr_tick), "mdr_tick records are copied as TickArgs");
   HIP_TRY(hipMemcpyAsync(c->d_batch_ticks, ticks, nrec * sizeof(TickArgs), hipMemcpyHostToDevice, st));
   const dim3 grid((unsigned)c->batch.n_envs), block(64u * blocks(c->batch.env_len, 128));
-#define MDR_LAUNCH_BATCH(A)                                                                                      \
-  hipLaunchKernelGGL((k_batch_rollout<A>), grid, block, 0, st, c->kp, c->batch, c->d_batch_ticks.get(), n, action, \
-                     act_stride, reward, rew_stride, p_out)
-  switch (mode) {
-    case MDR_ACT_BUFFER: MDR_LAUNCH_BATCH(MDR_ACT_BUFFER); break;
-    case MDR_ACT_RANDOM: MDR_LAUNCH_BATCH(MDR_ACT_RANDOM); break;
-    case MDR_ACT_ALWAYS_ON: MDR_LAUNCH_BATCH(MDR_ACT_ALWAYS_ON); break;
-    case MDR_ACT_BANGBANG: MDR_LAUNCH_BATCH(kActBangBang); break;
-    default: MDR_LAUNCH_BATCH(kActDeadband); break;
-  }
-#undef MDR_LAUNCH_BATCH
+  launch_batch_rollout(mode, grid, block, st, c->kp, c->batch, c->d_batch_ticks.get(), n, action, act_stride, reward,
+                       rew_stride, p_out);
   LAUNCH_CHECK("k_batch_rollout");
+  return seq.ok();
+}
+
+// k_batch_eval<A, F> for a run-time source and form (F = 1 .. 3)
+extern "C++" template <int F>
+static void launch_batch_eval(int mode, dim3 grid, dim3 block, hipStream_t st, const KParams& kp, const BatchArgs& b,
+                              const TickArgs* tk, int n, const uint8_t* action, int64_t act_stride, double* reward,
+                              int64_t rew_stride, double* p_out, const BatchEval& ev) {
+#define MDR_LAUNCH_EVAL(A)                                                                                       \
+  hipLaunchKernelGGL((k_batch_eval<A, F>), grid, block, 0, st, kp, b, tk, n, action, act_stride, reward, rew_stride, \
+                     p_out, ev)
+  switch (mode) {
+    case MDR_ACT_BUFFER: MDR_LAUNCH_EVAL(MDR_ACT_BUFFER); break;
+    case MDR_ACT_RANDOM: MDR_LAUNCH_EVAL(MDR_ACT_RANDOM); break;
+    case MDR_ACT_ALWAYS_ON: MDR_LAUNCH_EVAL(MDR_ACT_ALWAYS_ON); break;
+    case MDR_ACT_BANGBANG: MDR_LAUNCH_EVAL(kActBangBang); break;
+    default: MDR_LAUNCH_EVAL(kActDeadband); break;
+  }
+#undef MDR_LAUNCH_EVAL
+}
+
+int mdr_batch_rollout_eval(mdr_ctx* c, int n, const mdr_tick* ticks, const uint8_t* action, int64_t act_stride, int mode,
+                           double* reward, int64_t rew_stride, const double* weights, double* returns, double* stats,
+                           int stats_cap, int stats_row0, double* p_out, void* stream) {
+  const char* const who = "mdr_batch_rollout_eval";
+  enter_writer(c);
+  // what needs no context first, so each refusal names its argument (all before any HIP call)
+  if (!c || !ticks || !p_out) return fail(MDR_EARG, std::string(who) + ": null ctx, ticks or p_out");
+  if (n < 1) return fail(MDR_EARG, std::string(who) + ": n_ticks < 1");
+  if (!check_mode(mode)) return fail(MDR_EARG, std::string(who) + ": unknown action source");
+  if (mode == MDR_ACT_BUFFER && !action) return fail(MDR_EARG, std::string(who) + ": a buffer source without actions");
+  if (!reward && !returns && !stats)
+    return fail(MDR_EARG, std::string(who) + ": no output (reward, returns and stats all null)");
+  if (!weights != !returns) return fail(MDR_EARG, std::string(who) + ": weights and returns go together");
+  if (reward && returns) return fail(MDR_EARG, std::string(who) + ": reward rows and returns exclude each other");
+  if (stats && (stats_row0 < 0 || stats_cap < 0 || stats_row0 > stats_cap - n))
+    return fail(MDR_EARG, std::string(who) + ": stats_row0 .. stats_row0 + n_ticks outside [0, stats_cap)");
+  if (((uintptr_t)reward & 15) || (reward && (rew_stride & 1)))
+    return fail(MDR_EARG, std::string(who) + ": reward rows must be 16-byte aligned (an even rew_stride)");
+  if ((uintptr_t)returns & 15) return fail(MDR_EARG, std::string(who) + ": returns must be 16-byte aligned");
+  if (int rc = batch_ready(c, who)) return rc;
+  if ((int64_t)c->batch.n_envs * n > ((int64_t)1 << 27)) return fail(MDR_EARG, std::string(who) + ": n_envs * n_ticks > 2^27");
+  hipStream_t st = S(stream);
+  // the tick records, then (returns forms) the weights, in one context-owned buffer of 32-byte records
+  const size_t nrec = (size_t)c->batch.n_envs * (size_t)n;
+  const size_t wrec = returns ? (nrec + 3) / 4 : 0;
+  if (int rc = batch_reserve(c->d_batch_ticks, nrec + wrec, "d_batch_ticks")) return rc;
+  Sequence seq(c->v, Sequence::kRollout);
+  if (int rc = batch_refresh_if_dirty(c, st)) return rc;
+  // stream order: an earlier launch reading d_batch_ticks on st precedes these writes
+  HIP_TRY(hipMemcpyAsync(c->d_batch_ticks, ticks, nrec * sizeof(TickArgs), hipMemcpyHostToDevice, st));
+  double* const d_wts = reinterpret_cast<double*>(c->d_batch_ticks.get() + nrec);
+  if (returns) HIP_TRY(hipMemcpyAsync(d_wts, weights, nrec * sizeof(double), hipMemcpyHostToDevice, st));
+  const dim3 grid((unsigned)c->batch.n_envs), block(64u * blocks(c->batch.env_len, 128));
+  const BatchEval ev{returns ? d_wts : nullptr, returns, stats, stats_cap, stats_row0};
+  // rows alone are k_batch_rollout's; stats alone is the rows + stats form without a reward row
+  const int form = (stats ? kBatchStats : 0) | (returns ? kBatchRet : 0);
+  const TickArgs* const tk = c->d_batch_ticks.get();
+  if (form == 0)
+    launch_batch_rollout(mode, grid, block, st, c->kp, c->batch, tk, n, action, act_stride, reward, rew_stride, p_out);
+  else if (form == kBatchStats)
+    launch_batch_eval<kBatchStats>(mode, grid, block, st, c->kp, c->batch, tk, n, action, act_stride, reward, rew_stride,
+                                   p_out, ev);
+  else if (form == kBatchRet)
+    launch_batch_eval<kBatchRet>(mode, grid, block, st, c->kp, c->batch, tk, n, action, act_stride, nullptr, 0, p_out, ev);
+  else
+    launch_batch_eval<kBatchStats | kBatchRet>(mode, grid, block, st, c->kp, c->batch, tk, n, action, act_stride, nullptr, 0,
+                                               p_out, ev);
+  LAUNCH_CHECK(form ? "k_batch_eval" : "k_batch_rollout");
   return seq.ok();
 }
 

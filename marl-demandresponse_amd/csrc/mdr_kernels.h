@@ -432,6 +432,19 @@ __global__ void k_batch_refresh(KParams p, BatchArgs b, int* params_bad);
 template <int ACT>
 __global__ void k_batch_rollout(KParams p, BatchArgs b, const TickArgs* ticks, int nt, const uint8_t* action,
                                 int64_t act_stride, double* reward, int64_t rew_stride, double* p_out);
+// k_batch_rollout's other output forms (mdr_batch_rollout_eval): FORM = kBatchStats, kBatchRet or both
+constexpr int kBatchStats = 1;  // one kTickRow stats row per cluster and tick (with reward rows unless kBatchRet)
+constexpr int kBatchRet = 2;    // no reward row: every house's weighted return accumulated in a register
+struct BatchEval {
+  const double* wts;  // kBatchRet: device [n_envs][nt], cluster e's weight of tick t
+  double* returns;    // kBatchRet: [n_envs * stride] in the batch layout, 16-byte aligned
+  double* stats;      // kBatchStats: [n_envs][cap][kTickRow]; the call's rows are row0 .. row0 + nt - 1
+  int cap, row0;
+};
+// the same launch geometry and arguments; under kBatchStats alone a null reward writes no reward row
+template <int ACT, int FORM>
+__global__ void k_batch_eval(KParams p, BatchArgs b, const TickArgs* ticks, int nt, const uint8_t* action,
+                             int64_t act_stride, double* reward, int64_t rew_stride, double* p_out, BatchEval ev);
 // grid (ceil(env_len / kObsBlock), n_envs), kObsBlock threads, k_obs's dynamic LDS; sc: device
 // [n_envs][4] {p, s, solar, t_od}; p_dev: [n_envs] or null; obs: [n_envs][env_len][n_feat]
 __global__ void k_batch_obs(KParams p, ObsArgs o, BatchArgs b, const double* sc, const double* p_dev, float* obs);

@@ -2645,8 +2645,9 @@ __device__ __forceinline__ void tick_acc(double (&a)[kStats], double T, double T
   a[11] += hv_on(w) ? 1.0 : 0.0;
 }
 
-// a[] of the block's 256 threads -> the block's values in threads 0 .. kStats-1 (return value)
-__device__ __forceinline__ double tick_block_reduce(double (&a)[kStats], double (*sh)[4]) {
+// a[] of the wave's 64 lanes -> the wave's values in every lane: the xor butterfly 32, 16, ..., 1
+// (slot 2 by fmax)
+__device__ __forceinline__ void tick_wave_reduce(double (&a)[kStats]) {
   // butterfly step outermost: the twelve exchanges of a step are independent and in flight
   // together (slot-major, the 72 steps form one chain of cross-lane latencies)
 #pragma unroll
@@ -2657,6 +2658,11 @@ __device__ __forceinline__ double tick_block_reduce(double (&a)[kStats], double 
 #pragma unroll
     for (int k = 0; k < kStats; ++k) a[k] = k == 2 ? fmax(a[k], o[k]) : a[k] + o[k];
   }
+}
+
+// a[] of the block's 256 threads -> the block's values in threads 0 .. kStats-1 (return value)
+__device__ __forceinline__ double tick_block_reduce(double (&a)[kStats], double (*sh)[4]) {
+  tick_wave_reduce(a);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (lane == 0)
 #pragma unroll
@@ -5122,13 +5128,65 @@ __device__ __forceinline__ void store_rew2(double* __restrict__ row, uint32_t i0
 // counts from the ballots and has no barrier.  Per tick, in k_step_t's order: action (pick_action on
 // the pre-step state), house_tick, P in ascending class order, signal_term with the cluster's own
 // size, deadband_l2 on the new air temperature, reward_individual.  individual_L2 only.
-template <int ACT>
-__global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, BatchArgs b,
-                                                                    const TickArgs* __restrict__ ticks, int nt,
-                                                                    const uint8_t* __restrict__ action,
-                                                                    int64_t act_stride, double* __restrict__ reward,
-                                                                    int64_t rew_stride, double* __restrict__ p_out) {
+//
+// Output forms (FORM, bit flags; k_batch_rollout is form 0, k_batch_eval the other three):
+//   0                         reward rows
+//   kBatchStats               reward rows (none when `reward` is null) and one stats row per cluster and tick
+//   kBatchRet                 no reward row: ret = ret + w[e][t] * r(t) per house in a register, one multiply
+//                             and one add (never fused), loaded from `returns` before the first tick and
+//                             stored after the last; w[e][t] uniform in the block (scalar loads)
+//   kBatchStats | kBatchRet   both, still no reward row
+// State, FSM words, p_out and the pad elements are the same in every form, and r(t) has the bits form 0
+// writes.
+//
+// Stats row (kBatchStats): mdr_tick_stats' kTickRow doubles of cluster e after tick t, at
+// stats[(e * cap + row0 + t) * kTickRow + k].  Slots 0..11 are tick_acc<true> over the cluster's valid
+// houses with the post-step Tn, Tmn, the target, the post-step word, the tick's reward and N = env_len;
+// slot 12 the tick's P; slots 13..15 are written as 0.  Order of every sum (the contract): a lane starts
+// every slot at 0.0 and adds house i0, then i0 + 1 (pad lanes add nothing); the 64 lanes of a wave by
+// tick_wave_reduce's xor butterfly 32, 16, ..., 1 (slot 2: fmax, from 0.0); the block's waves in
+// ascending wave index, from wave 0's value.  A one-wave block takes the butterfly's value directly:
+// lanes 0..15 store the row in the tick, no barrier.
+// Multi-wave blocks: slot 4 needs the reward, hence P, so a wave's partials exist only behind the tick's
+// count barrier B(t).  Lane 0 of every wave leaves them in part[t & 1][wave], next to the count rows and
+// under the same parity; wave 0 adds them up and stores row t behind B(t + 1), and the last row behind
+// one barrier after the loop: one barrier per tick as before, plus that one.  Every wave wrote part[t & 1]
+// before it arrived at B(t + 1), so the reader sees all of it.  The next writes to that buffer are tick
+// t + 2's, behind B(t + 2), which no wave passes before wave 0 has arrived there, i.e. has finished
+// reading row t: a wave running ahead cannot overwrite a row still being read.
+
+// row of a multi-wave block from the waves' partials pt[wave][slot] (lanes 0..kTickRow-1 of one wave)
+__device__ __forceinline__ void batch_stats_row(const double (*pt)[kStats], int nwave, int lane, double P,
+                                                double* __restrict__ row) {
+  if (lane >= kTickRow) return;
+  double v = 0.0;
+  if (lane < kStats) {
+    v = pt[0][lane];
+    for (int w = 1; w < nwave; ++w) v = lane == 2 ? fmax(v, pt[w][lane]) : v + pt[w][lane];
+  } else if (lane == kStats) {
+    v = P;
+  }
+  row[lane] = v;
+}
+
+// row of a one-wave block from the butterfly's values (every lane holds a[]; lane k keeps slot k)
+__device__ __forceinline__ void batch_stats_row1(const double (&a)[kStats], int lane, double P,
+                                                 double* __restrict__ row) {
+  double v = lane == kStats ? P : 0.0;
+#pragma unroll
+  for (int k = 0; k < kStats; ++k) v = lane == k ? a[k] : v;
+  if (lane < kTickRow) row[lane] = v;
+}
+
+template <int ACT, int FORM>
+__device__ __forceinline__ void batch_rollout_body(const KParams& p, const BatchArgs& b,
+                                                   const TickArgs* __restrict__ ticks, int nt,
+                                                   const uint8_t* __restrict__ action, int64_t act_stride,
+                                                   double* __restrict__ reward, int64_t rew_stride,
+                                                   double* __restrict__ p_out, const BatchEval& ev) {
+  constexpr bool STATS = (FORM & kBatchStats) != 0, RET = (FORM & kBatchRet) != 0;
   __shared__ unsigned cnt[2][kBatchWaves][MDR_MAX_CAP];
+  __shared__ double part[STATS ? 2 : 1][STATS ? kBatchWaves : 1][kStats];  // (form 0 and kBatchRet: unused)
   const uint32_t e = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const uint32_t tile = (uint32_t)tid >> 6;
@@ -5149,10 +5207,25 @@ __global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, B
   const int cls[2] = {(int)(in.cls & 0xFF), (int)((in.cls >> 8) & 0xFF)};
   const double q_cls[2] = {q.q_on[cls[0]], q.q_on[cls[1]]};
   const bool params_ok = !*q.params_bad && q.fast_tick_ok;
+  double ret[2] = {0.0, 0.0};                                        // RET: the lane's pair of returns
+  const double* __restrict__ wte = nullptr;                          // RET: w[e][.], uniform in the block
+  double* __restrict__ srow = nullptr;                               // STATS: the cluster's row of tick 0
+  const double Nd = (double)b.env_len;
+  if constexpr (RET) {
+    wte = ev.wts + (size_t)e * (size_t)nt;
+    if (valid[1]) {
+      const double2 r2 = ldo<double2>(ev.returns + base, i0 * 8u);
+      ret[0] = r2.x; ret[1] = r2.y;
+    } else if (valid[0]) {
+      ret[0] = ev.returns[base + i0];
+    }
+  }
+  if constexpr (STATS) srow = ev.stats + ((size_t)e * (size_t)ev.cap + (size_t)ev.row0) * kTickRow;
 
   double P = 0.0;
   for (int t = 0; t < nt; ++t) {
     const TickArgs tk = tke[t];  // uniform in the block
+    [[maybe_unused]] const double P_prev = P;  // STATS: slot 12 of the row finished behind this tick's barrier
     const uint8_t* act_row = action + base + (int64_t)t * act_stride;  // (read under MDR_ACT_BUFFER only)
     bool rnd[2] = {false, false}, rnd1[2] = {false, false};
     if (ACT == MDR_ACT_RANDOM) tile_random(q, tile, i0, tk.tick, rnd, rnd1);
@@ -5184,6 +5257,8 @@ __global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, B
         if (lane == 0) row[tile][k] = c;
       }
       __syncthreads();
+      if constexpr (STATS)  // the previous tick's row, behind this tick's barrier (see above)
+        if (t > 0 && tile == 0) batch_stats_row(part[(t - 1) & 1], nwave, lane, P_prev, srow + (size_t)(t - 1) * kTickRow);
       for (int k = 0; k < q.n_cap; ++k) {
         unsigned long long c = 0;
         for (int v = 0; v < nwave; ++v) c += row[v][k];
@@ -5198,12 +5273,62 @@ __global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, B
       rw[h] = reward_individual(q, deadband_l2(tg[h], q.deadband, Tn[h]), sig_term);
       T[h] = Tn[h]; Tm[h] = Tmn[h]; w[h] = wn[h];
     }
-    store_rew2(reward + base + (int64_t)t * rew_stride, i0, valid, rw);
+    if constexpr (RET) {
+      const double wt = wte[t];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) ret[h] = ret[h] + wt * rw[h];
+    } else if (!STATS || reward) {
+      store_rew2(reward + base + (int64_t)t * rew_stride, i0, valid, rw);
+    }
+    if constexpr (STATS) {
+      double a[kStats];
+#pragma unroll
+      for (int k = 0; k < kStats; ++k) a[k] = 0.0;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        if (valid[h]) tick_acc<true>(a, T[h], Tm[h], tg[h], w[h], rw[h], Nd);
+      tick_wave_reduce(a);
+      if (nwave == 1) {
+        batch_stats_row1(a, lane, P, srow + (size_t)t * kTickRow);
+      } else if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kStats; ++k) part[t & 1][tile][k] = a[k];
+      }
+    }
   }
 
+  if constexpr (STATS)
+    if (nwave > 1) {  // the last tick's row
+      __syncthreads();
+      if (tile == 0) batch_stats_row(part[(nt - 1) & 1], nwave, lane, P, srow + (size_t)(nt - 1) * kTickRow);
+    }
   const double none[2] = {0.0, 0.0};
   store_tile2(q, i0, valid, T, Tm, w, false, nullptr, none);
+  if constexpr (RET) {
+    if (valid[1]) sto(ev.returns + base, i0 * 8u, make_double2(ret[0], ret[1]));
+    else if (valid[0]) ev.returns[base + i0] = ret[0];
+  }
   if (tid == 0) p_out[e] = P;
+}
+
+template <int ACT>
+__global__ void __launch_bounds__(64 * kBatchWaves) k_batch_rollout(KParams p, BatchArgs b,
+                                                                    const TickArgs* __restrict__ ticks, int nt,
+                                                                    const uint8_t* __restrict__ action,
+                                                                    int64_t act_stride, double* __restrict__ reward,
+                                                                    int64_t rew_stride, double* __restrict__ p_out) {
+  batch_rollout_body<ACT, 0>(p, b, ticks, nt, action, act_stride, reward, rew_stride, p_out, BatchEval{});
+}
+
+// the forms with stats rows and / or returns (mdr_batch_rollout_eval); FORM != 0
+template <int ACT, int FORM>
+__global__ void __launch_bounds__(64 * kBatchWaves) k_batch_eval(KParams p, BatchArgs b,
+                                                                 const TickArgs* __restrict__ ticks, int nt,
+                                                                 const uint8_t* __restrict__ action, int64_t act_stride,
+                                                                 double* __restrict__ reward, int64_t rew_stride,
+                                                                 double* __restrict__ p_out, BatchEval ev) {
+  static_assert(FORM >= 1 && FORM <= (kBatchStats | kBatchRet), "form 0 is k_batch_rollout");
+  batch_rollout_body<ACT, FORM>(p, b, ticks, nt, action, act_stride, reward, rew_stride, p_out, ev);
 }
 
 #define MDR_INST_BATCH(A)                                                                                  \
@@ -5214,6 +5339,17 @@ MDR_INST_BATCH(MDR_ACT_RANDOM)
 MDR_INST_BATCH(MDR_ACT_ALWAYS_ON)
 MDR_INST_BATCH(kActBangBang)
 MDR_INST_BATCH(kActDeadband)
+
+#define MDR_INST_BATCH_EVAL(A, F)                                                                             \
+  template __global__ void k_batch_eval<A, F>(KParams, BatchArgs, const TickArgs*, int, const uint8_t*, int64_t, \
+                                              double*, int64_t, double*, BatchEval);
+#define MDR_INST_BATCH_FORMS(A) \
+  MDR_INST_BATCH_EVAL(A, kBatchStats) MDR_INST_BATCH_EVAL(A, kBatchRet) MDR_INST_BATCH_EVAL(A, kBatchStats | kBatchRet)
+MDR_INST_BATCH_FORMS(MDR_ACT_BUFFER)
+MDR_INST_BATCH_FORMS(MDR_ACT_RANDOM)
+MDR_INST_BATCH_FORMS(MDR_ACT_ALWAYS_ON)
+MDR_INST_BATCH_FORMS(kActBangBang)
+MDR_INST_BATCH_FORMS(kActDeadband)
 
 // norm_state_dict rows of a batch, float32 [E][env_len][F]: block (x, e) builds houses [128 x, ..) of
 // cluster e from that cluster's view and its own obs scalars (sc[e] = {p, s, solar, t_od}; p_dev,

@@ -8,11 +8,11 @@ from . import config
 from .config import EnvironmentProperties
 
 __all__ = ["Environment", "EnvBatch", "EnvironmentProperties", "config", "load_library", "DeviceDQN", "DQNConfig",
-           "ReplayStore", "make_qnet"]
+           "ReplayStore", "make_qnet", "BatchRolloutStats", "evaluate_batch"]
 
 # names imported on first use (their modules pull in torch): name -> module
 _LAZY = {"Environment": "environment", "EnvBatch": "batch", "DeviceDQN": "dqn", "DQNConfig": "dqn", "ReplayStore": "replay",
-         "make_qnet": "actor"}
+         "make_qnet": "actor", "BatchRolloutStats": "services", "evaluate_batch": "services"}
 
 
 def load_library():

@@ -242,6 +242,8 @@ SIGNATURES = {
     "mdr_batch_stride": (C.c_size_t, [I64]),
     "mdr_batch_set": (I, [VP, C.c_int32, C.c_int32, VP]),
     "mdr_batch_rollout": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP]),
+    # weights const double* (host [n_envs][n_ticks]); returns / stats device doubles
+    "mdr_batch_rollout_eval": (I, [VP, I, VP, VP, I64, I, VP, I64, VP, VP, VP, I, I, VP, VP]),
     "mdr_batch_obs": (I, [VP, P(mdr_obs_spec), VP, VP, VP, VP]),
     "mdr_probe_stream": (I, [VP, VP, VP]),
     "mdr_div_check": (I, [VP, VP, I64, VP, VP]),

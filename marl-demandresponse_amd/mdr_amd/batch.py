@@ -30,7 +30,7 @@ import numpy as np
 from . import _lib as L
 from . import config as cfgmod
 from . import population as popmod
-from .environment import ACTION_MODES, Environment
+from .environment import ACTION_MODES, Environment, discount_weights
 from .shard import HipShard, decode_hvac
 
 MAX_LEN = 1024  # MDR_BATCH_MAX_LEN: a cluster is stepped by one workgroup
@@ -236,18 +236,19 @@ class EnvBatch:
         self._sync_power(ids)
 
     # ------------------------------------------------------------------ stepping
-    def rollout(self, n_ticks: int, action_mode: str = "random", actions=None, rewards=None):
-        """``n_ticks`` steps of every cluster in one launch.  Returns the float64 rewards ``[n_ticks, E,
-        N_c]`` (``rewards`` from ``empty_rewards(n_ticks)``, allocated if None); with a buffer from
-        ``empty_rewards(None)`` the last tick's ``[E, N_c]``.  ``action_mode='buffer'``: ``actions`` from
-        ``empty_actions(n_ticks)``.  Per cluster bit for bit the stand-alone ``step_tensor(None,
-        action_mode=c, lookahead=c)`` loop.  Every argument is checked before any member's drivers
-        advance.  The host side is one ``driver_window`` call per member."""
+    def empty_returns(self):
+        """Zero-filled float64 ``[E, N_c]`` returns for ``rollout_returns``.  A view of padded storage."""
         import torch
 
-        n_ticks = int(n_ticks)
-        if n_ticks < 1:
+        return self._view(torch.zeros(self.n_envs * self.stride, dtype=torch.float64, device=self.device))
+
+    def _check_source(self, n_ticks, action_mode: str, actions):
+        """(n_ticks, mode, act_stride) of a rollout call's tick count and action source, checked."""
+        import torch
+
+        if int(n_ticks) != n_ticks or n_ticks < 1:
             raise ValueError("rollout needs n_ticks >= 1")
+        n_ticks = int(n_ticks)
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}")
         mode = ACTION_MODES[action_mode]
@@ -262,6 +263,30 @@ class EnvBatch:
                 act_stride = self.n_envs * self.stride
         elif actions is not None:
             raise ValueError(f"action_mode={action_mode!r} takes no actions tensor")
+        return n_ticks, mode, act_stride
+
+    def _check_stats(self, stats, n_ticks: int) -> int:
+        """The first of the call's rows in ``stats`` (services.BatchRolloutStats), after checking that
+        they are this batch's and that ``n_ticks`` more fit; nothing is appended."""
+        if stats is None:
+            return 0
+        if getattr(stats, "batch", None) is not self:
+            raise ValueError("the stats rows belong to another batch (services.BatchRolloutStats(batch, capacity))")
+        return stats.begin_rows(n_ticks)  # (ValueError: overflow)
+
+    def rollout(self, n_ticks: int, action_mode: str = "random", actions=None, rewards=None, stats=None):
+        """``n_ticks`` steps of every cluster in one launch.  Returns the float64 rewards ``[n_ticks, E,
+        N_c]`` (``rewards`` from ``empty_rewards(n_ticks)``, allocated if None); with a buffer from
+        ``empty_rewards(None)`` the last tick's ``[E, N_c]``.  ``action_mode='buffer'``: ``actions`` from
+        ``empty_actions(n_ticks)``.  Per cluster bit for bit the stand-alone ``step_tensor(None,
+        action_mode=c, lookahead=c)`` loop.  ``stats`` (``services.BatchRolloutStats`` of this batch): the
+        same launch also writes every cluster's ``mdr_tick_stats`` row of every tick (k_batch_eval).
+        Every argument, the stats capacity included, is checked before any member's drivers advance.
+        The host side is one ``driver_window`` call per member."""
+        import torch
+
+        n_ticks, mode, act_stride = self._check_source(n_ticks, action_mode, actions)
+        srow0 = self._check_stats(stats, n_ticks)
         if rewards is None:
             rewards = self.empty_rewards(n_ticks)
         if rewards.dim() == 2:
@@ -271,8 +296,44 @@ class EnvBatch:
             self._check_view(rewards, n_ticks, torch.float64, "rewards")
             rew_stride = self.n_envs * self.stride
         ticks = self._driver_windows(n_ticks)
-        self._launch(ticks, actions, act_stride, mode, rewards, rew_stride)
+        self._launch(ticks, actions, act_stride, mode, rewards, rew_stride, stats=stats, srow0=srow0)
         return rewards
+
+    def rollout_returns(self, n_ticks: int, returns, gamma: float = 1.0, weight0=1.0, actions=None,
+                        action_mode: str = "random", stats=None):
+        """``rollout`` that writes no reward row: every house's weighted rewards of the call's ticks are
+        added to ``returns`` (from ``empty_returns()``, on top of its contents) in a register of the one
+        launch,
+
+            returns[e, i] += w[e][0] r_i(0) + w[e][1] r_i(1) + ...,   w[e] = discount_weights(weight0[e], gamma, n_ticks)
+
+        the sum running left to right, one multiply and one add per tick: the bits of ``ret = ret +
+        w[e][t] * rows[t]`` over ``rollout``'s rows, for every source.  ``weight0``: a scalar, or one value
+        per cluster (members reset independently and sit at different points of their episodes).
+        Returns the float64 ``[E]`` array of ``w[e][n_ticks]``, the ``weight0`` of the next call of a chain.
+        State, FSM words, cluster power, ticks and dates advance exactly as under ``rollout``; ``stats``
+        as there.  ``ValueError``: ``returns`` not from ``empty_returns()``, ``gamma`` outside (0, 1], a
+        non-finite ``weight0`` or one of another length, ``n_ticks < 1``, stats rows of another batch or
+        too few left — all before any member's drivers advance."""
+        import torch
+
+        n_ticks, mode, act_stride = self._check_source(n_ticks, action_mode, actions)
+        if not (isinstance(gamma, (int, float)) and 0.0 < gamma <= 1.0):
+            raise ValueError(f"gamma = {gamma!r} outside (0, 1]")
+        w0 = np.asarray(weight0, np.float64)
+        if w0.ndim == 0:
+            w0 = np.full(self.n_envs, float(w0))
+        if w0.shape != (self.n_envs,):
+            raise ValueError(f"weight0: a scalar or one value per cluster ({self.n_envs}), not shape {w0.shape}")
+        if not np.all(np.isfinite(w0)):
+            raise ValueError(f"weight0 = {weight0!r} is not finite")
+        self._check_view(returns, None, torch.float64, "returns")
+        srow0 = self._check_stats(stats, n_ticks)
+        w = np.stack([discount_weights(float(w0[e]), float(gamma), n_ticks) for e in range(self.n_envs)])
+        ticks = self._driver_windows(n_ticks)
+        self._launch(ticks, actions, act_stride, mode, None, 0, weights=np.ascontiguousarray(w[:, :n_ticks]),
+                     returns=returns, stats=stats, srow0=srow0)
+        return w[:, n_ticks].copy()
 
     def _driver_windows(self, n_ticks: int) -> np.ndarray:
         """Every member's host drivers ``n_ticks`` ahead (``Environment.driver_window``, one call per member)
@@ -285,13 +346,27 @@ class EnvBatch:
             ticks[e] = w.a
         return ticks
 
-    def _launch(self, ticks: np.ndarray, actions, act_stride: int, mode: int, rewards, rew_stride: int) -> None:
-        """mdr_batch_rollout of staged driver windows: the one launch of a rollout call."""
+    def _launch(self, ticks: np.ndarray, actions, act_stride: int, mode: int, rewards, rew_stride: int,
+                weights=None, returns=None, stats=None, srow0: int = 0) -> None:
+        """mdr_batch_rollout of staged driver windows: the one launch of a rollout call
+        (mdr_batch_rollout_eval when it also writes ``stats`` rows, or ``returns`` under the host
+        ``weights`` [E, n_ticks] instead of reward rows)."""
         st = self._store
-        L.check(st.lib.mdr_batch_rollout(st.ctx, ticks.shape[1], ticks.ctypes.data, L.ptr(actions), act_stride, mode,
-                                         L.ptr(rewards), rew_stride, L.ptr(self._p_dev), st.stream()),
-                "mdr_batch_rollout")
-        self._ticks_kept = ticks  # (the host records outlive the call, whatever the copy's staging does)
+        if weights is None and stats is None:
+            L.check(st.lib.mdr_batch_rollout(st.ctx, ticks.shape[1], ticks.ctypes.data, L.ptr(actions), act_stride, mode,
+                                             L.ptr(rewards), rew_stride, L.ptr(self._p_dev), st.stream()),
+                    "mdr_batch_rollout")
+        else:
+            if stats is not None:
+                stats.record_power(srow0)  # (the pre-step P of the call's first tick, before the launch overwrites it)
+            L.check(st.lib.mdr_batch_rollout_eval(
+                st.ctx, ticks.shape[1], ticks.ctypes.data, L.ptr(actions), act_stride, mode, L.ptr(rewards), rew_stride,
+                None if weights is None else weights.ctypes.data, L.ptr(returns),
+                None if stats is None else L.ptr(stats.stats), 0 if stats is None else stats.capacity, srow0,
+                L.ptr(self._p_dev), st.stream()), "mdr_batch_rollout_eval")
+            if stats is not None:  # tick t's post-step signal is tick t + 1's s_prev; the last one's is the grid's
+                stats.commit_rows(ticks, [float(m.power_grid.current_signal) for m in self.members])
+        self._ticks_kept = ticks, weights  # (the host records outlive the call, whatever the copy's staging does)
         for m in self.members:
             m._P_dev_valid = False  # (the members' own p_dev is not written: the batch's [E] vector is)
             m._counts_ready = 0

@@ -12,6 +12,8 @@ per-house UI list is materialised only when read.
                  tick written inside a rollout: ``mdr_tick_stats``)  training_manager.py:242-245,265-295
   ShardedRolloutStats  the same rows on a house-sharded env: the ranks' partial rows of a call, combined by one
                  exact exchange behind it (``rollout_stats_for(env, cap)`` picks the class)
+  BatchRolloutStats  the same rows for every cluster of an ``EnvBatch``, written by the batch's one launch
+  evaluate_batch  ``evaluate_controller`` + ``controller_returns`` for every cluster of a batch, one launch
   UISummary      ClientManagerService  server/app/services/client_manager_service.py:12-245
   ServerLoop     ControllerManager     server/app/services/controller_manager.py:93-260
   evaluate_controller  TrainingManager.test for the bang-bang and greedy-myopic baselines
@@ -221,6 +223,110 @@ class ShardedRolloutStats(RolloutStats):
             self.env.shard.stats_exchange_buffer(m).zero_()
 
 
+class _MemberRows:
+    """One cluster's rows of a ``BatchRolloutStats`` behind ``RolloutStats``' read interface (``rows``,
+    ``host()``, ``prev()``): what ``DeviceMetrics.update_rollout`` and ``evaluation_means`` take."""
+
+    def __init__(self, stats: "BatchRolloutStats", e: int):
+        self._stats, self._e = stats, int(e)
+        self.env = stats.batch.members[self._e]
+
+    @property
+    def rows(self) -> int:
+        return self._stats.rows
+
+    @property
+    def capacity(self) -> int:
+        return self._stats.capacity
+
+    def host(self) -> np.ndarray:
+        return self._stats.host()[self._e]
+
+    def prev(self) -> dict:
+        s, e = self._stats, self._e
+        s.host()
+        return {"reg_signal": np.asarray(s.reg_signal[e], np.float64), "OD_temp": np.asarray(s.od_temp[e], np.float64),
+                "cluster_hvac_power": s._host[1][e], "signal_post": np.asarray(s.signal_post[e], np.float64)}
+
+
+class BatchRolloutStats:
+    """``RolloutStats`` for an ``EnvBatch``: fixed-capacity device storage of one ``mdr_tick_stats`` row
+    per cluster and tick, ``[E, capacity, 16]``, written by the batch's one launch
+    (``EnvBatch.rollout(stats=...)`` / ``rollout_returns(stats=...)``, k_batch_eval) and read by the host
+    once (``host()``).  One allocation holds the rows and the ``[E, capacity]`` pre-step powers: the
+    pre-step power of a call's first tick is copied on the device from ``batch.cluster_power()`` before
+    the launch, without a synchronisation; every later tick's is the previous row's slot 12.
+
+    Per member the host keeps what ``Environment.rollout`` commits from that member's driver window:
+    the pre-step ``reg_signal`` (``s_prev``) and ``OD_temp`` (``t_od_prev``), and the post-step signal
+    (``s_prev[1:]`` and the member's grid signal after the window).  ``member(e)`` is cluster ``e`` behind
+    ``RolloutStats``' read interface.  ``clear()`` forgets every cluster's rows."""
+
+    def __init__(self, batch, capacity_ticks: int):
+        import torch
+
+        if capacity_ticks < 1:
+            raise ValueError("capacity_ticks must be at least 1")
+        self.batch = batch
+        cap = self.capacity = int(capacity_ticks)
+        E = batch.n_envs
+        self._buf = torch.zeros(E * cap * (TICK_ROW + 1), dtype=torch.float64, device=batch.device)
+        self.stats = self._buf[:E * cap * TICK_ROW].view(E, cap, TICK_ROW)
+        self._p_first = self._buf[E * cap * TICK_ROW:].view(E, cap)
+        self.clear()
+
+    def clear(self) -> None:
+        E = self.batch.n_envs
+        self.rows = 0
+        self.reg_signal, self.od_temp, self.signal_post = ([[] for _ in range(E)] for _ in range(3))
+        self._first = []
+        self._host = None
+
+    def begin_rows(self, k: int) -> int:
+        """The first of the next ``k`` rows, after checking that they fit; nothing is appended until
+        ``commit_rows``."""
+        if self.rows + k > self.capacity:
+            raise ValueError(f"BatchRolloutStats: {self.rows} + {k} ticks overflow the capacity of {self.capacity}")
+        return self.rows
+
+    def record_power(self, row: int) -> None:
+        """Every cluster's power before tick ``row`` (the first of a call) from the batch's device
+        vector: an asynchronous device copy on the current stream."""
+        self._p_first[:, row].copy_(self.batch.cluster_power(), non_blocking=True)
+
+    def commit_rows(self, ticks: np.ndarray, signal_after) -> None:
+        """Append the host scalars of the call whose rows were just launched: ``ticks`` the members'
+        driver windows ``[E, k, 4]`` (mdr_tick layout), ``signal_after[e]`` member e's grid signal
+        behind its window."""
+        k = ticks.shape[1]
+        for e in range(self.batch.n_envs):
+            s_prev = ticks[e, :, 2]
+            self.reg_signal[e].extend(float(x) for x in s_prev)
+            self.od_temp[e].extend(float(x) for x in ticks[e, :, 0])
+            self.signal_post[e].extend([float(x) for x in s_prev[1:]] + [float(signal_after[e])])
+        self._first.extend([True] + [False] * (k - 1))
+        self.rows += k
+        self._host = None
+
+    def host(self) -> np.ndarray:
+        """The filled rows as float64 [E, rows, 16] on the host (one download, one synchronisation)."""
+        if self._host is None:
+            h = self._buf.cpu().numpy()
+            E, cap = self.batch.n_envs, self.capacity
+            rows = h[:E * cap * TICK_ROW].reshape(E, cap, TICK_ROW)[:, :self.rows].copy()
+            p_prev = np.empty((E, self.rows), np.float64)
+            p_prev[:, 1:] = rows[:, :-1, S_POWER]
+            first = np.asarray(self._first, bool)
+            p_prev[:, first] = h[E * cap * TICK_ROW:].reshape(E, cap)[:, :self.rows][:, first]
+            self._host = (rows, p_prev)
+        return self._host[0]
+
+    def member(self, e: int) -> _MemberRows:
+        if not 0 <= int(e) < self.batch.n_envs:
+            raise ValueError(f"env id {e} outside [0, {self.batch.n_envs})")
+        return _MemberRows(self, e)
+
+
 def rollout_stats_for(env, capacity_ticks: int):
     """The stats rows class for ``env``: ``ShardedRolloutStats`` for a sharded environment or one with
     a communicator, ``RolloutStats`` otherwise."""
@@ -421,6 +527,43 @@ def controller_returns(env, controller: str, n_ticks: int, gamma: float = 1.0, t
     returns = torch.zeros(ev.n_local, dtype=torch.float64, device=ev.shard.device)
     ev.rollout_returns(n_ticks, returns, gamma=gamma, action_mode=controller)
     return returns, {"Mean test return": float(returns.mean().item()) / n_ticks}
+
+
+EVALUATION_KEYS = ("Mean test return", "Test mean temperature error", "Test mean signal error")
+
+
+def evaluate_batch(batch, controller: str, n_ticks: int, gamma: float = 1.0, stats=None) -> dict:
+    """``evaluate_controller`` and ``controller_returns`` for every cluster of an ``EnvBatch`` at once:
+    the batch is reset, then ONE ``rollout_returns(n_ticks, ..., action_mode=controller, stats=...)`` —
+    one launch, no reward matrix — gives every house's discounted return and every cluster's stats
+    rows.  ``controller``: one of ``RETURNS_CONTROLLERS``.  A batch has no deep copy, so unlike
+    ``evaluate_controller`` this resets ``batch`` ITSELF (every member, each from its own RNG):
+    evaluation batches are built for the purpose.  ``stats``: a ``BatchRolloutStats`` of ``batch``
+    with room for ``n_ticks`` rows to reuse (cleared here), or None.
+
+    Returns ``evaluation_means``' three keys as float64 ``[E]`` arrays (cluster e's value what
+    ``evaluate_controller`` gives its stand-alone twin, the sums regrouped), ``"returns"``: the
+    ``[E, N_c]`` device tensor, and ``"mean"``: the three keys averaged over the clusters."""
+    if controller not in RETURNS_CONTROLLERS:
+        raise ValueError(f"evaluate_batch: controller must be one of {RETURNS_CONTROLLERS}, not {controller!r}")
+    if int(n_ticks) != n_ticks or n_ticks < 1:
+        raise ValueError("n_ticks must be at least 1")
+    if not (isinstance(gamma, (int, float)) and 0.0 < gamma <= 1.0):
+        raise ValueError(f"gamma = {gamma!r} outside (0, 1]")
+    if stats is None:
+        stats = BatchRolloutStats(batch, n_ticks)
+    elif getattr(stats, "batch", None) is not batch or stats.capacity < n_ticks:
+        raise ValueError(f"evaluate_batch: stats must be a BatchRolloutStats of this batch with capacity >= {n_ticks}")
+    batch.reset()
+    stats.clear()
+    returns = batch.empty_returns()
+    batch.rollout_returns(n_ticks, returns, gamma=gamma, action_mode=controller, stats=stats)
+    per = [evaluation_means(stats.member(e).host(), stats.member(e).prev()["signal_post"], batch.n, n_ticks)
+           for e in range(batch.n_envs)]
+    out = {k: np.array([m[k] for m in per], np.float64) for k in EVALUATION_KEYS}
+    out["mean"] = {k: float(np.mean(out[k])) for k in EVALUATION_KEYS}
+    out["returns"] = returns
+    return out
 
 
 def observe(env) -> dict:
